@@ -8,12 +8,17 @@
 
 A "step" = one pass of the hot path over one batch of `--videos-per-step` (default 128; 32 for c5) videos per GPU, inputs already
 resident in HBM: CLIP-ViT-L/14-336 over 128 frames -> SpatialSlotPool -> splice -> Mistral-7B prefill (L = 1967) -> 256 greedy
-decode steps with head switching, then ONE RCCL all-gather of the packed token ids (N > 1).  Prints one JSON line
-(rank 0) with the whole-job videos/sec, the decode tokens/sec, `roofline` = the dominant kernel family of the run (the 256x256
+decode steps with head switching, then ONE RCCL all-gather of the packed token ids (N > 1).
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (rank 0) with the whole-job videos/sec (`value`) and `ms_per_step`;
+`--dump-outputs DIR` also writes what the last timed step returned to its caller (token ids, final heads) as DIR/<name>.npy.
+
+`--full` adds everything else, measured after the timed steps or beside them: the decode tokens/sec, `roofline` = the dominant kernel family of the run (the 256x256
 MFMA GEMM: gemm_ldr_kernel<1> is the top symbol by total time, gemm_w4_kernel<2> its largest single launch; all four ViT shapes are
 bracketed with HIP events inside the timed region), `roofline_hbm` = the dominant HBM-bound kernel of the decode phase (the decode
-attention at the default batch), per-rank timings and host placement (N > 1), and the CPU baseline (the oracle timed on a bounded sample
-on this box's host cores; N = 1 only).
+attention at the default batch), the stage breakdown, per-rank timings and host placement (N > 1), the check that every timed step returned the
+same ids, and the CPU baseline (the oracle timed on a bounded sample on this box's host cores; N = 1 only).  With `--full`, `--config c1` adds its
+CPU leg and the comparison of its ids with the oracle's.
 """
 from __future__ import annotations
 
@@ -32,6 +37,34 @@ sys.path.insert(0, ROOT)
 from trace_amd import config as tcfg, dist as tdist, synth  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float32 (or float64 if it came as float64).  An array larger than its share of
+    DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its rows, with the row indices beside it as <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share - 4096 and a.ndim >= 1:            # (4 KiB left for the two .npy headers)
+            row_bytes = max(1, a.nbytes // max(1, a.shape[0]))
+            n = max(1, min(a.shape[0], (share - 4096) // (row_bytes + 8)))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], size=n, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def ids_array(seqs, n_new: int) -> np.ndarray:
+    """token ids per sequence -> [B, n_new], -1 past a sequence's end"""
+    a = np.full((len(seqs), n_new), -1, dtype=np.float32)
+    for b, s in enumerate(seqs):
+        a[b, :len(s)] = s[:n_new]
+    return a
 
 
 def cpu_baseline(cfg, n_new: int, threads: int) -> dict:
@@ -161,33 +194,37 @@ def run_c1(args) -> None:
         prompt = conv.get_prompt() + "<sync>"
         return tensor, ts, tokenizer_MMODAL_token_all(prompt, tokenizer, return_tensors="pt")
 
-    # ---- CPU leg: the oracle end to end on this box's host cores (no extrapolation)
-    try:
-        cores = len(os.sched_getaffinity(0))
-    except AttributeError:
-        cores = os.cpu_count() or 1
-    threads = max(1, min(32, cores))
-    torch.set_num_threads(threads)
-    tok_cpu, proc_cpu = builder.ByteTokenizer(cfg.vocab_size), builder._image_processor(cfg, ckpt)
+    # ---- CPU leg (--full, or no HIP device): the oracle end to end on this box's host cores (no extrapolation)
+    import shutil
+    cpu_leg = args.full or not torch.cuda.is_available()
     sd = synth.state_dict(cfg)
-    t0 = time.perf_counter()
-    tensor, ts, ids = driver_inputs(tok_cpu, proc_cpu)
-    t_pre_cpu = time.perf_counter() - t0
-    ora = O.Oracle(cfg, {k: v.float() for k, v in sd.items()}, emulate_bf16=False)
-    with torch.no_grad():
-        t0 = time.perf_counter()
-        ids_fp32 = ora.generate(ids, tensor.float(), ts, head=1, max_new_tokens=n_new, eos_token_id=None)
-        t_gen_cpu = time.perf_counter() - t0
-    cpu = {"value": 1.0 / (t_pre_cpu + t_gen_cpu), "unit": "videos/s", "cores": threads, "kind": "port",
-           "sample": f"the whole C1 workload, no extrapolation: file read + PIL/HF preprocessing {t_pre_cpu * 1e3:.0f} ms, oracle fp32 ViT + slot pool + prefill L={len(ids) - 1 + args.frames * cfg.tokens_per_frame} + {n_new} greedy tokens {t_gen_cpu * 1e3:.0f} ms",
-           "decode_tok_s": None, "ids": ids_fp32}
+    pre_len = lambda ids: len(ids) - 1 + args.frames * cfg.tokens_per_frame
     line = {"metric": "videos/sec + decode tok/s, TRACE-7B 128-frame, 1/2/4/8 MI355X", "value": None, "unit": "videos/s", "n_gpus": 0, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"{CONFIGS['c1']['name']}: {args.frames} frames sampled from a 96-frame 160x120 y4m file, prefill L={len(ids) - 1 + args.frames * cfg.tokens_per_frame}, {n_new} greedy tokens, heads=[1], EOS off",
-                       "baseline_config": "c1", "videos_per_step_per_gpu": 1, "frames": args.frames, "new_tokens": n_new,
-                       "model": "tiny-layer geometry of the reference fixtures (hidden 4096, 2 decoder layers, 3-layer CLIP at 56x56), synthetic weights"},
-            "cpu_baseline": cpu}
-    import shutil
+            "config": {"baseline_config": "c1", "videos_per_step_per_gpu": 1, "frames": args.frames, "new_tokens": n_new,
+                       "model": "tiny-layer geometry of the reference fixtures (hidden 4096, 2 decoder layers, 3-layer CLIP at 56x56), synthetic weights"}}
+    workload = lambda ids: (f"{CONFIGS['c1']['name']}: {args.frames} frames sampled from a 96-frame 160x120 y4m file, prefill L={pre_len(ids)}, "
+                            f"{n_new} greedy tokens, heads=[1], EOS off")
+    if cpu_leg:
+        try:
+            cores = len(os.sched_getaffinity(0))
+        except AttributeError:
+            cores = os.cpu_count() or 1
+        threads = max(1, min(32, cores))
+        torch.set_num_threads(threads)
+        tok_cpu, proc_cpu = builder.ByteTokenizer(cfg.vocab_size), builder._image_processor(cfg, ckpt)
+        t0 = time.perf_counter()
+        tensor, ts, ids = driver_inputs(tok_cpu, proc_cpu)
+        t_pre_cpu = time.perf_counter() - t0
+        ora = O.Oracle(cfg, {k: v.float() for k, v in sd.items()}, emulate_bf16=False)
+        with torch.no_grad():
+            t0 = time.perf_counter()
+            ids_fp32 = ora.generate(ids, tensor.float(), ts, head=1, max_new_tokens=n_new, eos_token_id=None)
+            t_gen_cpu = time.perf_counter() - t0
+        line["config"]["workload"] = workload(ids)
+        line["cpu_baseline"] = {"value": 1.0 / (t_pre_cpu + t_gen_cpu), "unit": "videos/s", "cores": threads, "kind": "port",
+                                "sample": f"the whole C1 workload, no extrapolation: file read + PIL/HF preprocessing {t_pre_cpu * 1e3:.0f} ms, oracle fp32 ViT + slot pool + prefill L={pre_len(ids)} + {n_new} greedy tokens {t_gen_cpu * 1e3:.0f} ms",
+                                "decode_tok_s": None, "ids": ids_fp32}
     if not torch.cuda.is_available():
         line["config"]["note"] = "no HIP device visible: CPU leg only (the HIP path has no CPU fallback)"
         print(json.dumps(line), flush=True)
@@ -202,28 +239,32 @@ def run_c1(args) -> None:
         heads = [1]
         out = model.generate(ids_g.unsqueeze(0), attention_mask=None, images_or_videos=[tensor_g], modal_list=["video"], do_sample=False, temperature=0.0,
                              max_new_tokens=n_new, use_cache=True, pad_token_id=tokenizer.eos_token_id, eos_token_id=-1, video_timestamps=[ts_g], heads=heads)
-        return out[0].tolist(), ts_g, tensor_g
+        return out[0].tolist(), ts_g, tensor_g, ids_g
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        ids_hip, ts_g, tensor_g = step()
+        ids_hip, ts_g, tensor_g, ids_g = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # ids: against the oracle that rounds where the engine stores 16-bit values, on the frames the device preprocessing produced
-    ora_b = O.Oracle(cfg, sd, emulate_bf16=(True if el_dtype == torch.bfloat16 else el_dtype))
-    with torch.no_grad():
-        ids_emu, lg = ora_b.generate(ids, tensor_g.float().cpu(), ts_g, head=1, max_new_tokens=n_new, eos_token_id=None, return_logits=True)
-    srt = torch.sort(torch.where(torch.isfinite(lg), lg, torch.full_like(lg, -1e30)), dim=-1, descending=True).values
-    margin = (srt[:, 0] - srt[:, 1]).tolist()
-    first_diff = next((i for i, (a, b) in enumerate(zip(ids_hip, ids_emu)) if a != b), None)
-    V = cfg.vocab_size
-    line.update({"value": args.steps / dt, "n_gpus": 1, "ms_per_step": dt / args.steps * 1e3,
-                 "ids": {"hip": ids_hip, "oracle_16bit_emulating": ids_emu, "oracle_fp32_host_preprocessing": ids_fp32, "equal": ids_hip == ids_emu,
-                         "first_difference": first_diff, "oracle_top2_margin_there": (margin[first_diff] if first_diff is not None else None),
-                         "time_score_head_steps": sum(1 for t in ids_emu if t > V)},
-                 "parsed": parse_output_ids(ids_hip, tokenizer, model)})
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"token_ids": ids_array([ids_hip], n_new)})
+    line["config"].setdefault("workload", workload(ids_g))
+    line.update({"value": args.steps / dt, "n_gpus": 1, "ms_per_step": dt / args.steps * 1e3})
+    if args.full:
+        # ids: against the oracle that rounds where the engine stores 16-bit values, on the frames the device preprocessing produced
+        ora_b = O.Oracle(cfg, sd, emulate_bf16=(True if el_dtype == torch.bfloat16 else el_dtype))
+        with torch.no_grad():
+            ids_emu, lg = ora_b.generate(ids, tensor_g.float().cpu(), ts_g, head=1, max_new_tokens=n_new, eos_token_id=None, return_logits=True)
+        srt = torch.sort(torch.where(torch.isfinite(lg), lg, torch.full_like(lg, -1e30)), dim=-1, descending=True).values
+        margin = (srt[:, 0] - srt[:, 1]).tolist()
+        first_diff = next((i for i, (a, b) in enumerate(zip(ids_hip, ids_emu)) if a != b), None)
+        V = cfg.vocab_size
+        line.update({"ids": {"hip": ids_hip, "oracle_16bit_emulating": ids_emu, "oracle_fp32_host_preprocessing": ids_fp32, "equal": ids_hip == ids_emu,
+                             "first_difference": first_diff, "oracle_top2_margin_there": (margin[first_diff] if first_diff is not None else None),
+                             "time_score_head_steps": sum(1 for t in ids_emu if t > V)},
+                     "parsed": parse_output_ids(ids_hip, tokenizer, model)})
     print(json.dumps(line), flush=True)
     model.engine.close()
     shutil.rmtree(tmp, ignore_errors=True)
@@ -253,7 +294,9 @@ def run_stc(args) -> None:
     cfg = dataclasses.replace(tcfg.trace_7b(T), mm_projector_type="stc_connector", num_hidden_layers=1, vision_num_layers=2)    # the LLM and the tower are not run here
     eng = TraceEngine(cfg, device=0, max_batch=1, max_ctx=2048, max_frames=T, max_new_tokens=8)
     eng.load_weights(synth.iter_weights(cfg, device="cuda"))
-    feats = (torch.randn(T, cfg.vision_patches, cfg.vision_hidden_size, device="cuda") * 1.0).to(torch.bfloat16)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(42)                                    # the same features on every run (--dump-outputs compares runs output for output)
+    feats = (torch.randn(T, cfg.vision_patches, cfg.vision_hidden_size, generator=g, device="cuda") * 1.0).to(torch.bfloat16)
     for _ in range(max(1, args.warmup)):
         out = eng.stc_connector(feats, T)
     torch.cuda.synchronize()
@@ -264,6 +307,8 @@ def run_stc(args) -> None:
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"connector_out": out})
     fl = stc_flops(T, cfg.vision_grid, cfg.mm_hidden_size, cfg.hidden_size)
     gemm_fl = fl["s1_convs"] + fl["sampler"] + fl["s2_convs"] + fl["readout"]
     tf = gemm_fl / (ms * 1e-3) / 1e12
@@ -350,7 +395,14 @@ def main():
                     help="element type: bf16 (BASELINE's configs; libtrace_hip.so) or fp16 (the reference's own inference dtype; libtrace_hip_f16.so)")
     ap.add_argument("--tiny", action="store_true", help="tiny geometry (plumbing check)")
     ap.add_argument("--vit-batch", type=int, default=None, help="frames per ViT call (default: TraceEngine.full_round_frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure: stage breakdown, decode tok/s, roofline probes, per-rank figures, "
+                         "the repeat check of the timed steps' ids, the CPU baseline (c1: the CPU leg and the oracle comparison)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (token ids, final heads; stc: the connector output) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     preset = CONFIGS[args.config]
     if args.frames is None:
         args.frames = preset["frames"]
@@ -421,13 +473,13 @@ def main():
     ranks_seen = [1]
 
     def step():
-        out, _ = eng.generate(videos, ts, prompt, heads, n_new, eos=-1, use_graph=args.graph, forced=forced)
+        out, hd = eng.generate(videos, ts, prompt, heads, n_new, eos=-1, use_graph=args.graph, forced=forced)
         if world > 1 or torch.distributed.is_initialized():
             g = tdist.gather_outputs(out, n_new, B, dev)
             ranks_seen[0] = len(g)
             if len(g) != world or any(len(x) != B for x in g):
                 raise SystemExit(f"bench: the all-gather returned {len(g)} ranks, expected {world}")
-        return out
+        return out, hd
 
     def gather(out):
         if world > 1 or torch.distributed.is_initialized():
@@ -443,19 +495,53 @@ def main():
         if not pipelined or k < 2:
             return [step() for _ in range(k)]
         batch = (videos, ts, prompt, heads, forced)
-        return [gather(o[0]) for o in eng.generate_stream([batch] * k, n_new, eos=-1, use_graph=args.graph)]
+        return [(gather(o[0]), o[1]) for o in eng.generate_stream([batch] * k, n_new, eos=-1, use_graph=args.graph)]
 
     run(args.warmup)
-    eng.set_profile(2)
-    eng.stage_timing(True)               # event pairs around the tower / slot-pool / prefill calls of the batch(es) that have the GPU to themselves
+    if args.full:
+        eng.set_profile(2)
+        eng.stage_timing(True)           # event pairs around the tower / slot-pool / prefill calls of the batch(es) that have the GPU to themselves
     tdist.barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
-    outs = run(args.steps)
+    res = run(args.steps)
     torch.cuda.synchronize()
     dt_local = time.perf_counter() - t0                 # this rank's own K steps (before the closing barrier): the per-rank figure of the line
     tdist.barrier(); torch.cuda.synchronize()
     dt = tdist.max_over_ranks(time.perf_counter() - t0)
-    out = outs[-1]
+    outs = [r[0] for r in res]
+    if args.dump_outputs and rank == 0:                 # what the last timed step returned to rank 0's caller: ids [B, n_new], final heads [B]
+        dump_outputs(args.dump_outputs, {"token_ids": ids_array(outs[-1], n_new), "final_heads": np.asarray(res[-1][1], dtype=np.float32)})
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "videos/sec + decode tok/s, TRACE-7B 128-frame, 1/2/4/8 MI355X",
+            "value": world * B * args.steps / dt, "unit": "videos/s", "n_gpus": world, "rccl_ranks": ranks_seen[0], "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": (("fp8 e4m3 weights in the decoder projections: W8A8 (fp8 MFMA, fp32 accumulate) in the prefill GEMMs, " +
+                       ("weight-only (bf16 activations, bf16 MFMA) in the decode GEMVs" if args.fp8_scheme == "weight_only" else "W8A8 in the decode GEMVs") +
+                       "; bf16 elsewhere (ViT, attention, KV cache, norms, heads)") if args.fp8 else args.dtype), "data": "synthetic",
+            "config": {"workload": ("tiny plumbing check" if args.tiny else
+                                    f"{preset['name'].replace(' bf16', ' ' + args.dtype)}, {args.frames}x336^2 frames, prefill L={L}, {n_new} greedy tokens, heads=[1]"),
+                       "baseline_config": args.config,
+                       "videos_per_step_per_gpu": B, "frames": args.frames, "prefill_len": L, "new_tokens": n_new, "head_schedule": ("forced MR pattern: 14 time + 4 score + 14 text steps per 32 tokens" if preset["schedule"] == "mr" else "forced DVC pattern per event: 14 time + 4 score + 33 text steps") + " (argmax still computed every step)",
+                       "decode_launch": ("hipGraph replay (the roofline_hbm bracket is taken in a short eager pass after the timed region)" if args.graph else "eager"), "parallelism": f"dp{world} (replica per GPU)",
+                       "step_schedule": ("two-stage pipeline over the timed steps: step k's decode on one HIP stream under step k+1's ViT + prefill on another "
+                                         "(fill and drain inside the timed region; the roofline brackets are taken in the fill / drain phases only)"
+                                         if pipelined else "steps strictly one after the other"),
+                       "weights": "random-init (device RNG), reference architecture"},
+            # what the ids of this configuration are worth (profiles/r04_fp8_error_growth.txt: no e4m3 scheme — W8A8, weight-only, 128-k block-scaled —
+            # keeps the 32-layer 13-way time / score decisions within twice the flip count of the reference's own bf16 run; the bf16 / fp16 paths do)
+            "parity": ("fp8 tolerance only: logits within the a-priori e4m3 budget of the bf16 path (tests/test_gpu_fp8.py); about a third of the 13-way time / score "
+                       "arg-max decisions of a random-weight 32-layer stack differ from the reference's — use the bf16 path where ids must match" if args.fp8 else
+                       "reference-anchored: logits inside the reference's own 16-bit-vs-fp32 deviation, 13-way ids bit-exact vs the 16-bit-emulating oracle (tests/test_gpu_*.py)"),
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        eng.close()
+        if torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
+        return
     # every step runs the same inputs through a path whose reductions all have a fixed order: the ids must repeat exactly
     # (checked on every rank; reported in the line as `steps_repeat_exactly` — the run is not aborted: under torchrun one rank leaving would hang the
     # others in the closing collectives, and a throughput measured on a run with one differing sequence is still a throughput; the tests are where
@@ -538,7 +624,6 @@ def main():
     per_rank = tdist.gather_floats([dt_local / args.steps * 1e3, t_enc, t_pre, t_dec / (n_new - 1), t_load, t_one, float(place.get("numa_node", -1))])
 
     if rank == 0:
-        vps = world * B * args.steps / dt
         vit_flops = args.frames * (366.0e9 if not args.tiny else 0.0)
         pre_flops = 2 * 6.979e9 * Ls + 32 * 2 * Ls * Ls * 4096 if not args.tiny else 0.0
         k_ms, k_n, k_bytes = prof_k[2], int(prof_k[3]), prof_k[4]
@@ -568,31 +653,11 @@ def main():
         # the persistent kernel the shapes without a residual run on: gemm_w4.hip (4 waves of 128x128) unless TRACE_GEMM_W4=0 sends them back to gemm_pers.hip
         pers_sym = "gemm_w4_kernel" if use_w4 else "gemm_pers_kernel"
         fold_tag = stat_tag = ""                               # (rounds 3-4 tagged the LayerNorm-fold instantiations here; the fold left the product in round 5)
-        line = {
-            "metric": "videos/sec + decode tok/s, TRACE-7B 128-frame, 1/2/4/8 MI355X",
-            "value": vps, "unit": "videos/s", "n_gpus": world, "rccl_ranks": ranks_seen[0], "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": (("fp8 e4m3 weights in the decoder projections: W8A8 (fp8 MFMA, fp32 accumulate) in the prefill GEMMs, " +
-                       ("weight-only (bf16 activations, bf16 MFMA) in the decode GEMVs" if args.fp8_scheme == "weight_only" else "W8A8 in the decode GEMVs") +
-                       "; bf16 elsewhere (ViT, attention, KV cache, norms, heads)") if args.fp8 else args.dtype), "data": "synthetic",
-            "config": {"workload": ("tiny plumbing check" if args.tiny else
-                                    f"{preset['name'].replace(' bf16', ' ' + args.dtype)}, {args.frames}x336^2 frames, prefill L={Ls}, {n_new} greedy tokens, heads=[1]"),
-                       "baseline_config": args.config,
-                       "videos_per_step_per_gpu": B, "frames": args.frames, "prefill_len": Ls, "new_tokens": n_new, "head_schedule": ("forced MR pattern: 14 time + 4 score + 14 text steps per 32 tokens" if preset["schedule"] == "mr" else "forced DVC pattern per event: 14 time + 4 score + 33 text steps") + " (argmax still computed every step)",
-                       "decode_launch": ("hipGraph replay (the roofline_hbm bracket is taken in a short eager pass after the timed region)" if args.graph else "eager"), "parallelism": f"dp{world} (replica per GPU)",
-                       "step_schedule": ("two-stage pipeline over the timed steps: step k's decode on one HIP stream under step k+1's ViT + prefill on another "
-                                         "(fill and drain inside the timed region; the roofline brackets are taken in the fill / drain phases only)"
-                                         if pipelined else "steps strictly one after the other"),
-                       "weights": "random-init (device RNG), reference architecture"},
+        line.update({
             "per_rank": {**{k: [round(r[i], 4) for r in per_rank] for i, k in enumerate(rank_keys)},
                          "ms_per_step_min_median_max": [float(np.min([r[0] for r in per_rank])), float(np.median([r[0] for r in per_rank])), float(np.max([r[0] for r in per_rank]))],
                          "host_placement_rank0": place,
                          "note": "ms_per_step per rank = that rank's own K steps up to its own synchronize (before the closing barrier); `ms_per_step` of the line is the max over ranks with the barrier; stage times are re-timed per rank after the timed region"},
-            # what the ids of this configuration are worth (profiles/r04_fp8_error_growth.txt: no e4m3 scheme — W8A8, weight-only, 128-k block-scaled —
-            # keeps the 32-layer 13-way time / score decisions within twice the flip count of the reference's own bf16 run; the bf16 / fp16 paths do)
-            "parity": ("fp8 tolerance only: logits within the a-priori e4m3 budget of the bf16 path (tests/test_gpu_fp8.py); about a third of the 13-way time / score "
-                       "arg-max decisions of a random-weight 32-layer stack differ from the reference's — use the bf16 path where ids must match" if args.fp8 else
-                       "reference-anchored: logits inside the reference's own 16-bit-vs-fp32 deviation, 13-way ids bit-exact vs the 16-bit-emulating oracle (tests/test_gpu_*.py)"),
             "steps_repeat_exactly": bool(steps_repeat), **({"steps_repeat_detail": repeat_detail[:12]} if repeat_detail else {}),
             "decode_tok_s": world * B * (n_new - 1) / (t_dec * 1e-3),
             "stages_ms": {"vit_slotpool_per_video": t_enc, "prefill_per_video": t_pre, f"decode_{n_new - 1}_steps_batch{B}": t_dec,
@@ -625,7 +690,7 @@ def main():
                                         ("vit_out_proj", "gemm_ldr_kernel<EPI_RESIDUAL>" + stat_tag, 1024, 1024, prof[13], prof[16]),
                                         ("vit_fc1", pers_sym + "<EPI_QUICKGELU" + fold_tag + ">", 4096, 1024, g_ms, g_gf),
                                         ("vit_fc2", "gemm_ldr_kernel<EPI_RESIDUAL>" + stat_tag, 1024, 4096, prof[14], prof[17]))}},
-        }
+        })
         # dominant HBM-bound kernel of the decode phase
         # whole decode step: algorithmic bytes = the decoder weights once + the heads on the steps that stream them (not counted) + every sequence's KV rows
         kv_step = B * (Ls + n_new / 2.0) * cfg.num_key_value_heads * 128 * 2 * 2 * cfg.num_hidden_layers

@@ -76,13 +76,37 @@ def test_affinity_plan_and_sysfs_parsing(tmp_path):
     assert td.gather_floats([1.5, 2]) == [[1.5, 2.0]]                   # no process group: this rank only
 
 
+def test_dump_outputs_format_and_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 (float64 stays float64), ids padded with -1 past a sequence's end, and an array over its share of the size
+    budget written as a fixed, seeded sample of its rows with the row indices beside it; the files stay inside the budget."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    big = np.arange(4096 * 256, dtype=np.float64).reshape(4096, 256)           # 8 MiB: over its 512 KiB share
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"token_ids": bench.ids_array([[5, 6, 7], [8]], 4), "big": big,
+                                                "t": torch.ones(2, 3, dtype=torch.bfloat16)})
+    ids = np.load(tmp_path / "a" / "token_ids.npy")
+    assert ids.dtype == np.float32 and ids.tolist() == [[5, 6, 7, -1], [8, -1, -1, -1]]
+    t = np.load(tmp_path / "a" / "t.npy")
+    assert t.dtype == np.float32 and t.shape == (2, 3) and (t == 1).all()
+    rows, sample = np.load(tmp_path / "a" / "big_rows.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert sample.dtype == np.float64 and len(rows) == len(np.unique(rows)) == sample.shape[0] > 0 and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(sample, big[rows.astype(np.int64)])
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "b" / "big_rows.npy"))   # the same sample on every run
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 1 << 20
+
+
 def test_c1_cpu_leg_runs_here():
     """BASELINE config 1's CPU leg ("C1 runs fully on CPU end-to-end"): with no HIP device the line still comes out, from the
     oracle alone — clip file -> process_video -> llama_2 prompt -> tokenizer_MMODAL_token_all -> 32 greedy ids starting on the time head."""
     if torch.cuda.is_available():
         import pytest
         pytest.skip("GPU present: tests/test_gpu_bench_launch.py runs both legs")
-    r = _run(["--config", "c1", "--steps", "1", "--warmup", "0"])
+    r = _run(["--config", "c1", "--steps", "1", "--warmup", "0", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 0 and d["value"] is None and "CPU leg only" in d["config"]["note"]

@@ -19,7 +19,7 @@ def test_bench_tiny_under_torchrun():
     env = dict(os.environ, TRACE_FORCE_PG="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiny",
-           "--frames", "4", "--videos-per-step", "3", "--max-new", "12", "--pipeline"]
+           "--frames", "4", "--videos-per-step", "3", "--max-new", "12", "--pipeline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -30,11 +30,34 @@ def test_bench_tiny_under_torchrun():
     assert d["steps_repeat_exactly"] is True, d.get("steps_repeat_detail")
 
 
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline line without the --full figures; --dump-outputs writes what the
+    last timed step returned (ids [B, max_new], final heads [B], float32), and a --full run of the same arguments dumps the same arrays."""
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--tiny", "--frames", "4",
+            "--videos-per-step", "3", "--max-new", "12"]
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[tag] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    d = lines["plain"]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "videos/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 3 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]          # videos/s = 3 videos per step / the time of one timed step
+    assert not {"roofline", "roofline_hbm", "stages_ms", "cpu_baseline", "per_rank", "steps_repeat_exactly"} & set(d)
+    assert "roofline" in lines["full"] and lines["full"]["steps_repeat_exactly"] is True
+    for name, shape in (("token_ids", (3, 12)), ("final_heads", (3,))):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == shape, (name, a.dtype, a.shape)
+        np.testing.assert_array_equal(a, b)
+    assert (np.load(tmp_path / "plain" / "token_ids.npy") >= 0).all()
+
+
 def test_bench_c1_single_clip_from_a_file():
     """BASELINE config 1 on the GPU box: a clip FILE (y4m) -> process_video -> prompt -> generate through the drop-in surface, 8 frames, 32 greedy
     tokens; the ids equal the oracle's (the oracle that rounds where the engine stores bf16) at least up to its first near-tie, the CPU leg (the
     oracle end to end, fp32) is timed beside it, and the line carries the new per-shape roofline fields of the default config's line format."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "2", "--warmup", "1"], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True,
                        timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -21,12 +21,12 @@ cd $R
 python tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write > $O/traffic.json && cp $O/traffic.json profiles/traffic.json; head -6 $O/traffic.json
 python tools/pmc_summary.py $O/pmc_sq $O/pmc_insts > $O/pmc_sq.txt
 python tools/pmc_summary.py $O/pmc_fetch $O/pmc_write > $O/pmc_traffic.txt
-python bench.py --gpus 1 --steps 6 --warmup 2 > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench c2 rc=$?"; cut -c1-1500 $O/bench_c2.json
-python bench.py --steps 3 --warmup 1 --no-pipeline --no-cpu-baseline > $O/bench_c2_seq.json 2> $O/bench_c2_seq.err; echo "bench c2 sequential rc=$?"
-python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.err; echo "bench c4 rc=$?"
-python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c5_fp8.json 2> $O/bench_c5.err; echo "bench c5 rc=$?"
+python bench.py --gpus 1 --steps 6 --warmup 2 --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench c2 rc=$?"; cut -c1-1500 $O/bench_c2.json
+python bench.py --steps 3 --warmup 1 --no-pipeline --no-cpu-baseline --full > $O/bench_c2_seq.json 2> $O/bench_c2_seq.err; echo "bench c2 sequential rc=$?"
+python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline --full > $O/bench_c4.json 2> $O/bench_c4.err; echo "bench c4 rc=$?"
+python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline --full > $O/bench_c5_fp8.json 2> $O/bench_c5.err; echo "bench c5 rc=$?"
 python bench.py --config stc --steps 10 --warmup 2 > $O/bench_stc.json 2> $O/bench_stc.err; echo "bench stc rc=$?"; cat $O/bench_stc.json
-python bench.py --config c1 > $O/bench_c1.json 2> $O/bench_c1.err; echo "bench c1 rc=$?"; cut -c1-600 $O/bench_c1.json
+python bench.py --config c1 --full > $O/bench_c1.json 2> $O/bench_c1.err; echo "bench c1 rc=$?"; cut -c1-600 $O/bench_c1.json
 timeout 400 python tools/pipeline_stress.py --steps 60 --max-new 200 --plan 0 > $O/pipeline_stress.txt 2>&1; echo "stress rc=$?"; tail -3 $O/pipeline_stress.txt
 timeout 300 python tools/gemm_w4_check.py --time > $O/gemm_w4_check.txt 2>&1; echo "w4 check rc=$?"; grep -c "^ok" $O/gemm_w4_check.txt; grep "mismatching" $O/gemm_w4_check.txt
 timeout 300 python tools/attn_vit_big_probe.py > $O/attn_probe.txt 2>&1; echo "attn probe rc=$?"; grep -v amdgpu $O/attn_probe.txt | tail -6

@@ -6,7 +6,7 @@ mkdir -p $O
 for rep in 1 2; do
  for v in 128 256 192; do
   steps=3; [ $v -ge 192 ] && steps=2
-  timeout 1200 python bench.py --videos-per-step $v --steps $steps --warmup 1 --no-cpu-baseline > $O/bench_v${v}_$rep.json 2> $O/bench_v${v}_$rep.err; echo "v=$v rep=$rep rc=$?"
+  timeout 1200 python bench.py --videos-per-step $v --steps $steps --warmup 1 --no-cpu-baseline --full > $O/bench_v${v}_$rep.json 2> $O/bench_v${v}_$rep.err; echo "v=$v rep=$rep rc=$?"
  done
 done
 python - <<'P'
