@@ -142,6 +142,23 @@ int trace_decode_read(trace_ctx* ctx, int32_t* out_ids, int32_t* out_len, int32_
 int trace_decode_host_mode(trace_ctx* ctx, int on);
 int trace_decode_feed(trace_ctx* ctx, const int32_t* tokens, int B, void* stream);
 
+/* Sampling (generate(do_sample=True): HF TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> multinomial, transformers 4.40.1),
+ * on the device.  Set before trace_decode_begin; it holds for every later batch until changed.  temperature <= 0 = greedy (the arg-max path,
+ * unchanged).  Otherwise every token is drawn from the masked fp32 logits of the row's active head [lo, hi) (the text head includes <sync>):
+ *   1. x = logit / temperature (fp32 division);
+ *   2. top_k in [1, 1024]: keep x >= the k-th largest x (ties at the threshold kept; k >= the head's width keeps all).  top_k = 0 = off;
+ *   3. top_p in (0, 1]: order the kept tokens by (x desc, id asc) and keep a token iff the probability mass ranked strictly above it is < top_p
+ *      (the top token always stays);
+ *   4. draw u in [0, 1) and walk the kept tokens in that order (top_k = 0: the whole head in id order) accumulating exp(x - max): the first token
+ *      whose running sum exceeds u * total (the last kept token if rounding leaves none).
+ * RNG contract: u = (x >> 8) * 2^-24 with x = word 0 of Philox4x32-10 under key = seed (64 bits), counter = (step, 0, b, 0), where step is the
+ * device step counter (0 = the token of trace_decode_begin) and b the row within the decode batch — the first rocrand() after
+ * rocrand_init(seed, b, 4 * step) of rocrand_philox4x32_10.h.  Identical inputs and seed give identical ids, eager or graph-replayed.
+ * Domain: top_k in [1, 1024] with any top_p, or top_k = 0 with top_p = 1; anything else (and a NaN / infinite temperature) -> TRACE_ERR_ARG.
+ * Forced ids, EOS and the head switch behave as in greedy decoding; host-select mode (trace_decode_host_mode) ignores the setting.
+ * The params live in device memory: a captured decode step (use_graph) stays valid when they change between calls. */
+int trace_decode_set_sampling(trace_ctx* ctx, float temperature, int top_k, float top_p, uint64_t seed);
+
 /* Two-stage pipeline support (trace/eval/evaluate.py:298-417 loops over independent videos: while one batch decodes — HBM-bound —
  * the next batch's ViT + prefill — MFMA-bound — can run on another stream into other KV slots; the stages share no buffers).
  * trace_stream_create: a HIP stream confined to cu_count CUs starting at logical CU cu_first (hipExtStreamCreateWithCUMask; mask bit i
@@ -219,6 +236,11 @@ int trace_op_add_rmsnorm(const float* part, int KS, const void* R, void* xout, c
    The kernel fetches whole 32-position blocks: positions pos[b] + 1 .. the next multiple of 32 are READ (their scores are masked
    and their weights are exactly 0, so what they hold never counts) — both caches must hold finite values there (the engine's
    caches are zero-filled at creation and only ever hold finite values). */
+/* The same sampler over loose rows (tests; the host-driven decode loop): logits [B][ld] fp32 device (ld >= V+1+Tv+Sv, masked or not — only the
+ * head's range is read), heads / steps int32 [B] device (active head, Philox step), out_ids int32 [B] device = global vocabulary ids.
+ * T > 0 and the domain above; row b uses counter (steps[b], 0, b, 0). */
+int trace_op_sample(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, float T, int top_k, float top_p,
+                    uint64_t seed, const int32_t* steps, int32_t* out_ids, void* stream);
 int trace_op_attn_decode(const void* q, const void* kcache, const void* vtcache, const int32_t* pos, void* O, float* ws,
                          int B, int nq, int nkv, int max_ctx, int nsplit, float scale, void* stream);
 

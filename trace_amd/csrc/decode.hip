@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "sample.h"
 
 namespace {
 
@@ -929,11 +930,16 @@ __global__ __launch_bounds__(512) void head_logits_kernel(const bf16_t* __restri
 
 // one workgroup per sequence.  `step` is shared: every workgroup reads it first, then checks in; the last one to
 // check in advances it (so no workgroup can observe the next step's value).
+// SAMPLE = false: the arg-max over head_logits_kernel's tile partials (greedy).  SAMPLE = true: the token is drawn by sample_row (sample.h)
+// from the masked logits head_logits_kernel wrote to `logits` [B, V+1+Tv+Sv] under the device-resident params *sp, with the step counter and
+// the row index as the Philox counter.  Forced ids, EOS, record_feed and the head switch are the same code in both.
+template <bool SAMPLE>
 __global__ __launch_bounds__(256) void select_next_kernel(const float* __restrict__ part_val, const int32_t* __restrict__ part_idx,
                                                           StepState st, const bf16_t* __restrict__ embed,
                                                           const bf16_t* __restrict__ time_tab, const bf16_t* __restrict__ score_tab,
                                                           const bf16_t* __restrict__ sync_row, bf16_t* __restrict__ xnext, int ldx,
-                                                          int B, int H, int V, int Tv, int Sv, int ntiles, int advance) {
+                                                          int B, int H, int V, int Tv, int Sv, int ntiles, int advance,
+                                                          const float* __restrict__ logits, const SampleParams* __restrict__ sp) {
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ int s_feed;
@@ -951,6 +957,12 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
     }
     float v = -INFINITY;
     int idx = 0x7fffffff;
+    if constexpr (SAMPLE) {
+        __shared__ SampleLds L;
+        int lo, hi;
+        head_bounds(st.heads[b], V, Tv, Sv, lo, hi);
+        idx = lo + sample_row(logits + (size_t)b * (V + 1 + Tv + Sv) + lo, hi - lo, *sp, (uint32_t)step, (uint32_t)b, L);
+    } else {
     for (int t = tid; t < ntiles; t += 256) {
         const float ov = part_val[(size_t)b * ntiles + t];
         const int oi = part_idx[(size_t)b * ntiles + t];
@@ -964,7 +976,9 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
     }
     if (lane == 0) { sv[wid] = v; si[wid] = idx; }
     __syncthreads();
+    }
     if (tid == 0) {
+        if constexpr (!SAMPLE)
         for (int w = 1; w < 4; ++w)
             if (sv[w] > v || (sv[w] == v && si[w] < idx)) { v = sv[w]; idx = si[w]; }
         int tok = idx;
@@ -1241,10 +1255,15 @@ int launch_head_logits(const bf16_t* X, int ldx, const bf16_t* Wh, int H, const 
 
 int launch_select_next(const float* part_val, const int32_t* part_idx, const StepState& st, const bf16_t* embed,
                        const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B,
-                       int H, int V, int Tv, int Sv, int advance, hipStream_t s) {
+                       int H, int V, int Tv, int Sv, int advance, hipStream_t s, const float* logits, const SampleParams* sp) {
     if (B < 1 || B > SK_ROWS || H % 8) return TRACE_ERR_ARG;
+    if ((logits == nullptr) != (sp == nullptr)) return TRACE_ERR_ARG;
     const int ntiles = (V + 1 + Tv + Sv + 15) / 16;
-    hipLaunchKernelGGL(select_next_kernel, dim3(B), dim3(256), 0, s, part_val, part_idx, st, embed, time_tab, score_tab,
-                       sync_row, xnext, ldx, B, H, V, Tv, Sv, ntiles, advance);
+    if (sp)
+        hipLaunchKernelGGL(select_next_kernel<true>, dim3(B), dim3(256), 0, s, part_val, part_idx, st, embed, time_tab, score_tab,
+                           sync_row, xnext, ldx, B, H, V, Tv, Sv, ntiles, advance, logits, sp);
+    else
+        hipLaunchKernelGGL(select_next_kernel<false>, dim3(B), dim3(256), 0, s, part_val, part_idx, st, embed, time_tab, score_tab,
+                           sync_row, xnext, ldx, B, H, V, Tv, Sv, ntiles, advance, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

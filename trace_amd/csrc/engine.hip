@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -16,6 +17,7 @@
 #include "../../include/trace_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "sample.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& m) { g_err = m; return code; }
@@ -109,6 +111,13 @@ struct trace_ctx {
     int host_mode = 0, fed = 0;        // host-driven token selection (sampling): head logits only, ids fed back by the host
     int steps_done = 0;                // decode steps taken since trace_decode_begin (bounded by max_new - 1: the KV slot and the RoPE tables end at max_ctx)
     hipGraphExec_t graphs[SK_ROWS + 1] = {nullptr};   // one captured decode step per batch size
+    hipGraphExec_t graphs_sample[SK_ROWS + 1] = {nullptr};   // the same with the sampling form of the token selection
+    // sampling (trace_decode_set_sampling): host copy of the params, armed at trace_decode_begin; the device copy d_sparams is what the
+    // selection kernel reads (a captured graph stays valid across calls), d_slog the [SK_ROWS][NV] masked logits it samples from
+    SampleParams samp{};
+    int samp_set = 0, samp_on = 0;
+    SampleParams* d_sparams = nullptr;
+    float* d_slog = nullptr;
     hipStream_t cap_stream = nullptr;
     std::vector<hipStream_t> streams;   // trace_stream_create
     // profiling
@@ -296,7 +305,7 @@ extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ct
     // trace_llm_head_logits: its own arg-max partials and three constant head-id rows (all 0 / all 1 / all 2), so that it shares nothing with a
     // decode batch in flight on another stream and needs no host copy or synchronisation per call
     A(c->hl_val, (size_t)SK_ROWS * c->ntiles); A(c->hl_idx, (size_t)SK_ROWS * c->ntiles);
-    A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4);
+    A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4); A(c->d_sparams, 1);
     A(c->d_out_ids, (size_t)SK_ROWS * cfg->max_new_tokens); A(c->d_forced, (size_t)SK_ROWS * cfg->max_new_tokens);
 #undef A
     if (rc == TRACE_OK && hipHostMalloc((void**)&c->h_ring, Lm * 8 * trace_ctx::NSTAGE_H) != hipSuccess) rc = fail(TRACE_ERR_HIP, "hipHostMalloc");
@@ -322,6 +331,7 @@ extern "C" int trace_ctx_destroy(trace_ctx* c) {
     hipDeviceSynchronize();
     for (auto& st : c->streams) { gemm_pers_forget(st); hipStreamDestroy(st); }
     for (auto& g : c->graphs) if (g) hipGraphExecDestroy(g);
+    for (auto& g : c->graphs_sample) if (g) hipGraphExecDestroy(g);
     for (auto& e : c->kev) if (e) hipEventDestroy(e);
     for (auto& e : c->vev) if (e) hipEventDestroy(e);
     if (c->mev0) hipEventDestroy(c->mev0);
@@ -1067,15 +1077,17 @@ static int head_only(trace_ctx* c, const bf16_t* xn, float* logits_out, hipStrea
                             c->B, s));
     return TRACE_OK;
 }
-static int select_only(trace_ctx* c, int advance, hipStream_t s) {
+static int select_only(trace_ctx* c, int advance, hipStream_t s, const float* sample_logits = nullptr) {
     LCHK(launch_select_next(c->part_val, c->part_idx, step_state(c), c->embed, c->time_tab, c->score_tab, c->sync_row, c->dX,
-                            c->H, c->B, c->H, c->V, c->Tv, c->Sv, advance, s));
+                            c->H, c->B, c->H, c->V, c->Tv, c->Sv, advance, s, sample_logits, sample_logits ? c->d_sparams : nullptr));
     return TRACE_OK;
 }
 static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* logits_out, hipStream_t s) {
-    TRY(head_only(c, xn, logits_out, s));
+    // sampling: the selection draws from the masked logits rows the head kernel writes (the caller's logits_out, else d_slog)
+    float* lg = c->samp_on && !c->host_mode && !logits_out ? c->d_slog : logits_out;
+    TRY(head_only(c, xn, lg, s));
     if (c->host_mode) return TRACE_OK;      // the host picks the token and calls trace_decode_feed
-    return select_only(c, advance, s);
+    return select_only(c, advance, s, c->samp_on ? lg : nullptr);
 }
 
 // decode attention context split: ~256-320 workgroups (8 kv heads x B x nsplit) fill the CUs; more splits only add
@@ -1295,6 +1307,8 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     HIPCHK(hipMemsetAsync(c->d_out_ids, 0, (size_t)B * max_new * 4, s));
     const int32_t prm[3] = {max_new, eos, c->host_mode};
     HIPCHK(hipMemcpyAsync(c->d_params, prm, 12, hipMemcpyHostToDevice, s));
+    c->samp_on = c->samp_set && !c->host_mode;     // host-select mode: the host picks (trace_op_sample), the device only feeds
+    if (c->samp_on) HIPCHK(hipMemcpyAsync(c->d_sparams, &c->samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     c->fed = 0; c->steps_done = 0;
     if (forced) HIPCHK(hipMemcpyAsync(c->d_forced, forced, (size_t)B * max_new * 4, hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemsetAsync(c->d_forced, 0xff, (size_t)B * max_new * 4, s));      // -1 = not forced
@@ -1322,7 +1336,7 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
         for (int i = 0; i < n; ++i) { c->step_in_call = steps_before + i; TRY(decode_step(c, logits_out, s)); }
     } else {
         const int key = c->B;
-        hipGraphExec_t* slot_g = &c->graphs[key];
+        hipGraphExec_t* slot_g = c->samp_on ? &c->graphs_sample[key] : &c->graphs[key];
         if (!*slot_g) {
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamSynchronize(s));
@@ -1371,6 +1385,40 @@ extern "C" int trace_decode_read(trace_ctx* c, int32_t* out_ids, int32_t* out_le
     if (out_len) HIPCHK(hipMemcpyAsync(out_len, c->d_out_len, c->B * 4, hipMemcpyDeviceToHost, s));
     if (heads) HIPCHK(hipMemcpyAsync(heads, c->d_heads, c->B * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return TRACE_OK;
+}
+
+// the device sampler's domain (sample.h): T > 0 finite, 0 < p <= 1, k in [1, 1024], or k = 0 with p = 1
+static const char* sampling_bad(float T, int k, float p) {
+    if (!(T > 0.f) || !std::isfinite(T)) return "temperature must be a finite number > 0";
+    if (!(p > 0.f && p <= 1.f)) return "top_p must lie in (0, 1]";
+    if (k < 0 || k > SAMPLE_MAX_K) return "top_k must lie in [0, 1024] on the device";
+    if (k == 0 && p < 1.f) return "top_k = 0 (off) with top_p < 1 is outside the device sampler (sort of the whole head)";
+    return nullptr;
+}
+static SampleParams make_sampling(float T, int k, float p, uint64_t seed) {
+    SampleParams sp{};
+    sp.temperature = T; sp.top_k = k; sp.top_p = p; sp.seed_lo = (uint32_t)seed; sp.seed_hi = (uint32_t)(seed >> 32);
+    return sp;
+}
+
+extern "C" int trace_decode_set_sampling(trace_ctx* c, float temperature, int top_k, float top_p, uint64_t seed) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (std::isnan(temperature)) return fail(TRACE_ERR_ARG, "temperature is NaN");
+    if (temperature <= 0.f) { c->samp_set = 0; return TRACE_OK; }          // greedy
+    if (const char* m = sampling_bad(temperature, top_k, top_p)) return fail(TRACE_ERR_ARG, m);
+    if (!c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
+    c->samp = make_sampling(temperature, top_k, top_p, seed);
+    c->samp_set = 1;
+    return TRACE_OK;
+}
+
+extern "C" int trace_op_sample(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, float T, int top_k, float top_p,
+                               uint64_t seed, const int32_t* steps, int32_t* out_ids, void* stream) {
+    if (!logits || !heads || !steps || !out_ids) return fail(TRACE_ERR_ARG, "null pointer");
+    if (const char* m = sampling_bad(T, top_k, top_p)) return fail(TRACE_ERR_ARG, m);
+    const int rc = launch_sample_rows(logits, ld, B, heads, V, Tv, Sv, make_sampling(T, top_k, top_p, seed), steps, out_ids, (hipStream_t)stream);
+    if (rc != TRACE_OK) return fail(rc, "sample launch failed (B, ld or head widths out of range)");
     return TRACE_OK;
 }
 

@@ -182,6 +182,7 @@ int launch_attn_decode(const bf16_t* qkv, int ldq, bf16_t* kcache, bf16_t* vtcac
 int launch_head_logits(const bf16_t* X, int ldx, const bf16_t* Wh, int H, const int32_t* heads, int V, int Tv, int Sv,
                        float* part_val, int32_t* part_idx, float* logits_out, int B, hipStream_t s);
 // argmax over partials + state machine + next-token embedding
+struct SampleParams;   // sample.h
 struct StepState {
     int32_t* heads;       // [B] in/out
     int32_t* pos;         // [B] in/out (position of the NEXT token to be written)
@@ -194,7 +195,12 @@ struct StepState {
 };
 int launch_select_next(const float* part_val, const int32_t* part_idx, const StepState& st, const bf16_t* embed,
                        const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx,
-                       int B, int H, int V, int Tv, int Sv, int advance, hipStream_t s);
+                       int B, int H, int V, int Tv, int Sv, int advance, hipStream_t s, const float* logits = nullptr,
+                       const SampleParams* sp = nullptr);
+// the sampling form above (logits + sp given) = sample.h's sampler; the same device code for loose rows (trace_op_sample): logits [B][ld] fp32,
+// heads / steps int32 [B] (device) -> out_ids [B] global ids
+int launch_sample_rows(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const SampleParams& sp, const int32_t* steps,
+                       int32_t* out_ids, hipStream_t s);
 
 // ---- fp8 (e4m3) weight path of the decoder (fp8.hip; the fp8 GEMM is launch_gemm_bf16 with GemmArgs::fp8 set) ----
 // X bf16 [rows][K] -> X8 e4m3 [rows][K] + sx[row] = amax/448 (per-row dynamic scale).  Also used row-wise on weight matrices at load.

@@ -10,6 +10,9 @@ import torch
 from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
+from .sampling import SamplingParams, sample_rows_host
+
+__all__ = ["TraceEngine", "SamplingParams", "ops"]
 
 EPI_NONE, EPI_RESIDUAL, EPI_QUICKGELU, EPI_SWIGLU, EPI_PARTIAL = 0, 1, 2, 3, 4
 
@@ -356,6 +359,24 @@ class TraceEngine:
     def feed(self, tokens: Sequence[int]):
         _lib.check(self.lib.trace_decode_feed(self.h, _i32(tokens), len(tokens), _stream()))
 
+    def set_sampling(self, sampling: Optional[SamplingParams]):
+        """Device sampling for the decode batches begun from now on (trace_decode_set_sampling); None or temperature <= 0 = greedy.
+        Only parameters inside the device sampler's domain (SamplingParams.on_device) are accepted here; decode() routes the others."""
+        if sampling is None or sampling.greedy:
+            _lib.check(self.lib.trace_decode_set_sampling(self.h, 0.0, 0, 1.0, 0))
+        else:
+            _lib.check(self.lib.trace_decode_set_sampling(self.h, float(sampling.temperature), int(sampling.top_k), float(sampling.top_p),
+                                                          int(sampling.seed)))
+
+    def sample(self, logits: torch.Tensor, heads: Sequence[int], sampling: SamplingParams, steps: Sequence[int]) -> List[int]:
+        """One id per row of masked logits [B, NV] fp32 (device), drawn as a decode step draws them (row b: Philox step steps[b], row index b):
+        the device sampler (trace_op_sample) inside its domain, the host statement of the same rules outside it."""
+        cfg = self.cfg
+        if not sampling.on_device:
+            return sample_rows_host(logits, heads, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size, sampling, steps)
+        out = ops.sample(logits, heads, sampling, steps, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size, element=_lib.element_of(self.dtype))
+        return out.tolist()
+
     def set_profile(self, mode: int):
         """0 off; 1 time decode_steps calls; 2 also bracket one gate|up GEMV launch per decode step with HIP events."""
         _lib.check(self.lib.trace_set_profile(self.h, int(mode)))
@@ -457,8 +478,40 @@ class TraceEngine:
         flush()
 
     def decode(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
-               forced: Optional[Sequence[Sequence[int]]] = None):
-        """Stage 2 of generate(): the greedy loop over prefilled KV slots, on the current stream -> (ids per sequence, final heads)."""
+               forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None):
+        """Stage 2 of generate(): the decode loop over prefilled KV slots, on the current stream -> (ids per sequence, final heads).
+        sampling: None / temperature <= 0 = greedy; otherwise every id is drawn on the device (trace_decode_set_sampling: same graphs, same
+        stepping), or — parameters outside the device sampler's domain — one eager step at a time with the host statement of the same rules."""
+        if sampling is not None and not sampling.greedy:
+            if not sampling.on_device:
+                return self._decode_host_sampled(slots, heads, max_new_tokens, eos, forced, sampling)
+            self.set_sampling(sampling)
+            try:
+                return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced)
+            finally:
+                self.set_sampling(None)
+        return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced)
+
+    def _decode_host_sampled(self, slots, heads, max_new_tokens, eos, forced, sampling: SamplingParams):
+        B = len(slots)
+        self.host_mode(True)
+        try:
+            lg = self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, want_logits=True)
+            cur = list(heads)
+            for step in range(max_new_tokens):
+                tok = self.sample(lg, cur, sampling, [step] * B)
+                if forced is not None:
+                    tok = [f[step] if step < len(f) and f[step] >= 0 else t for t, f in zip(tok, forced)]
+                self.feed(tok)
+                ids, cur = self.decode_read()
+                if step == max_new_tokens - 1 or (eos >= 0 and all(len(x) and x[-1] == eos for x in ids)):
+                    break
+                lg = self.decode_steps(1, use_graph=False, want_logits=True)
+            return self.decode_read()
+        finally:
+            self.host_mode(False)
+
+    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced):
         self.decode_begin(list(slots), heads, max_new_tokens, eos, forced)
         if max_new_tokens > 1:
             if eos < 0:
@@ -476,12 +529,12 @@ class TraceEngine:
 
     def generate(self, videos: Sequence[torch.Tensor], timestamps: Sequence, input_ids: Sequence[Sequence[int]],
                  heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
-                 forced: Optional[Sequence[Sequence[int]]] = None):
+                 forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None):
         B = len(videos)
         if B > self.decode_batch_max:
             raise ValueError(f"batch {B} exceeds the engine's decode batch {self.decode_batch_max}")
         self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
-        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced)
+        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling)
 
     # ---- two-stage pipeline over a stream of batches ---------------------------------------------------
     def make_streams(self, decode_cus: int = 0):
@@ -501,11 +554,12 @@ class TraceEngine:
         dec, enc = masked(0, decode_cus), masked(decode_cus, ncu - decode_cus)      # (trace_stream_create caps each stream's persistent GEMMs at its CU count)
         return enc, dec
 
-    def generate_stream(self, batches: Iterable, max_new_tokens: int, eos: int = -1, use_graph: bool = True, streams=None):
+    def generate_stream(self, batches: Iterable, max_new_tokens: int, eos: int = -1, use_graph: bool = True, streams=None,
+                        sampling: Optional[SamplingParams] = None):
         """generate() over a stream of batches as a two-stage pipeline: while batch k decodes (HBM-bound) on one stream, batch k+1
         runs its ViT + slot pool + prefill (MFMA-bound) on another, into the other half of the KV slots.  `batches` yields
         (videos, timestamps, input_ids, heads, forced-or-None); yields generate()'s result per batch, in order.  Every batch holds at
-        most max_batch // 2 videos.  Results are identical to generate() batch by batch: the stages share no buffers (KV banks,
+        most max_batch // 2 videos.  sampling: as decode(), the same params (and seed) for every batch.  Results are identical to generate() batch by batch: the stages share no buffers (KV banks,
         prefill / ViT scratch vs decode scratch) and every kernel's reductions have a fixed order.
 
         The decode stage is issued from a worker thread: one decode batch is ~75 k kernel dispatches, far more than a HIP stream's
@@ -523,7 +577,7 @@ class TraceEngine:
             torch.cuda.set_device(self.device)
             with torch.cuda.stream(dec_s):
                 dec_s.wait_event(ready)
-                return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced)
+                return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced, sampling)
 
         pending = None                                  # (bank, heads, forced, B, ready event): prefilled, waiting for its decode
         bank = 0
@@ -573,6 +627,21 @@ class ops:
     @staticmethod
     def dtype() -> torch.dtype:
         return torch.float16 if ops.element == "f16" else torch.bfloat16
+
+    @staticmethod
+    def sample(logits, heads, sampling: SamplingParams, steps, V: int, Tv: int, Sv: int, element=None):
+        """trace_op_sample: logits [B, ld >= V+1+Tv+Sv] fp32 (device) -> int32 ids [B] (device), row b drawn from head heads[b] with Philox step
+        steps[b] and row index b.  heads / steps: sequences of ints or int32 device tensors."""
+        lib = _lib.load(element or ops.element)
+        lg = logits.contiguous()
+        B, ld = lg.shape
+        dev = lg.device
+        hd = heads if isinstance(heads, torch.Tensor) else torch.tensor([int(h) for h in heads], dtype=torch.int32, device=dev)
+        st = steps if isinstance(steps, torch.Tensor) else torch.tensor([int(x) for x in steps], dtype=torch.int32, device=dev)
+        out = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(lib.trace_op_sample(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, float(sampling.temperature), int(sampling.top_k),
+                                       float(sampling.top_p), int(sampling.seed), _ptr(st), _ptr(out), _stream()))
+        return out
 
     @staticmethod
     def set_gemm_variant(v: int):

@@ -92,10 +92,11 @@ def parse_output_ids(ids: Sequence[int], tokenizer, model, stop_str: Optional[st
 @torch.no_grad()
 def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: str, *, num_frames: Optional[int] = None,
                     max_new_tokens: int = 512, batch_size: Optional[int] = None, conv_mode: str = "llama_2",
-                    device_preprocess: bool = True, pipeline: bool = True) -> List[dict]:
+                    device_preprocess: bool = True, pipeline: bool = True, sampling=None) -> List[dict]:
     """items: dicts with "video" (decoded frames array / list / a reader with get_batch), optional "fps", "id", "query"
     (formatted into `prompt` as the tvg / vhd tasks do, evaluate.py:303-306).  Returns one result dict per item, in order, on
-    every rank: {"video", "id", "timestamps", "scores", "captions", "output_ids"}."""
+    every rank: {"video", "id", "timestamps", "scores", "captions", "output_ids"}.  sampling: a trace_amd.engine.SamplingParams (None = greedy),
+    the same params and seed for every chunk."""
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
     world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
     eng = model.engine
@@ -124,11 +125,11 @@ def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: 
             yield vids, tss, idl, [1] * len(chunk), None
 
     if pipelined and len(mine) > bs:
-        for out, _ in eng.generate_stream(chunks(), max_new_tokens, eos=eos):
+        for out, _ in eng.generate_stream(chunks(), max_new_tokens, eos=eos, sampling=sampling):
             local.extend(out)
     else:
         for vids, tss, idl, heads, _ in chunks():
-            out, _ = eng.generate(vids, tss, idl, heads, max_new_tokens, eos=eos)
+            out, _ = eng.generate(vids, tss, idl, heads, max_new_tokens, eos=eos, sampling=sampling)
             local.extend(out)
     per_rank = (len(items) + world - 1) // world
     if torch.distributed.is_initialized():

@@ -134,6 +134,19 @@ def load_tokenizer(model_path: str, cfg: TraceConfig, **kwargs):
     return ByteTokenizer(cfg.vocab_size)
 
 
+def apply_generation_config(model, model_path: str) -> None:
+    """from_pretrained reads the checkpoint's generation_config.json (when present) into the model's generate() defaults; the sampling keys
+    this build acts on are do_sample / temperature / top_k / top_p."""
+    fn = os.path.join(model_path, "generation_config.json")
+    if not os.path.exists(fn):
+        return
+    with open(fn) as f:
+        gc = json.load(f)
+    for k in ("do_sample", "temperature", "top_k", "top_p"):
+        if gc.get(k) is not None:
+            setattr(model.generation_config, k, gc[k])
+
+
 def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", use_flash_attn=False, max_batch: int = 1, max_new_tokens: int = 1024, **kwargs):
     if load_8bit or load_4bit:
@@ -170,6 +183,7 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
         tokenizer = load_tokenizer(model_path, cfg, **kwargs)
     processor = _image_processor(cfg, model_path)
     model = TraceMistralForCausalLM(cfg, eng, processor)
+    apply_generation_config(model, model_path)
     # builder.py:135-149: optional extra tokens must not change the embedding table the engine already holds
     if getattr(cfg, "mm_use_im_patch_token", False):
         tokenizer.add_tokens([DEFAULT_IMAGE_PATCH_TOKEN], special_tokens=True)

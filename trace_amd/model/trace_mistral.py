@@ -12,6 +12,7 @@ import torch
 
 from ..config import TraceConfig
 from ..constants import MMODAL_TOKEN_INDEX, NUM_FRAMES
+from ..sampling import SamplingParams, check_sampling
 from .encoders import NumberTokenizer, ScoreTower, TimeTower
 
 
@@ -66,6 +67,8 @@ class TraceMistralForCausalLM:
         self.model = _MetaModel(config, _VisionTower(config, image_processor))
         self.device = engine.device
         self.dtype = engine.dtype
+        # HF GenerationConfig defaults; builder.load_pretrained_model overrides them from the checkpoint's generation_config.json
+        self.generation_config = SimpleNamespace(do_sample=False, temperature=1.0, top_k=50, top_p=1.0)
 
     # ---- nn.Module-like conveniences the drivers call ----
     def get_model(self):
@@ -93,11 +96,17 @@ class TraceMistralForCausalLM:
     # ---- generate (trace_mistral.py:268-314) ----
     @torch.no_grad()
     def generate(self, inputs=None, images_or_videos=None, times=None, scores=None, video_timestamps=None,
-                 modal_list=None, heads=None, max_new_tokens: int = 128, do_sample: bool = False, temperature: float = 1.0,
+                 modal_list=None, heads=None, max_new_tokens: int = 128, do_sample: Optional[bool] = None,
+                 temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None, generation_config=None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, stopping_criteria=None,
                  use_cache: bool = True, attention_mask=None, position_ids=None, **kwargs):
+        """do_sample / temperature / top_k / top_p: explicit values, else `generation_config`'s, else this model's defaults (HF's: greedy,
+        1.0, 50, 1.0, or the checkpoint's generation_config.json).  Sampling follows HF's warpers (temperature -> top_k -> top_p ->
+        multinomial) on the device (trace_amd/csrc/sample.h); the 64-bit seed is drawn from torch's default generator, so torch.manual_seed
+        makes a call reproducible.  temperature == 0 or do_sample=False: greedy."""
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")          # trace_mistral.py:282-283
+        sampling = self._sampling_params(do_sample, temperature, top_k, top_p, generation_config, kwargs)
         if images_or_videos is None:
             raise NotImplementedError("text-only generation is outside the accelerated path")
         cfg, eng = self.config, self.engine
@@ -133,15 +142,18 @@ class TraceMistralForCausalLM:
                 eng.vit_forward(vids[b])
                 eng.stc_connector(None, vids[b].shape[0])
                 eng.prefill(b, eng.splice(id_lists[b]))
-            eng.decode_begin(list(range(B)), [0] * B, max_new_tokens, eos)
-            if max_new_tokens > 1:
-                eng.decode_steps(max_new_tokens - 1)
-            out, new_heads = eng.decode_read()
-        elif not do_sample and not stopping_criteria:
-            out, new_heads = eng.generate(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos=eos)
+            if sampling is not None:
+                out, new_heads = eng.decode(list(range(B)), [0] * B, max_new_tokens, eos, sampling=sampling)
+            else:
+                eng.decode_begin(list(range(B)), [0] * B, max_new_tokens, eos)
+                if max_new_tokens > 1:
+                    eng.decode_steps(max_new_tokens - 1)
+                out, new_heads = eng.decode_read()
+        elif not stopping_criteria:
+            out, new_heads = eng.generate(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos=eos, sampling=sampling)
         else:
             out, new_heads = self._generate_stepwise(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos,
-                                                     do_sample, temperature, stopping_criteria, ids)
+                                                     sampling, stopping_criteria, ids)
         for b in range(B):                       # the reference mutates `heads` in place (trace_mistral.py:342)
             heads[b] = int(new_heads[b])
         pad = eos if pad_token_id is None else pad_token_id
@@ -151,25 +163,55 @@ class TraceMistralForCausalLM:
             res[b, : len(row)] = torch.tensor(row, dtype=torch.long)
         return res.to(self.device)
 
-    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, do_sample, temperature, stopping, prompt_ids):
-        """Sampling / stopping-criteria path: one device step at a time with the masked logits brought back
-        (the reference's HF sampling loop does the same round trip every token)."""
+    # arguments of HF's generate() this build does not implement, with the value that means "off"
+    _UNSUPPORTED = {"num_beams": 1, "num_return_sequences": 1, "typical_p": 1.0, "min_p": None, "repetition_penalty": 1.0}
+
+    def _sampling_params(self, do_sample, temperature, top_k, top_p, generation_config, kwargs) -> Optional[SamplingParams]:
+        """HF's precedence: explicit argument > generation_config > the model's defaults.  None = greedy."""
+        srcs = [s for s in (generation_config, self.generation_config) if s is not None]
+
+        def pick(name, val):
+            if val is not None:
+                return val
+            for src in srcs:
+                v = src.get(name) if isinstance(src, dict) else getattr(src, name, None)
+                if v is not None:
+                    return v
+            return None
+        for name, off in self._UNSUPPORTED.items():
+            v = pick(name, kwargs.get(name))
+            if v is not None and v != off:
+                raise NotImplementedError(f"{name}={v!r} is not implemented on the MI355X path (only {name}={off!r})")
+        do_sample, temperature = bool(pick("do_sample", do_sample)), float(pick("temperature", temperature))
+        top_k, top_p = pick("top_k", top_k), float(pick("top_p", top_p))
+        top_k = 0 if top_k is None else top_k
+        check_sampling(temperature, top_k, top_p)
+        if not do_sample or temperature <= 0:
+            return None
+        g = torch.randint(0, 1 << 32, (2,), dtype=torch.int64)        # torch's default generator: torch.manual_seed(s) reproduces a call
+        return SamplingParams(temperature, int(top_k), top_p, (int(g[0]) << 32) | int(g[1]))
+
+    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, prompt_ids):
+        """Stopping-criteria path: one device step at a time with the masked logits brought back; ids from the device sampler
+        (trace_op_sample: the same draw a device decode step makes at that step and row) or the arg-max."""
         eng = self.engine
         B = len(vids)
         for b in range(B):
             eng.encode_video(vids[b], timestamps[b])
             eng.prefill(b, eng.splice(id_lists[b]))
         done = [False] * B
+        cur_heads = list(heads)
         eng.host_mode(True)
         try:
             lg = eng.decode_begin(list(range(B)), heads, max_new, eos=eos, want_logits=True)
             for step in range(max_new):
-                if do_sample and temperature and temperature > 0:
-                    probs = torch.softmax(lg.float() / temperature, dim=-1)
-                    tok = torch.multinomial(probs, 1).view(-1).tolist()
+                if sampling is not None:
+                    tok = eng.sample(lg, cur_heads, sampling, [step] * B)
                 else:
                     tok = torch.argmax(lg, dim=-1).tolist()
                 eng.feed(tok)
+                if sampling is not None:
+                    _, cur_heads = eng.decode_read()
                 for b in range(B):
                     done[b] = done[b] or (eos >= 0 and tok[b] == eos)
                 if all(done) or step == max_new - 1:

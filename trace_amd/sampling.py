@@ -1,0 +1,204 @@
+"""Sampling parameters and the host-side statement of the device sampler (trace_amd/csrc/sample.h).
+
+`SamplingParams` is what Engine.decode / generate / generate_stream and evaluate_videos take.  `sample_row_ref` restates the device
+sampler in float32 numpy, operation by operation (the same exp polynomial, the same run sums and Hillis-Steele scan, the same rank
+arithmetic), so it returns the device's id bit for bit; it also serves as the host path for the parameter combinations the device does not
+take (top_k > 1024, or top_k = 0 with top_p < 1), where it applies the same rules.  `philox_uniform` is the RNG contract in numpy."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+DEVICE_MAX_K = 1024           # sample.h SAMPLE_MAX_K
+_THREADS = 256                # sample.h SAMPLE_THREADS
+_F = np.float32
+
+
+@dataclass(frozen=True)
+class SamplingParams:
+    """HF sampling warpers in HF's order: temperature, top_k (50 = HF's default; 0 = off), top_p (1.0 = off).  seed: 64-bit Philox key;
+    the counter of row b at decode step s is (s, 0, b, 0).  temperature <= 0 means greedy."""
+    temperature: float = 1.0
+    top_k: int = 50
+    top_p: float = 1.0
+    seed: int = 0
+
+    def __post_init__(self):
+        check_sampling(self.temperature, self.top_k, self.top_p)
+        if not 0 <= int(self.seed) < 1 << 64:
+            raise ValueError(f"seed must be a 64-bit unsigned integer, got {self.seed}")
+
+    @property
+    def greedy(self) -> bool:
+        return self.temperature <= 0
+
+    @property
+    def on_device(self) -> bool:
+        """the device sampler's domain: top_k in [1, 1024] with any top_p, or top_k = 0 with top_p = 1"""
+        return 1 <= self.top_k <= DEVICE_MAX_K or (self.top_k == 0 and self.top_p >= 1.0)
+
+
+def check_sampling(temperature, top_k, top_p) -> None:
+    """HF's own argument checks (TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper)"""
+    t = float(temperature)
+    if t != t or t in (float("inf"), float("-inf")):
+        raise ValueError(f"`temperature` has to be a finite float, but is {temperature}")
+    if not isinstance(top_k, (int, np.integer)) or isinstance(top_k, bool) or top_k < 0:
+        raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")
+    p = float(top_p)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
+
+
+# ---- RNG: Philox4x32-10, word 0 of counter (c0, c1, c2, c3) under the 64-bit key (vectorised over numpy arrays) ----
+def philox_x(seed, c0, c1, c2, c3):
+    seed = np.asarray(seed, np.uint64)
+    k0 = (seed & np.uint64(0xFFFFFFFF)).astype(np.uint64)
+    k1 = (seed >> np.uint64(32)).astype(np.uint64)
+    c = [np.asarray(v, np.uint64) & np.uint64(0xFFFFFFFF) for v in (c0, c1, c2, c3)]
+    c0, c1, c2, c3 = np.broadcast_arrays(*c, k0)[:4]
+    k0, k1 = np.broadcast_arrays(k0, k1, c0)[:2]
+    m32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        m0 = np.uint64(0xD2511F53) * c0
+        m1 = np.uint64(0xCD9E8D57) * c2
+        n0 = (m1 >> np.uint64(32)) ^ c1 ^ k0
+        n2 = (m0 >> np.uint64(32)) ^ c3 ^ k1
+        c1, c3, c0, c2 = m1 & m32, m0 & m32, n0, n2
+        k0 = (k0 + np.uint64(0x9E3779B9)) & m32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & m32
+    return c0.astype(np.uint32)
+
+
+def philox_uniform(seed, step, row):
+    """u in [0, 1) of row `row` at decode step `step` (float32)"""
+    x = philox_x(seed, step, 0, row, 0)
+    return ((x >> np.uint32(8)).astype(np.float32) * _F(1.0 / 16777216.0)).astype(np.float32)
+
+
+# ---- the sampler ----
+def _sexp(x):
+    """sample.h sample_exp: exp(x), x <= 0, every operation rounded in float32"""
+    x = np.asarray(x, np.float32)
+    out = np.zeros_like(x)
+    ok = x > _F(-80.0)
+    v = x[ok]
+    n = np.rint(v * _F(float.fromhex("0x1.715476p+0")))
+    r = v - n * _F(float.fromhex("0x1.62e4p-1"))
+    r = r - n * _F(float.fromhex("0x1.7f7d1cp-20"))
+    p = np.full_like(v, _F(float.fromhex("0x1.6c16c2p-10")))
+    for c in ("0x1.111112p-7", "0x1.555556p-5", "0x1.555556p-3"):
+        p = p * r + _F(float.fromhex(c))
+    p = p * r + _F(0.5)
+    p = p * r + _F(1.0)
+    p = p * r + _F(1.0)
+    out[ok] = p * np.ldexp(_F(1.0), n.astype(np.int32)).astype(np.float32)
+    return out
+
+
+def _scan(v):
+    """Hillis-Steele inclusive scan over 256 values (sample.h sample_scan): v[t] = v[t - d] + v[t]"""
+    v = v.copy()
+    d = 1
+    while d < _THREADS:
+        v[d:] = v[:-d] + v[d:]
+        d <<= 1
+    return v
+
+
+def _keys(x):
+    u = x.view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _run_sums(w, per):
+    """running sums of w in sample.h's order: runs of `per` per thread, then the scan over the run totals"""
+    buf = np.zeros(_THREADS * per, np.float32)
+    buf[: len(w)] = w
+    runs = np.cumsum(buf.reshape(_THREADS, per), axis=1, dtype=np.float32)
+    incl = _scan(runs[:, -1].copy())
+    excl = np.concatenate([np.zeros(1, np.float32), incl[:-1]])
+    return (excl[:, None] + runs).reshape(-1), incl[-1]
+
+
+def sample_row_ref(row, temperature, top_k, top_p, u, info=None):
+    """The device sampler on one head row (float32 [n]): the chosen offset in [0, n).  `info` (a dict, optional) receives the kept
+    offsets in walk order ('kept'), the running sums ('cum'), and the target ('target') — for tests."""
+    x = np.asarray(row, np.float32) / _F(temperature)
+    n = len(x)
+    u = _F(u)
+    p = _F(top_p)
+    if top_k <= 0 and p >= _F(1.0):
+        M = x.max()
+        w = _sexp(x - M)
+        C = (n + _THREADS - 1) // _THREADS
+        buf = np.zeros(_THREADS * C, np.float32)
+        buf[:n] = w
+        runs = np.cumsum(buf.reshape(_THREADS, C), axis=1, dtype=np.float32)
+        incl = _scan(runs[:, -1].copy())
+        excl = np.concatenate([np.zeros(1, np.float32), incl[:-1]])
+        run = (excl[:, None] + runs).reshape(-1)[:n]
+        target = u * incl[-1]
+        hit = np.nonzero(run > target)[0]
+        if info is not None:
+            info.update(kept=np.arange(n), cum=run, target=target, total=incl[-1])
+        return int(hit[0]) if len(hit) else n - 1
+    k = n if top_k <= 0 else min(int(top_k), n)
+    keys = _keys(x)
+    theta = np.sort(keys)[::-1][k - 1]
+    above = np.nonzero(keys > theta)[0]
+    ties = np.nonzero(keys == theta)[0]
+    order = above[np.lexsort((above, ~keys[above]))]          # (value desc, id asc)
+    na, m = len(order), len(ties)
+    tv = x[ties[0]]
+    M = x[order[0]] if na else tv
+    per = max(4, -(-na // _THREADS))
+    cw, _ = _run_sums(_sexp(x[order] - M), per)
+    cw = cw[:na]
+    A = cw[na - 1] if na else _F(0.0)
+    wt = _sexp(np.array([tv - M], np.float32))[0]
+    Z = A + _F(m) * wt
+    na_keep, mk = na, m
+    if p < _F(1.0):
+        pZ = p * Z
+        above_mass = np.concatenate([np.zeros(1, np.float32), cw[:-1]]) if na else cw
+        bad = np.nonzero(above_mass >= pZ)[0]
+        na_keep = int(bad[0]) if len(bad) else na
+        if na_keep < na:
+            mk = 0
+        else:
+            q = (pZ - A) / wt
+            mk = 0 if q <= 0 else (m if q >= _F(m) else min(m, int(np.ceil(q))))
+            if na == 0 and mk < 1:
+                mk = 1
+    Ak = cw[na_keep - 1] if na_keep else _F(0.0)
+    target = u * (Ak + _F(mk) * wt)
+    if info is not None:
+        tcum = Ak + (np.arange(1, mk + 1, dtype=np.float32) * wt).astype(np.float32)
+        info.update(kept=np.concatenate([order[:na_keep], ties[:mk]]), cum=np.concatenate([cw[:na_keep], tcum]).astype(np.float32),
+                    target=target, total=Ak + _F(mk) * wt)
+    hit = np.nonzero(cw[:na_keep] > target)[0]
+    if len(hit):
+        return int(order[hit[0]])
+    if mk == 0:
+        return int(order[na_keep - 1])
+    r = (target - Ak) / wt
+    jt = 0 if r <= 0 else (mk - 1 if r >= _F(mk - 1) else int(np.floor(r)))
+    return int(ties[jt])
+
+
+def head_bounds(head: int, V: int, Tv: int, Sv: int):
+    return ((0, V + 1), (V + 1, V + 1 + Tv), (V + 1 + Tv, V + 1 + Tv + Sv))[int(head)]
+
+
+def sample_rows_host(logits, heads, V, Tv, Sv, params: SamplingParams, steps):
+    """The host path (parameters outside the device sampler's domain): one id per row of masked logits [B, NV] (numpy or a torch tensor)
+    under the same rules and the same RNG contract as the device."""
+    lg = logits.detach().float().cpu().numpy() if hasattr(logits, "detach") else np.asarray(logits, np.float32)
+    out = []
+    for b in range(lg.shape[0]):
+        lo, hi = head_bounds(heads[b], V, Tv, Sv)
+        u = philox_uniform(params.seed, int(steps[b]), b)
+        out.append(lo + sample_row_ref(lg[b, lo:hi], params.temperature, params.top_k, params.top_p, u))
+    return out
