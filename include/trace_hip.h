@@ -120,6 +120,26 @@ int trace_llm_prefill_pair(trace_ctx* ctx, int slot0, const void* embeds0, const
  * prompts' 17 panels need 2 rounds for 1.06 of work).  Results per prompt do not depend on n. */
 int trace_llm_prefill_multi(trace_ctx* ctx, int slot0, const void* const* embeds, int n, int L, void* stream);
 
+/* One video, several questions (trace/eval/videomme/evaluate.py:349-386 calls model.generate once per entry of qa_list with the same frame tensor, the
+ * same timestamps and a prompt identical up to and including <video>; trace/eval/mvbench and any multi-turn use of one video do the same): the rows
+ * through <video> are prefilled once and kept, each question prefills only the rows after them.
+ * n <= 8 slots slot0 .. slot0+n-1, each holding at least `past` rows: run L new rows per slot at positions past .. past+L-1 attending rows
+ * 0 .. past+L-1; rows >= past that the slot held before are discarded.  embeds: HOST array of n device pointers [L, hidden]; NULL with n == 1 = the
+ * internal embedding buffer (the last trace_embed_rows / trace_splice_embeds).  hidden_out (n == 1 only, may be NULL): [L, hidden] final-norm rows.
+ * past == 0 is trace_llm_prefill_multi.  A row's results are bit-identical to the same row of one trace_llm_prefill over all past + L rows, wherever
+ * the cut is, on the bf16, fp16 and fp8 paths.  TRACE_ERR_STATE: past above the rows a slot holds; TRACE_ERR_ARG: past < 0, past + L > max_ctx, n x L
+ * above the prefill workspace (see trace_llm_prefill_multi), a slot out of range — all before any launch. */
+int trace_llm_prefill_append(trace_ctx* ctx, int slot0, int n, int past, const void* const* embeds, int L, void* hidden_out, void* stream);
+/* rows [0, rows) of every layer's K and V^T from src_slot to n other slots (HOST dst_slots); their length becomes `rows` (the V^T side may copy up to 7
+ * positions more: finite values that a later append overwrites and the attention masks).  rows == the source's length: the copies can be decoded from as
+ * the source can.  TRACE_ERR_STATE: rows above the source's length; TRACE_ERR_ARG: a slot out of range, src_slot among the destinations. */
+int trace_kv_copy(trace_ctx* ctx, int src_slot, const int32_t* dst_slots, int n, int rows, void* stream);
+/* trace_splice_embeds for rows that hold no <video> (the part of a prompt after the placeholder, trace/model/trace_arch.py:410-427 for those rows):
+ * token / <sync> / <time> / <score> ids -> [n_ids, hidden] (internal buffer; embeds_out may be NULL).  A video placeholder among the ids is
+ * TRACE_ERR_ARG; trace_splice_embeds itself keeps its "only have one video" rule. */
+int trace_embed_rows(trace_ctx* ctx, const int32_t* ids, int n_ids, const int32_t* time_rows, int n_time, const int32_t* score_rows, int n_score,
+                     void* embeds_out, void* stream);
+
 /* The head stage of forward() for EVERY position (trace_mistral.py:190-252: lm_head | sync_head | time_head | score_head, fp32,
  * everything outside head `head`'s id range set to -inf): hidden [R, hidden] bf16 device = the hidden_out of trace_llm_prefill ->
  * logits_out [R, V+1+Tv+Sv] fp32 device.  The decode loop needs the last row only and gets it from trace_decode_begin / _steps. */

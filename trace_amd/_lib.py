@@ -49,6 +49,9 @@ SIGNATURES = {
     "trace_llm_prefill": (I, [P, I, P, I, P, P]),
     "trace_llm_prefill_pair": (I, [P, I, P, P, I, P]),
     "trace_llm_prefill_multi": (I, [P, I, C.POINTER(P), I, I, P]),
+    "trace_llm_prefill_append": (I, [P, I, I, I, C.POINTER(P), I, P, P]),
+    "trace_kv_copy": (I, [P, I, P, I, I, P]),
+    "trace_embed_rows": (I, [P, P, I, P, I, P, I, P, P]),
     "trace_llm_head_logits": (I, [P, P, I, I, P, P]),
     "trace_decode_begin": (I, [P, P, I, P, I, I, P, P, P]),
     "trace_decode_steps": (I, [P, I, I, P, P]),

@@ -995,23 +995,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     }
 }
 
-// V [rows, HD] (row stride src_rs) -> V^T [HD, rows_pad] (row stride dst_rs), zero-filled for rows >= n.
-// One block per 64-row tile: 16-byte loads -> LDS -> 16-byte stores along the token axis.
-// perm = 1: within every 16 keys the destination order is [0-3, 8-11, 4-7, 12-15] (attn_vit_dma_kernel's PV operand layout).
+// V [rows, HD] (row stride src_rs) -> V^T [HD, rows_pad] (row stride dst_rs): source row r lands at position p0 + r, positions
+// p0 + n .. the end of that 64-block are zero-filled, positions < p0 (a prefill continuing a slot that holds p0 rows) are left as they are.
+// One block per 64-position tile: 16-byte loads -> LDS -> 16-byte stores along the token axis; only the 8-position chunk that straddles
+// p0 (p0 % 8 != 0) is written element by element.
+// perm = 1: within every 16 keys the destination order is [0-3, 8-11, 4-7, 12-15] (attn_vit_dma_kernel's PV operand layout; p0 = 0 only).
 template <int HD>
 __global__ __launch_bounds__(256) void transpose_v_kernel(const bf16_t* __restrict__ src, long src_bs, long src_hs, int src_rs,
                                                           bf16_t* __restrict__ dst, long dst_bs, long dst_hs, int dst_rs,
-                                                          int n, int perm) {
+                                                          int n, int perm, int p0) {
     constexpr int LROW = HD + 2;   // elements; odd dword stride -> column reads spread over banks
     __shared__ bf16_t tile[64 * LROW];
-    const int t0 = blockIdx.x * 64, hh = blockIdx.y, b = blockIdx.z;
+    const int t0 = (p0 / 64 + blockIdx.x) * 64, hh = blockIdx.y, b = blockIdx.z;
     const bf16_t* s = src + (size_t)b * src_bs + (size_t)hh * src_hs;
     bf16_t* d = dst + (size_t)b * dst_bs + (size_t)hh * dst_hs;
     constexpr int CPR = HD / 8;
     for (int c = threadIdx.x; c < 64 * CPR; c += 256) {
         const int row = c / CPR, kc = c % CPR;
         uint4 v = make_uint4(0, 0, 0, 0);
-        if (t0 + row < n) v = *reinterpret_cast<const uint4*>(s + (size_t)(t0 + row) * src_rs + kc * 8);
+        const int sr = t0 + row - p0;                      // source row of destination position t0 + row
+        if (sr >= 0 && sr < n) v = *reinterpret_cast<const uint4*>(s + (size_t)sr * src_rs + kc * 8);
         uint32_t* tp = reinterpret_cast<uint32_t*>(&tile[row * LROW + kc * 8]);
         tp[0] = v.x; tp[1] = v.y; tp[2] = v.z; tp[3] = v.w;
     }
@@ -1026,7 +1029,17 @@ __global__ __launch_bounds__(256) void transpose_v_kernel(const bf16_t* __restri
             const uint32_t lo = tile[r0 * LROW + dd], hi = tile[(r0 + 1) * LROW + dd];
             o[e] = lo | (hi << 16);
         }
-        *reinterpret_cast<uint4*>(d + (size_t)dd * dst_rs + t0 + tc * 8) = make_uint4(o[0], o[1], o[2], o[3]);
+        const int cp = t0 + tc * 8;                         // first position of this 8-position chunk
+        bf16_t* dp = d + (size_t)dd * dst_rs + cp;
+        if (cp >= p0) {
+            *reinterpret_cast<uint4*>(dp) = make_uint4(o[0], o[1], o[2], o[3]);
+        } else if (cp + 8 > p0) {                           // the chunk p0 falls into: positions < p0 belong to the rows already cached
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (cp + 2 * e >= p0) dp[2 * e] = (bf16_t)(o[e] & 0xffffu);
+                if (cp + 2 * e + 1 >= p0) dp[2 * e + 1] = (bf16_t)(o[e] >> 16);
+            }
+        }
     }
 }
 
@@ -1109,10 +1122,10 @@ int launch_attn_prefill(const AttnArgs& a, hipStream_t s) {
 }
 
 int launch_transpose_v(const bf16_t* src, long src_bs, long src_hs, int src_rs, bf16_t* dst, long dst_bs, long dst_hs,
-                       int dst_rs, int n, int hd, int heads, int batch, hipStream_t s, int perm) {
-    if (dst_rs % 64 || dst_rs < n || (hd != 64 && hd != 128)) return TRACE_ERR_ARG;
-    dim3 grid((n + 63) / 64, heads, batch);
-    if (hd == 64) hipLaunchKernelGGL(transpose_v_kernel<64>, grid, dim3(256), 0, s, src, src_bs, src_hs, src_rs, dst, dst_bs, dst_hs, dst_rs, n, perm);
-    else hipLaunchKernelGGL(transpose_v_kernel<128>, grid, dim3(256), 0, s, src, src_bs, src_hs, src_rs, dst, dst_bs, dst_hs, dst_rs, n, perm);
+                       int dst_rs, int n, int hd, int heads, int batch, hipStream_t s, int perm, int p0) {
+    if (dst_rs % 64 || n < 1 || p0 < 0 || dst_rs < p0 + n || (hd != 64 && hd != 128) || (perm && p0)) return TRACE_ERR_ARG;
+    dim3 grid((p0 + n + 63) / 64 - p0 / 64, heads, batch);
+    if (hd == 64) hipLaunchKernelGGL(transpose_v_kernel<64>, grid, dim3(256), 0, s, src, src_bs, src_hs, src_rs, dst, dst_bs, dst_hs, dst_rs, n, perm, p0);
+    else hipLaunchKernelGGL(transpose_v_kernel<128>, grid, dim3(256), 0, s, src, src_bs, src_hs, src_rs, dst, dst_bs, dst_hs, dst_rs, n, perm, p0);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

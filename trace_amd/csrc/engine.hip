@@ -797,17 +797,9 @@ extern "C" int trace_encode_features(trace_ctx* c, const void* feats, int T, con
     return encode_tail(c, feats, T, time_ids, video_out, stream);
 }
 
-extern "C" int trace_splice_embeds(trace_ctx* c, const int32_t* ids, int n_ids, const int32_t* time_rows, int n_time,
-                                   const int32_t* score_rows, int n_score, int* L_out, void* embeds_out, void* stream) {
-    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
-    if (!ids || n_ids < 1) return fail(TRACE_ERR_ARG, "bad ids");
-    hipStream_t s = (hipStream_t)stream;
-    int nvid = 0;
-    for (int i = 0; i < n_ids; ++i) nvid += (ids[i] == -201 || ids[i] == -200);
-    if (nvid != 1) return fail(TRACE_ERR_ARG, "only have one video inputs!");          // trace_arch.py:411
-    if (c->video_rows <= 0) return fail(TRACE_ERR_STATE, "no encoded video");
-    const int L = n_ids - 1 + c->video_rows;
-    if (L > c->max_ctx) return fail(TRACE_ERR_ARG, "spliced prompt longer than max_ctx");
+// the L embedding rows `ids` name (a video placeholder = the rows of the last encode) gathered into pX: the body of trace_splice_embeds / trace_embed_rows
+static int splice_rows(trace_ctx* c, const int32_t* ids, int n_ids, const int32_t* time_rows, int n_time, const int32_t* score_rows, int n_score,
+                       int L, void* embeds_out, hipStream_t s) {
     TRY(stage_acquire(c));
     int r = 0, ti = 0, si = 0;
     for (int i = 0; i < n_ids; ++i) {
@@ -838,9 +830,34 @@ extern "C" int trace_splice_embeds(trace_ctx* c, const int32_t* ids, int n_ids, 
     tabs.t[0] = c->embed; tabs.t[1] = c->video; tabs.t[2] = c->time_tab; tabs.t[3] = c->score_tab; tabs.t[4] = c->sync_row;
     LCHK(launch_gather_rows(tabs, c->d_kind, c->d_row, c->pX, L, c->H, s));
     c->spliced_len = L;
-    if (L_out) *L_out = L;
     if (embeds_out) HIPCHK(hipMemcpyAsync(embeds_out, c->pX, (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
     return TRACE_OK;
+}
+
+extern "C" int trace_splice_embeds(trace_ctx* c, const int32_t* ids, int n_ids, const int32_t* time_rows, int n_time,
+                                   const int32_t* score_rows, int n_score, int* L_out, void* embeds_out, void* stream) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (!ids || n_ids < 1) return fail(TRACE_ERR_ARG, "bad ids");
+    int nvid = 0;
+    for (int i = 0; i < n_ids; ++i) nvid += (ids[i] == -201 || ids[i] == -200);
+    if (nvid != 1) return fail(TRACE_ERR_ARG, "only have one video inputs!");          // trace_arch.py:411
+    if (c->video_rows <= 0) return fail(TRACE_ERR_STATE, "no encoded video");
+    const int L = n_ids - 1 + c->video_rows;
+    if (L > c->max_ctx) return fail(TRACE_ERR_ARG, "spliced prompt longer than max_ctx");
+    TRY(splice_rows(c, ids, n_ids, time_rows, n_time, score_rows, n_score, L, embeds_out, (hipStream_t)stream));
+    if (L_out) *L_out = L;
+    return TRACE_OK;
+}
+
+// The same gather for rows that hold no video: the part of a prompt after <video>, appended to a cached prefix (trace_llm_prefill_append)
+extern "C" int trace_embed_rows(trace_ctx* c, const int32_t* ids, int n_ids, const int32_t* time_rows, int n_time,
+                                const int32_t* score_rows, int n_score, void* embeds_out, void* stream) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (!ids || n_ids < 1) return fail(TRACE_ERR_ARG, "bad ids");
+    if (n_ids > c->max_ctx) return fail(TRACE_ERR_ARG, "more rows than max_ctx");
+    for (int i = 0; i < n_ids; ++i)
+        if (ids[i] == -201 || ids[i] == -200) return fail(TRACE_ERR_ARG, "a <video> placeholder among the ids: trace_embed_rows takes rows that hold no video");
+    return splice_rows(c, ids, n_ids, time_rows, n_time, score_rows, n_score, n_ids, embeds_out, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------ frame preprocessing
@@ -945,7 +962,10 @@ extern "C" int trace_preprocess_frames(trace_ctx* c, const void* frames_u8, int 
 // prompts give the GEMMs M = 3934: 16 row tiles fill the 256x256 tile grid in whole rounds (gate|up 1792 tiles = 7.0
 // rounds instead of 896 = 3.5) and o-proj / down-proj reach the 256^2 kernel.
 int g_prefill_last_rows = 1;   // 0: the last decoder layer of a prefill runs over all rows like the others (A/B and the bit-identity test: trace_op_set_gemm_variant(750 + x))
-static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out, hipStream_t s) {
+// past > 0 (trace_llm_prefill_append): every target slot already holds `past` rows; the nb x L new rows take positions past .. past + L - 1
+// (RoPE, cache rows) and attend the cached rows 0 .. past - 1 as well: query row i of a prompt sees keys <= i + past.  Every kernel is the one
+// the past == 0 call runs, every per-row sum in the same order: a row's bits do not depend on where the prompt was cut (tests/test_gpu_prefix_reuse.py).
+static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out, hipStream_t s, int past = 0) {
     const int H = c->H, I = c->I, HD = c->HD, QKV = c->QKV, M = nb * L;
     AttnArgs a{};
     a.Q = c->pQKV; a.O = c->pO;
@@ -953,7 +973,7 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
     a.k_bs = (long)c->slot_stride; a.k_hs = (long)c->kv_head_stride; a.k_rs = HD;
     a.v_bs = (long)c->slot_stride; a.v_hs = (long)c->kv_head_stride; a.v_rs = c->ctx_pad;      // V^T straight from the cache
     a.o_bs = (long)L * H; a.o_hs = HD; a.o_rs = H;
-    a.nq_rows = L; a.nkv_rows = L; a.batch = nb; a.heads = c->NQ; a.kv_heads = c->NKV;
+    a.nq_rows = L; a.nkv_rows = past + L; a.batch = nb; a.heads = c->NQ; a.kv_heads = c->NKV;
     a.scale = 1.0f / sqrtf((float)HD); a.causal = 1;
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
@@ -970,13 +990,13 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
             const size_t last = (size_t)(L - 1);
             TRY(gemm(c->pH, H, W.wqkv + (size_t)QW * H, H, c->pQKV + QW, QKV, nullptr, nullptr, 0, M, KV, H, EPI_NONE, s));
             TRY(gemm(c->pH + last * H, L * H, W.wqkv, H, c->pQKV + last * QKV, L * QKV, nullptr, nullptr, 0, nb, QW, H, EPI_NONE, s));
-            LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, slot0, 0, M,
+            LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, slot0, past, M,
                                 c->NQ, c->NKV, HD, c->rope_cos, c->rope_sin, L, s));      // (also rotates the stale q of the other rows: 10 us, nobody reads them)
             LCHK(launch_transpose_v(c->pQKV + (size_t)(c->NQ + c->NKV) * HD, (long)L * QKV, HD, QKV, vc + (size_t)slot0 * c->slot_stride,
-                                    (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, L, HD, c->NKV, nb, s));
+                                    (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, L, HD, c->NKV, nb, s, 0, past));
             AttnArgs a1 = a;
             a1.Q = c->pQKV + last * QKV; a1.O = c->pO + last * H;
-            a1.nq_rows = 1;                                  // one query row per prompt: row L - 1 attends all L keys (causal offset nkv - nq)
+            a1.nq_rows = 1;                                  // one query row per prompt: row L - 1 attends all past + L keys (causal offset nkv - nq)
             a1.K = kc + (size_t)slot0 * c->slot_stride;
             a1.V = vc + (size_t)slot0 * c->slot_stride;
             LCHK(launch_attn_prefill(a1, s));
@@ -990,11 +1010,11 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
         }
         if (c->fp8) { TRY(gemm_fp8(c, c->pH, H, W.wqkv8, W.sqkv, c->pQKV, QKV, nullptr, 0, M, QKV, H, EPI_NONE, s)); }
         else TRY(gemm(c->pH, H, W.wqkv, H, c->pQKV, QKV, nullptr, nullptr, 0, M, QKV, H, EPI_NONE, s));
-        LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, slot0, 0, M,
+        LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, slot0, past, M,
                             c->NQ, c->NKV, HD, c->rope_cos, c->rope_sin, L, s));
-        // V goes into the cache transposed ([kvh][hd][ctx_pad]; positions L..Lpad-1 are zero-filled, later overwritten)
+        // V goes into the cache transposed ([kvh][hd][ctx_pad]; positions past+L..Lpad-1 are zero-filled, later overwritten)
         LCHK(launch_transpose_v(c->pQKV + (size_t)(c->NQ + c->NKV) * HD, (long)L * QKV, HD, QKV, vc + (size_t)slot0 * c->slot_stride,
-                                (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, L, HD, c->NKV, nb, s));
+                                (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, L, HD, c->NKV, nb, s, 0, past));
         a.K = kc + (size_t)slot0 * c->slot_stride;
         a.V = vc + (size_t)slot0 * c->slot_stride;
         LCHK(launch_attn_prefill(a, s));
@@ -1014,7 +1034,7 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
     for (int b = 0; b < nb; ++b) {
         LCHK(launch_rmsnorm(c->pX + ((size_t)b * L + L - 1) * H, H, c->xlast + (size_t)(slot0 + b) * H, H, c->final_norm, 1, H,
                             c->c.rms_eps, s));
-        c->slot_len[slot0 + b] = L;
+        c->slot_len[slot0 + b] = past + L;
     }
     return TRACE_OK;
 }
@@ -1048,6 +1068,54 @@ extern "C" int trace_llm_prefill_multi(trace_ctx* c, int slot0, const void* cons
         HIPCHK(hipMemcpyAsync(c->pX + (size_t)i * L * c->H, embeds[i], (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
     }
     return prefill_impl(c, slot0, n, L, nullptr, s);
+}
+
+// Continue n slots that hold at least `past` rows each (a prompt prefix prefilled or copied there earlier) with L new rows per slot: what
+// trace_llm_prefill_multi is for whole prompts.  Everything is checked before the first launch.
+extern "C" int trace_llm_prefill_append(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, void* hidden_out, void* stream) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (n < 1 || n > PF_MAX_N || slot0 < 0 || slot0 + n > c->max_B) return fail(TRACE_ERR_ARG, "bad slot / n");
+    if (L < 1 || past < 0) return fail(TRACE_ERR_ARG, "bad L / past");
+    if ((long)past + L > c->max_ctx) return fail(TRACE_ERR_ARG, "past + L exceeds max_ctx");
+    if ((size_t)n * L > pf_rows(c->max_ctx)) return fail(TRACE_ERR_ARG, "n x L exceeds the prefill workspace (max(4 max_ctx, min(8192, 8 max_ctx)) rows)");
+    if (!embeds && n != 1) return fail(TRACE_ERR_ARG, "the internal embedding buffer holds one prompt: embeds may be NULL with n == 1 only");
+    if (hidden_out && n != 1) return fail(TRACE_ERR_ARG, "hidden_out with n == 1 only");
+    for (int i = 0; i < n; ++i) {
+        if (embeds && !embeds[i]) return fail(TRACE_ERR_ARG, "null embeds");
+        if (past > c->slot_len[slot0 + i]) return fail(TRACE_ERR_STATE, "past exceeds the rows the slot holds");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (embeds)
+        for (int i = 0; i < n; ++i) HIPCHK(hipMemcpyAsync(c->pX + (size_t)i * L * c->H, embeds[i], (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
+    return prefill_impl(c, slot0, n, L, hidden_out, s, past);
+}
+
+// Rows [0, rows) of every layer's K and V^T from one slot to n others (launch_kv_copy, KV_COPY_MAX destinations per launch).  A copy of ALL the
+// source's rows also takes its last-position hidden row, so the destination can be decoded from as the source can.
+extern "C" int trace_kv_copy(trace_ctx* c, int src_slot, const int32_t* dst_slots, int n, int rows, void* stream) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (!dst_slots || n < 1 || n > c->max_B) return fail(TRACE_ERR_ARG, "bad dst_slots / n");
+    if (src_slot < 0 || src_slot >= c->max_B) return fail(TRACE_ERR_ARG, "source slot out of range");
+    if (rows < 1) return fail(TRACE_ERR_ARG, "bad rows");
+    if (rows > c->slot_len[src_slot]) return fail(TRACE_ERR_STATE, "rows exceeds the rows the source slot holds");
+    for (int i = 0; i < n; ++i) {
+        if (dst_slots[i] < 0 || dst_slots[i] >= c->max_B) return fail(TRACE_ERR_ARG, "destination slot out of range");
+        if (dst_slots[i] == src_slot) return fail(TRACE_ERR_ARG, "the source slot is among the destinations");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    for (int i0 = 0; i0 < n; i0 += KV_COPY_MAX) {
+        KvCopyDst d{};
+        d.n = std::min(KV_COPY_MAX, n - i0);
+        for (int i = 0; i < d.n; ++i) d.slot[i] = dst_slots[i0 + i];
+        LCHK(launch_kv_copy(c->kcache, c->vcache, (long)c->layer_stride, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->HD, c->NL,
+                            c->NKV, src_slot, d, rows, s));
+    }
+    for (int i = 0; i < n; ++i) {
+        if (rows == c->slot_len[src_slot])
+            HIPCHK(hipMemcpyAsync(c->xlast + (size_t)dst_slots[i] * c->H, c->xlast + (size_t)src_slot * c->H, (size_t)c->H * 2, hipMemcpyDeviceToDevice, s));
+        c->slot_len[dst_slots[i]] = rows;
+    }
+    return TRACE_OK;
 }
 
 // masked logits of R final-norm hidden rows under ONE head: what forward() returns for every position of a sequence

@@ -114,9 +114,10 @@ struct AttnArgs {
 // NB: V is passed PRE-TRANSPOSED: V^T[d, kv] with row stride v_rs (multiple of 64, >= nkv_rows, zero padded)
 int launch_attn_vit(const AttnArgs& a, hipStream_t s);       // head_dim 64, non-causal, heads == kv_heads
 int launch_attn_prefill(const AttnArgs& a, hipStream_t s);   // head_dim 128, causal, GQA 4:1
-// V [n, hd] (row stride src_rs) -> V^T [hd, dst_rs] per (batch, head); zero fill beyond n
+// V [n, hd] (row stride src_rs) -> V^T [hd, dst_rs] per (batch, head) at positions p0 .. p0 + n - 1; zero fill from p0 + n to the end of
+// that 64-position block; positions < p0 keep what they hold (p0 need not be a multiple of 8)
 int launch_transpose_v(const bf16_t* src, long src_bs, long src_hs, int src_rs, bf16_t* dst, long dst_bs, long dst_hs,
-                       int dst_rs, int n, int hd, int heads, int batch, hipStream_t s, int perm = 0);
+                       int dst_rs, int n, int hd, int heads, int batch, hipStream_t s, int perm = 0, int p0 = 0);
 // true: launch_attn_vit can run its LDS-DMA kernel for this key count -> transpose V with perm = 1 and set AttnArgs::v_perm
 bool attn_vit_wants_perm(int nkv_rows, bool has_vrow);
 // true: with attn_vit_wants_perm(), set v_perm = 2 and skip launch_transpose_v altogether (false only under an A/B debug switch)
@@ -140,6 +141,14 @@ int launch_gather_rows(const GatherTabs& tabs, const int32_t* kind, const int32_
 int launch_rope_kv(bf16_t* qkv, int ld, bf16_t* kcache, bf16_t* vcache, long slot_stride, long kv_head_stride,
                    const int32_t* slot_arr, const int32_t* pos_arr, int slot0, int pos0, int R, int nq, int nkv, int hd,
                    const float* cos_t, const float* sin_t, int seq_len, hipStream_t s);   // seq_len > 0: R/seq_len prefill sequences end to end -> slots slot0, slot0+1, ...
+
+// KV-cache rows [0, rows) of every layer from slot `src` to the n <= KV_COPY_MAX slots dst.slot[]: K [layer][slot][kv head][ctx_pad][hd] (rows x hd
+// contiguous elements per kv head) and V^T [layer][slot][kv head][hd][ctx_pad] (rows rounded up to 8 positions out of every ctx_pad).  One launch,
+// every 16-byte chunk read once and stored n times.  ctx_pad % 8 == 0, hd % 8 == 0.
+constexpr int KV_COPY_MAX = 16;
+struct KvCopyDst { int n; int slot[KV_COPY_MAX]; };
+int launch_kv_copy(bf16_t* kcache, bf16_t* vtcache, long layer_stride, long slot_stride, long kv_head_stride, int ctx_pad, int hd, int layers,
+                   int kv_heads, int src, const KvCopyDst& dst, int rows, hipStream_t s);
 
 // ---- decode (decode.hip) ----
 // out[b, n] = sum_k X[b,k] W[n,k]  (B <= 64) (+ residual / SwiGLU on interleaved W)

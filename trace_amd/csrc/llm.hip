@@ -3,8 +3,12 @@
 //                  410-426 prefill; the per-frame [8 slots | 6 time tokens] interleave of :240-258)
 //   rope_kv      — rotate-half RoPE on q (in place) and k (HF modeling_mistral apply_rotary_pos_emb), and the
 //                  KV-cache append, for prefill rows or one decode row per sequence.
+//   kv_copy      — the first `rows` positions of one KV slot to other slots, all layers in one launch (a prompt prefix computed
+//                  once and shared by several sequences: the reference's per-question loop over one video,
+//                  trace/eval/videomme/evaluate.py:349-386).
 #include "common.h"
 #include "kernels.h"
+#include <algorithm>
 
 namespace {
 
@@ -68,7 +72,41 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(bf16_t* __restrict__ qkv, 
         *reinterpret_cast<uint4*>(dst + half + c * 8) = make_uint4(o2[0], o2[1], o2[2], o2[3]);
     }
 }
+// blockIdx.y = layer * kv_heads + kv head.  Per (layer, kv head) the work is kchunks = rows * hd / 8 contiguous 16-byte chunks of K followed by
+// hd runs of vchunks = ceil(rows / 8) chunks of V^T (run stride ctx_pad): consecutive lanes take consecutive chunks of a run.
+__global__ __launch_bounds__(256) void kv_copy_kernel(bf16_t* __restrict__ kcache, bf16_t* __restrict__ vtcache, long layer_stride,
+                                                      long slot_stride, long kv_head_stride, int ctx_pad, int hd, int kv_heads, int src,
+                                                      KvCopyDst dst, int rows) {
+    const int layer = blockIdx.y / kv_heads, kvh = blockIdx.y - layer * kv_heads;
+    const size_t base = (size_t)layer * layer_stride + (size_t)kvh * kv_head_stride;
+    const int kchunks = rows * (hd >> 3), vchunks = (rows + 7) >> 3;
+    const int total = kchunks + hd * vchunks;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        bf16_t* cache = kcache;
+        size_t off;
+        if (i < kchunks) off = base + (size_t)i * 8;
+        else {
+            const int j = i - kchunks, d = j / vchunks, c = j - d * vchunks;
+            cache = vtcache;
+            off = base + (size_t)d * ctx_pad + (size_t)c * 8;
+        }
+        const uint4 v = *reinterpret_cast<const uint4*>(cache + (size_t)src * slot_stride + off);
+        for (int k = 0; k < dst.n; ++k) *reinterpret_cast<uint4*>(cache + (size_t)dst.slot[k] * slot_stride + off) = v;
+    }
+}
 }  // namespace
+
+int launch_kv_copy(bf16_t* kcache, bf16_t* vtcache, long layer_stride, long slot_stride, long kv_head_stride, int ctx_pad, int hd, int layers,
+                   int kv_heads, int src, const KvCopyDst& dst, int rows, hipStream_t s) {
+    if (rows < 1 || rows > ctx_pad || ctx_pad % 8 || hd % 8 || dst.n < 1 || dst.n > KV_COPY_MAX || layers < 1 || kv_heads < 1 ||
+        (long)layers * kv_heads > 65535) return TRACE_ERR_ARG;
+    const long total = (long)rows * (hd / 8) + (long)hd * ((rows + 7) / 8);
+    if (total > 0x7fffffffL - 65536L * 256) return TRACE_ERR_ARG;
+    const int gx = (int)std::min<long>((total + 255) / 256, 64);       // layers x kv heads x 64 workgroups: a few waves of the chip at 32 x 8
+    hipLaunchKernelGGL(kv_copy_kernel, dim3(gx, layers * kv_heads), dim3(256), 0, s, kcache, vtcache, layer_stride, slot_stride, kv_head_stride,
+                       ctx_pad, hd, kv_heads, src, dst, rows);
+    return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
+}
 
 int launch_gather_rows(const GatherTabs& tabs, const int32_t* kind, const int32_t* row, bf16_t* out, int L, int H,
                        hipStream_t s) {

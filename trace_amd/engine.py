@@ -10,6 +10,7 @@ import torch
 from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
+from .prefix import APPEND_GROUP_MAX, group_by_length, split_questions
 from .sampling import SamplingParams, sample_rows_host
 
 __all__ = ["TraceEngine", "SamplingParams", "ops"]
@@ -81,6 +82,8 @@ class TraceEngine:
         self._max_new = 0
         self._stage_ev = None          # stage_timing(): [(kind, event, event)] while on
         self._stage_videos = 0
+        self.stats = {"vit_frames": 0, "prefill_rows": 0}      # frames the tower has run / rows prefilled so far (what prefix reuse saves is read off these)
+        self._prefix = None            # (key, rows): KV slot 0 holds `rows` prefilled prompt rows described by `key` (set_prefix_entry); see _drop_prefix
         self._dbg = None               # debugging hook: callable(tag, index, tensor-or-None) called between the stages (tools/pipeline_stress.py)
 
     @property
@@ -159,6 +162,7 @@ class TraceEngine:
     def vit_forward(self, frames: torch.Tensor, want_output: bool = True) -> Optional[torch.Tensor]:
         frames, dt = self._frames(frames)
         T = frames.shape[0]
+        self.stats["vit_frames"] += T
         if not want_output:
             _lib.check(self.lib.trace_vit_forward(self.h, _ptr(frames), dt, T, None, _stream()))
             return None
@@ -175,6 +179,7 @@ class TraceEngine:
 
     def stc_connector(self, feats: Optional[torch.Tensor], T: int) -> torch.Tensor:
         """Legacy STC connector (projector_type 'stc_connector'); result also becomes the video rows for splice()."""
+        self._drop_prefix()
         g = self.cfg.vision_grid // 2 + 1
         rows = (T // 2 + 1) * g * g
         out = torch.empty((rows, self.cfg.hidden_size), dtype=self.dtype, device=self.device)
@@ -194,8 +199,10 @@ class TraceEngine:
         return [i for x in toks for i in x[:-1]]
 
     def encode_video(self, frames: torch.Tensor, timestamps, want_output: bool = False):
+        self._drop_prefix()
         frames, dt = self._frames(frames)
         T = frames.shape[0]
+        self.stats["vit_frames"] += T
         ids = _i32(self.time_ids(timestamps))
         out = None
         if want_output:
@@ -205,6 +212,7 @@ class TraceEngine:
 
     def encode_features(self, feats: torch.Tensor, timestamps, want_output: bool = False):
         """encode_video from ViT features computed earlier (vit_forward on a frame batch that may span several videos)"""
+        self._drop_prefix()
         T = feats.shape[0]
         assert feats.dtype == self.dtype and feats.is_cuda and feats.is_contiguous()
         ids = _i32(self.time_ids(timestamps))
@@ -233,6 +241,7 @@ class TraceEngine:
             if not chunk_n:
                 return
             x = chunk[0] if len(chunk) == 1 else torch.cat(chunk, dim=0)
+            self.stats["vit_frames"] += chunk_n
             _lib.check(self.lib.trace_vit_forward(self.h, _ptr(x.contiguous()), dt, chunk_n, _ptr(feats[pos:pos + chunk_n]), _stream()))
             pos += chunk_n
             chunk, chunk_n = [], 0
@@ -268,8 +277,63 @@ class TraceEngine:
         hid = torch.empty((L, self.cfg.hidden_size), dtype=self.dtype, device=self.device) if want_hidden else None
         if embeds is not None:
             embeds = embeds.to(self.device, self.dtype).contiguous()
+        if slot == 0:
+            self._drop_prefix()
         _lib.check(self.lib.trace_llm_prefill(self.h, slot, _ptr(embeds), L, _ptr(hid), _stream()))
+        self.stats["prefill_rows"] += L
         return hid
+
+    # ---- prompt-prefix reuse: continue a slot that holds rows, copy rows between slots, embed rows without a video ----
+    def embed_rows(self, ids: Sequence[int], time_rows: Sequence[int] = (), score_rows: Sequence[int] = (), want_output: bool = False):
+        """splice() for rows that hold no <video> (trace_embed_rows): the embeddings stay in the engine's buffer for prefill_append(embeds=None);
+        want_output returns a copy [len(ids), hidden]."""
+        arr, tr, sr = _i32(ids), _i32(time_rows), _i32(score_rows)
+        out = torch.empty((len(arr), self.cfg.hidden_size), dtype=self.dtype, device=self.device) if want_output else None
+        _lib.check(self.lib.trace_embed_rows(self.h, arr, len(arr), tr, len(tr), sr, len(sr), _ptr(out), _stream()))
+        return out
+
+    def prefill_append(self, slot0: int, past: int, embeds=None, L: Optional[int] = None, want_hidden: bool = False):
+        """L new rows at positions past .. past + L - 1 of slots slot0 .. slot0 + n - 1, each of which holds at least `past` rows
+        (trace_llm_prefill_append).  embeds: one [L, hidden] tensor, a list of up to 8 of equal shape (one per slot), or None = the rows of the
+        last embed_rows() (then L is required).  want_hidden (one slot): the [L, hidden] final-norm rows."""
+        if embeds is None:
+            if L is None:
+                raise ValueError("prefill_append(embeds=None) needs L, the row count of the last embed_rows()")
+            keep, n = [], 1
+        else:
+            keep = [e.to(self.device, self.dtype).contiguous() for e in ([embeds] if isinstance(embeds, torch.Tensor) else list(embeds))]
+            n = len(keep)
+            if not 1 <= n <= APPEND_GROUP_MAX or any(e.dim() != 2 or e.shape != keep[0].shape or e.shape[1] != self.cfg.hidden_size for e in keep):
+                raise ValueError(f"embeds: 1 to {APPEND_GROUP_MAX} tensors of one shape [L, hidden]")
+            L = keep[0].shape[0]
+        if want_hidden and n != 1:
+            raise ValueError("want_hidden with one slot only")
+        hid = torch.empty((L, self.cfg.hidden_size), dtype=self.dtype, device=self.device) if want_hidden else None
+        ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in keep]) if keep else None
+        if self._prefix is not None and slot0 == 0 and past < self._prefix[1]:
+            self._drop_prefix()
+        _lib.check(self.lib.trace_llm_prefill_append(self.h, int(slot0), n, int(past), ptrs, int(L), _ptr(hid), _stream()))
+        self.stats["prefill_rows"] += n * L
+        return hid
+
+    def kv_copy(self, src: int, dsts: Sequence[int], rows: int):
+        """KV rows [0, rows) of slot `src` to every slot of `dsts` (trace_kv_copy); their length becomes `rows`."""
+        dsts = [int(d) for d in dsts]
+        if 0 in dsts:
+            self._drop_prefix()
+        _lib.check(self.lib.trace_kv_copy(self.h, int(src), _i32(dsts), len(dsts), int(rows), _stream()))
+
+    # The model's prefix cache (TraceMistralForCausalLM.enable_prefix_cache) keeps its one entry in KV slot 0.  Whether the slot still holds those rows is
+    # decided here: every call that rewrites slot 0 from row 0 or below the entry's length, or encodes a video (the entry's owner then no longer knows
+    # which video the engine last saw), drops it.  Decoding never does: it writes rows at and above the slot's length.
+    def set_prefix_entry(self, key, rows: int):
+        self._prefix = (key, int(rows))
+
+    def prefix_entry(self):
+        return self._prefix
+
+    def _drop_prefix(self):
+        self._prefix = None
 
     def head_logits(self, hidden: torch.Tensor, head: int) -> torch.Tensor:
         """masked fp32 logits [R, total_vocab] of final-norm hidden rows under one head (forward()'s logits at every position)"""
@@ -281,8 +345,11 @@ class TraceEngine:
     def prefill_pair(self, slot0: int, embeds0: torch.Tensor, embeds1: torch.Tensor):
         """two spliced prompts of equal length -> KV slots slot0, slot0 + 1 in one pass (trace_llm_prefill_pair)"""
         assert embeds0.shape == embeds1.shape and embeds0.dtype == self.dtype and embeds0.is_cuda
+        if slot0 == 0:
+            self._drop_prefix()
         _lib.check(self.lib.trace_llm_prefill_pair(self.h, slot0, _ptr(embeds0.contiguous()), _ptr(embeds1.contiguous()),
                                                    embeds0.shape[0], _stream()))
+        self.stats["prefill_rows"] += 2 * embeds0.shape[0]
 
     PREFILL_GROUP = 4          # equal-length prompts of max_ctx rows one prefill pass takes (trace_llm_prefill_multi); shorter prompts: prefill_group(L)
     PREFILL_GROUP_MAX = 8
@@ -318,7 +385,10 @@ class TraceEngine:
         assert 1 <= n <= self.PREFILL_GROUP_MAX and n * embeds[0].shape[0] <= self.prefill_rows and all(e.shape == embeds[0].shape and e.dtype == self.dtype and e.is_cuda for e in embeds)
         keep = [e.contiguous() for e in embeds]
         ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in keep])
+        if slot0 == 0:
+            self._drop_prefix()
         _lib.check(self.lib.trace_llm_prefill_multi(self.h, slot0, ptrs, n, keep[0].shape[0], _stream()))
+        self.stats["prefill_rows"] += n * keep[0].shape[0]
 
     # ---- decode --------------------------------------------------------------------------------
     def decode_begin(self, slots: Sequence[int], heads: Sequence[int], max_new: int, eos: int = -1,
@@ -535,6 +605,41 @@ class TraceEngine:
             raise ValueError(f"batch {B} exceeds the engine's decode batch {self.decode_batch_max}")
         self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
         return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling)
+
+    def generate_questions(self, video: torch.Tensor, timestamps, prompts: Sequence[Sequence[int]], heads: Sequence[int], max_new_tokens: int,
+                           eos: int = -1, sampling: Optional[SamplingParams] = None, use_graph: bool = True,
+                           forced: Optional[Sequence[Sequence[int]]] = None, prefix_key=None):
+        """generate() for Q prompts about ONE video whose ids agree up to and including the <video> placeholder (the reference's per-question
+        loops, trace/eval/videomme/evaluate.py:349-386): the tower, the slot pool and the prefill of the common prefix run once (slot 0), the
+        prefix's KV rows are copied to the other Q - 1 slots, each prompt's rows after <video> are appended (one pass per group of equal
+        length, at most 8 prompts each, over consecutive slots), and all Q rows decode as one batch — row q is prompt q, as in generate().
+        Returns what generate() returns, bit-identical to it.  prefix_key: recorded with set_prefix_entry() once slot 0 holds the shared rows."""
+        Q = len(prompts)
+        if Q > min(self.max_batch, self.decode_batch_max):
+            raise ValueError(f"{Q} prompts exceed the engine's KV slots / decode batch ({self.max_batch} / {self.decode_batch_max})")
+        if len(heads) != Q:
+            raise ValueError("one head per prompt")
+        prefix, suffixes = split_questions(prompts)
+        if any(len(x) == 0 for x in suffixes):
+            raise ValueError("a prompt ends at its video placeholder: nothing to append (use generate())")
+        groups = group_by_length([len(x) for x in suffixes])
+        self.encode_video(video, timestamps)
+        P = self.splice(prefix)
+        self.prefill(0, P)
+        if Q > 1:
+            self.kv_copy(0, list(range(1, Q)), P)
+        slot_of, slot = [0] * Q, 0
+        for n_rows, idx in groups:
+            cap = max(1, self.prefill_rows // n_rows)          # a run of long suffixes must also fit the prefill workspaces
+            for o in range(0, len(idx), cap):
+                run = idx[o:o + cap]
+                self.prefill_append(slot, P, [self.embed_rows(suffixes[i], want_output=True) for i in run])
+                for i in run:
+                    slot_of[i] = slot
+                    slot += 1
+        if prefix_key is not None:
+            self.set_prefix_entry(prefix_key, P)
+        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling)
 
     # ---- two-stage pipeline over a stream of batches ---------------------------------------------------
     def make_streams(self, decode_cus: int = 0):

@@ -12,6 +12,7 @@ import torch
 
 from ..config import TraceConfig
 from ..constants import MMODAL_TOKEN_INDEX, NUM_FRAMES
+from ..prefix import split_questions
 from ..sampling import SamplingParams, check_sampling
 from .encoders import NumberTokenizer, ScoreTower, TimeTower
 
@@ -69,6 +70,56 @@ class TraceMistralForCausalLM:
         self.dtype = engine.dtype
         # HF GenerationConfig defaults; builder.load_pretrained_model overrides them from the checkpoint's generation_config.json
         self.generation_config = SimpleNamespace(do_sample=False, temperature=1.0, top_k=50, top_p=1.0)
+        self._prefix_cache = False
+
+    # ---- prompt-prefix reuse across generate() calls ----
+    def enable_prefix_cache(self, on: bool = True):
+        """One video, several questions (the reference's drivers call generate once per question with the same frame tensor and a prompt that
+        is identical through `<video>`, trace/eval/videomme/evaluate.py:349-386): with the cache on, generate() prefills a prompt in two
+        passes — the rows through `<video>`, then the rows after it — and a B = 1 call whose frame tensor (the same object, not edited in
+        place since), timestamps, modal and ids through `<video>` equal the previous call's skips the tower, the slot pool and the first pass:
+        the rows are still in KV slot 0.  A B > 1 call whose rows all name one tensor object encodes and prefills the shared rows once
+        (TraceEngine.generate_questions).  Results are bit-identical to the cache being off.  Off by default: an enabled cache keeps a
+        reference to the caller's frame tensor after generate() returns; enable_prefix_cache(False) drops it."""
+        self._prefix_cache = bool(on)
+        self.engine._drop_prefix()
+        return self
+
+    @property
+    def prefix_cache_enabled(self) -> bool:
+        return self._prefix_cache
+
+    def _generate_prefix_cached(self, raw, vids, modals, timestamps, id_lists, heads, max_new_tokens, eos, sampling):
+        """generate()'s main path with the cache on; None = this call is not of the cacheable shape (today's path runs)."""
+        eng, B = self.engine, len(vids)
+        try:
+            prefix, suffixes = split_questions(id_lists)
+        except ValueError:
+            return None
+        if any(len(x) == 0 for x in suffixes):
+            return None
+        ts_of = lambda ts: tuple(tuple(float(v) for v in (t if hasattr(t, "__iter__") else (t,))) for t in ts)      # one tuple of stamps per frame
+        ts_key = ts_of(timestamps[0])
+        if B > 1:
+            if any(r is not raw[0] for r in raw[1:]) or any(m != modals[0] for m in modals[1:]) or any(ts_of(t) != ts_key for t in timestamps[1:]):
+                return None
+            if B > eng.decode_batch_max:
+                return None
+        key = (raw[0], raw[0]._version, ts_key, modals[0], tuple(prefix))
+        if B > 1:
+            return eng.generate_questions(vids[0], timestamps[0], id_lists, heads, max_new_tokens, eos=eos, sampling=sampling, prefix_key=key)
+        ent = eng.prefix_entry()
+        hit = ent is not None and ent[0][0] is key[0] and ent[0][1:] == key[1:]
+        if hit:
+            P = ent[1]
+        else:
+            eng.encode_video(vids[0], timestamps[0])
+            P = eng.splice(prefix)
+            eng.prefill(0, P)
+            eng.set_prefix_entry(key, P)
+        eng.embed_rows(suffixes[0])
+        eng.prefill_append(0, P, None, L=len(suffixes[0]))
+        return eng.decode([0], heads, max_new_tokens, eos, sampling=sampling)
 
     # ---- nn.Module-like conveniences the drivers call ----
     def get_model(self):
@@ -126,7 +177,8 @@ class TraceMistralForCausalLM:
             raise ValueError("video_timestamps is required on the TRACE path (time tokens per frame)")
         nf = cfg.num_frames if hasattr(cfg, "num_frames") else NUM_FRAMES
         vids = []
-        for x, modal in zip(images_or_videos, modal_list or ["video"] * B):
+        modals = list(modal_list or ["video"] * B)
+        for x, modal in zip(images_or_videos, modals):
             if modal == "image":                                                  # trace_arch.py:221
                 x = x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
             vids.append(x)
@@ -150,7 +202,10 @@ class TraceMistralForCausalLM:
                     eng.decode_steps(max_new_tokens - 1)
                 out, new_heads = eng.decode_read()
         elif not stopping_criteria:
-            out, new_heads = eng.generate(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos=eos, sampling=sampling)
+            res = None
+            if self._prefix_cache and all(isinstance(x, torch.Tensor) for x in images_or_videos):
+                res = self._generate_prefix_cached(list(images_or_videos), vids, modals, video_timestamps, id_lists, list(heads), max_new_tokens, eos, sampling)
+            out, new_heads = res if res is not None else eng.generate(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos=eos, sampling=sampling)
         else:
             out, new_heads = self._generate_stepwise(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos,
                                                      sampling, stopping_criteria, ids)
