@@ -179,6 +179,24 @@ int trace_decode_feed(trace_ctx* ctx, const int32_t* tokens, int B, void* stream
  * The params live in device memory: a captured decode step (use_graph) stays valid when they change between calls. */
 int trace_decode_set_sampling(trace_ctx* ctx, float temperature, int top_k, float top_p, uint64_t seed);
 
+/* Per-token log-probabilities, computed on the device inside the decode step.  Set before trace_decode_begin; it holds for every later batch
+ * until changed (like trace_decode_set_sampling).  The first call with on != 0 allocates the masked-logits rows and [256][max_new_tokens] floats.
+ * For row b at step s, with head = the row's active head at that step, [lo, hi) its id range, and x the RAW masked fp32 logits of that range as
+ * the head stage writes them (no temperature, no top-k, no top-p: the model's distribution, not the warped one):
+ *     logprob[b][s] = (x[id] - M) - log(S),   M = max x,   S = sum_i exp(x_i - M)
+ * id = the token recorded in out_ids[b][s] (under forced ids: the model's own choice; an id outside [lo, hi) gives -inf).  S is formed exactly
+ * as the sampler forms its sums: weights from the sampler's exp, thread t of 256 sums the id-order run [t C, (t + 1) C), C = ceil((hi - lo) / 256),
+ * then a Hillis-Steele scan over the 256 run totals; no FMA contraction anywhere.  log (arguments >= 1: the maximum contributes exp(0)) is
+ * the odd atanh series of csrc/sample.h sample_log, every operation rounded on its own.  trace_amd/sampling.py token_logprob_ref restates it
+ * in float32 and reproduces the device value bit for bit; greedy or sampled, eager or graph-replayed, the value is the same.
+ * Entries past a row's length are 0.0, so a plain sum over a row is the sequence score; the EOS token's entry is included.
+ * Host-select mode (trace_decode_host_mode) computes nothing: the host holds the logits and calls trace_op_token_logprob on them.
+ * With the setting off a decode batch issues the launches and replays the graphs it did before (steps with the extra launch are cached apart).
+ * trace_decode_read_logprobs: synchronises and copies [B, max_new] floats to a HOST buffer; TRACE_ERR_STATE if the current batch was begun
+ * without log-probabilities. */
+int trace_decode_set_logprobs(trace_ctx* ctx, int on);
+int trace_decode_read_logprobs(trace_ctx* ctx, float* out, void* stream);
+
 /* Two-stage pipeline support (trace/eval/evaluate.py:298-417 loops over independent videos: while one batch decodes — HBM-bound —
  * the next batch's ViT + prefill — MFMA-bound — can run on another stream into other KV slots; the stages share no buffers).
  * trace_stream_create: a HIP stream confined to cu_count CUs starting at logical CU cu_first (hipExtStreamCreateWithCUMask; mask bit i
@@ -261,6 +279,10 @@ int trace_op_add_rmsnorm(const float* part, int KS, const void* R, void* xout, c
  * T > 0 and the domain above; row b uses counter (steps[b], 0, b, 0). */
 int trace_op_sample(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, float T, int top_k, float top_p,
                     uint64_t seed, const int32_t* steps, int32_t* out_ids, void* stream);
+/* The log-probability above over loose rows, the same device code: logits [B][ld] fp32 device (only the head's range is read), heads / ids
+ * int32 [B] device (active head, global vocabulary id), out fp32 [B] device; an id outside the head's range gives -inf. */
+int trace_op_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out,
+                           void* stream);
 int trace_op_attn_decode(const void* q, const void* kcache, const void* vtcache, const int32_t* pos, void* O, float* ws,
                          int B, int nq, int nkv, int max_ctx, int nsplit, float scale, void* stream);
 

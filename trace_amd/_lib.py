@@ -59,6 +59,8 @@ SIGNATURES = {
     "trace_decode_host_mode": (I, [P, I]),
     "trace_decode_feed": (I, [P, P, I, P]),
     "trace_decode_set_sampling": (I, [P, F, I, F, C.c_uint64]),
+    "trace_decode_set_logprobs": (I, [P, I]),
+    "trace_decode_read_logprobs": (I, [P, P, P]),
     "trace_stream_create": (I, [P, I, I, C.POINTER(P)]),
     "trace_stream_destroy": (I, [P, P]),
     "trace_set_gemm_cus": (I, [P, I]),
@@ -87,6 +89,7 @@ SIGNATURES = {
     "trace_op_swiglu_combine": (I, [P, I, I, P, I, P]),
     "trace_op_add_rmsnorm": (I, [P, I, P, P, P, P, I, I, F, P]),
     "trace_op_sample": (I, [P, I, I, P, I, I, I, F, I, F, C.c_uint64, P, P, P]),
+    "trace_op_token_logprob": (I, [P, I, I, P, I, I, I, P, P, P]),
     "trace_op_attn_decode": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
 }
 

@@ -112,12 +112,18 @@ struct trace_ctx {
     int steps_done = 0;                // decode steps taken since trace_decode_begin (bounded by max_new - 1: the KV slot and the RoPE tables end at max_ctx)
     hipGraphExec_t graphs[SK_ROWS + 1] = {nullptr};   // one captured decode step per batch size
     hipGraphExec_t graphs_sample[SK_ROWS + 1] = {nullptr};   // the same with the sampling form of the token selection
+    hipGraphExec_t graphs_lp[SK_ROWS + 1] = {nullptr};          // both again with the log-probability launch after the selection: a step with it is
+    hipGraphExec_t graphs_sample_lp[SK_ROWS + 1] = {nullptr};   // another graph, so toggling the setting between batches never replays the other form
     // sampling (trace_decode_set_sampling): host copy of the params, armed at trace_decode_begin; the device copy d_sparams is what the
     // selection kernel reads (a captured graph stays valid across calls), d_slog the [SK_ROWS][NV] masked logits it samples from
     SampleParams samp{};
     int samp_set = 0, samp_on = 0;
     SampleParams* d_sparams = nullptr;
     float* d_slog = nullptr;
+    // per-token log-probabilities (trace_decode_set_logprobs): armed at trace_decode_begin like the sampling; d_logprobs [SK_ROWS][max_new_tokens]
+    // (rows of the current batch at stride max_new), written by the launch after the selection from the same d_slog rows
+    int lp_set = 0, lp_on = 0;
+    float* d_logprobs = nullptr;
     hipStream_t cap_stream = nullptr;
     std::vector<hipStream_t> streams;   // trace_stream_create
     // profiling
@@ -332,6 +338,8 @@ extern "C" int trace_ctx_destroy(trace_ctx* c) {
     for (auto& st : c->streams) { gemm_pers_forget(st); hipStreamDestroy(st); }
     for (auto& g : c->graphs) if (g) hipGraphExecDestroy(g);
     for (auto& g : c->graphs_sample) if (g) hipGraphExecDestroy(g);
+    for (auto& g : c->graphs_lp) if (g) hipGraphExecDestroy(g);
+    for (auto& g : c->graphs_sample_lp) if (g) hipGraphExecDestroy(g);
     for (auto& e : c->kev) if (e) hipEventDestroy(e);
     for (auto& e : c->vev) if (e) hipEventDestroy(e);
     if (c->mev0) hipEventDestroy(c->mev0);
@@ -1151,11 +1159,14 @@ static int select_only(trace_ctx* c, int advance, hipStream_t s, const float* sa
     return TRACE_OK;
 }
 static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* logits_out, hipStream_t s) {
-    // sampling: the selection draws from the masked logits rows the head kernel writes (the caller's logits_out, else d_slog)
-    float* lg = c->samp_on && !c->host_mode && !logits_out ? c->d_slog : logits_out;
+    // sampling / log-probabilities: both read the masked logits rows the head kernel writes (the caller's logits_out, else d_slog)
+    float* lg = (c->samp_on || c->lp_on) && !c->host_mode && !logits_out ? c->d_slog : logits_out;
     TRY(head_only(c, xn, lg, s));
     if (c->host_mode) return TRACE_OK;      // the host picks the token and calls trace_decode_feed
-    return select_only(c, advance, s, c->samp_on ? lg : nullptr);
+    TRY(select_only(c, advance, s, c->samp_on ? lg : nullptr));
+    // the log-probability of the token just recorded: after the selection (it reads out_ids / out_len / the advanced step counter), from the same rows
+    if (c->lp_on) LCHK(launch_step_logprob(lg, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_logprobs, s));
+    return TRACE_OK;
 }
 
 // decode attention context split: ~256-320 workgroups (8 kv heads x B x nsplit) fill the CUs; more splits only add
@@ -1377,6 +1388,8 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     HIPCHK(hipMemcpyAsync(c->d_params, prm, 12, hipMemcpyHostToDevice, s));
     c->samp_on = c->samp_set && !c->host_mode;     // host-select mode: the host picks (trace_op_sample), the device only feeds
     if (c->samp_on) HIPCHK(hipMemcpyAsync(c->d_sparams, &c->samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+    c->lp_on = c->lp_set && !c->host_mode;         // host-select mode: the host has the logits and calls trace_op_token_logprob on them
+    if (c->lp_on) HIPCHK(hipMemsetAsync(c->d_logprobs, 0, (size_t)B * max_new * 4, s));    // entries past a row's length stay 0.0
     c->fed = 0; c->steps_done = 0;
     if (forced) HIPCHK(hipMemcpyAsync(c->d_forced, forced, (size_t)B * max_new * 4, hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemsetAsync(c->d_forced, 0xff, (size_t)B * max_new * 4, s));      // -1 = not forced
@@ -1404,7 +1417,8 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
         for (int i = 0; i < n; ++i) { c->step_in_call = steps_before + i; TRY(decode_step(c, logits_out, s)); }
     } else {
         const int key = c->B;
-        hipGraphExec_t* slot_g = c->samp_on ? &c->graphs_sample[key] : &c->graphs[key];
+        hipGraphExec_t* slot_g = c->lp_on ? (c->samp_on ? &c->graphs_sample_lp[key] : &c->graphs_lp[key])
+                                          : (c->samp_on ? &c->graphs_sample[key] : &c->graphs[key]);
         if (!*slot_g) {
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamSynchronize(s));
@@ -1478,6 +1492,34 @@ extern "C" int trace_decode_set_sampling(trace_ctx* c, float temperature, int to
     if (!c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
     c->samp = make_sampling(temperature, top_k, top_p, seed);
     c->samp_set = 1;
+    return TRACE_OK;
+}
+
+extern "C" int trace_decode_set_logprobs(trace_ctx* c, int on) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (on) {
+        if (!c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
+        if (!c->d_logprobs) TRY(dalloc(c, &c->d_logprobs, (size_t)SK_ROWS * c->c.max_new_tokens));
+    }
+    c->lp_set = on ? 1 : 0;
+    return TRACE_OK;
+}
+
+extern "C" int trace_decode_read_logprobs(trace_ctx* c, float* out, void* stream) {
+    if (!c || c->B < 1) return fail(TRACE_ERR_STATE, "trace_decode_begin not called");
+    if (!c->lp_on) return fail(TRACE_ERR_STATE, "the current batch was begun without log-probabilities (trace_decode_set_logprobs)");
+    if (!out) return fail(TRACE_ERR_ARG, "null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(out, c->d_logprobs, (size_t)c->B * c->max_new * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return TRACE_OK;
+}
+
+extern "C" int trace_op_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out,
+                                      void* stream) {
+    if (!logits || !heads || !ids || !out) return fail(TRACE_ERR_ARG, "null pointer");
+    const int rc = launch_token_logprob(logits, ld, B, heads, V, Tv, Sv, ids, out, (hipStream_t)stream);
+    if (rc != TRACE_OK) return fail(rc, "token_logprob launch failed (B, ld or head widths out of range)");
     return TRACE_OK;
 }
 

@@ -210,6 +210,11 @@ int launch_select_next(const float* part_val, const int32_t* part_idx, const Ste
 // heads / steps int32 [B] (device) -> out_ids [B] global ids
 int launch_sample_rows(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const SampleParams& sp, const int32_t* steps,
                        int32_t* out_ids, hipStream_t s);
+// log-probability of one token per row (sample.h token_logprob_row; the raw masked logits, no warping).  Loose rows: ids / heads int32 [B],
+// out fp32 [B] (trace_op_token_logprob).  Decode step: after launch_select_next on the same stream, over the rows of masked logits the head
+// kernel wrote for this step [B][NV]; writes out_logprobs[b][step] ([B][max_new]) where select_next recorded a token in this step.
+int launch_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out, hipStream_t s);
+int launch_step_logprob(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, float* out_logprobs, hipStream_t s);
 
 // ---- fp8 (e4m3) weight path of the decoder (fp8.hip; the fp8 GEMM is launch_gemm_bf16 with GemmArgs::fp8 set) ----
 // X bf16 [rows][K] -> X8 e4m3 [rows][K] + sx[row] = amax/448 (per-row dynamic scale).  Also used row-wise on weight matrices at load.

@@ -83,6 +83,68 @@ __device__ __forceinline__ V sample_scan(V v, V* buf) {
     return v;
 }
 
+// log(s) for s >= 1 (finite): s = m 2^e with m in (sqrt(1/2), sqrt(2)], log m = 2 atanh(t), t = (m - 1) / (m + 1), as the odd series up to t^9
+// (|t| <= 0.1716: the first dropped term is below 2e-9 of the result); e ln 2 from the same two-part ln 2 as sample_exp.  Every operation is
+// rounded on its own (a true fp32 division, no FMA contraction), constants in hex: a float32 restatement gives the same bits.
+__device__ __forceinline__ float sample_log(float s) {
+#pragma clang fp contract(off)
+    const uint32_t u = __float_as_uint(s);
+    int e = (int)(u >> 23) - 127;
+    float m = __uint_as_float((u & 0x007fffffu) | 0x3f800000u);   // [1, 2)
+    if (m > 0x1.6a09e6p+0f) { m = m * 0.5f; e += 1; }             // (sqrt 2 / 2, sqrt 2]
+    const float f = m - 1.0f;                                     // exact
+    const float t = f / (2.0f + f);
+    const float t2 = t * t;
+    float p = 0x1.c71c72p-4f;                                     // 1/9, 1/7, 1/5, 1/3
+    p = p * t2 + 0x1.24924ap-3f;
+    p = p * t2 + 0x1.99999ap-3f;
+    p = p * t2 + 0x1.555556p-2f;
+    p = p * t2 + 1.0f;
+    const float lm = (t + t) * p;
+    const float fe = (float)e;
+    return fe * 0x1.62e4p-1f + (fe * 0x1.7f7d1cp-20f + lm);
+}
+
+// ---- the log-probability of one token of a row of masked head logits (trace_decode_set_logprobs / trace_op_token_logprob) ----
+// row = the active head's RAW fp32 logits [0, n) as head_logits_kernel writes them (no temperature, no top-k / top-p: the model's own
+// distribution), off = the token's offset in the row:
+//     logprob = (x[off] - M) - log(S),   M = max x,   S = sum_i exp(x_i - M)
+// S is formed as the sampler forms its sums: weights from sample_exp, thread t of 256 sums its id-order run [t C, (t + 1) C) sequentially,
+// sample_scan runs over the 256 run totals, nothing is contracted into an FMA; log = sample_log (S >= 1: the maximum contributes exp(0)).
+// An offset outside [0, n) gives -inf.  trace_amd/sampling.py token_logprob_ref restates it in float32 numpy bit for bit.
+// One workgroup of SAMPLE_THREADS threads; every thread returns the value.  fbuf: SAMPLE_THREADS floats, wmax: 4 floats (LDS).
+__device__ inline float token_logprob_row(const float* __restrict__ row, int n, int off, float* fbuf, float* wmax) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, wid = tid >> 6;
+    float m = -INFINITY;
+    for (int i = tid; i < n; i += 4 * SAMPLE_THREADS) {              // four loads in flight per thread (one row per workgroup: latency-bound)
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = i + q * SAMPLE_THREADS < n ? row[i + q * SAMPLE_THREADS] : -INFINITY;
+        m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+    }
+    m = wave_max(m);
+    if ((tid & 63) == 0) wmax[wid] = m;
+    __syncthreads();
+    const float M = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    const int C = (n + SAMPLE_THREADS - 1) / SAMPLE_THREADS;
+    const int i0 = min(n, tid * C), i1 = min(n, i0 + C);
+    float s = 0.f;
+    int i = i0;
+    for (; i + 4 <= i1; i += 4) {                                    // the run in id order; the four loads are issued together, the adds stay sequential
+        const float a = row[i], b = row[i + 1], c = row[i + 2], d = row[i + 3];
+        s = s + sample_exp(a - M);
+        s = s + sample_exp(b - M);
+        s = s + sample_exp(c - M);
+        s = s + sample_exp(d - M);
+    }
+    for (; i < i1; ++i) s = s + sample_exp(row[i] - M);
+    sample_scan(s, fbuf);
+    const float S = fbuf[SAMPLE_THREADS - 1];
+    if (off < 0 || off >= n) return -INFINITY;
+    return (row[off] - M) - sample_log(S);
+}
+
 __device__ __forceinline__ void sample_min_result(SampleLds& L, int v) {
     __hip_atomic_fetch_min(&L.result, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }

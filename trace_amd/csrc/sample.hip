@@ -19,11 +19,56 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float
     if (threadIdx.x == 0) out_ids[b] = id;
 }
 
+// The log-probability of one token per row (sample.h token_logprob_row), one workgroup per row, in two forms that share every line of arithmetic:
+//   loose rows (heads != null): row b's token is ids[b], its head heads[b]; out[b].  An id outside the head's range gives -inf.
+//   decode step (heads == null): launched after select_next_kernel, which has recorded this step's token and advanced the counter: the step is
+//     *step - 1, the token out_ids[b][step]; the head it was drawn from is the one whose id range holds it (the three ranges are disjoint).
+//     Only rows select_next recorded a token for in this step (out_len[b] == step + 1) write out[b][step]; rows that finished earlier and
+//     steps at or past max_new leave `out` untouched.
+__global__ __launch_bounds__(SAMPLE_THREADS) void token_logprob_kernel(const float* __restrict__ logits, int ld, const int32_t* __restrict__ heads,
+                                                                       int V, int Tv, int Sv, const int32_t* __restrict__ ids,
+                                                                       float* __restrict__ out, const int32_t* __restrict__ step_ctr,
+                                                                       const int32_t* __restrict__ out_len, const int32_t* __restrict__ params) {
+    __shared__ float fbuf[SAMPLE_THREADS];
+    __shared__ float wmax[4];
+    const int b = blockIdx.x;
+    int id, head;
+    size_t o;
+    if (heads) {
+        id = ids[b];
+        head = heads[b];
+        o = (size_t)b;
+    } else {
+        const int step = step_ctr[0] - 1, max_new = params[0];
+        if (step < 0 || step >= max_new || out_len[b] != step + 1) return;       // (uniform over the workgroup)
+        id = ids[(size_t)b * max_new + step];
+        head = id <= V ? 0 : (id < V + 1 + Tv ? 1 : 2);
+        o = (size_t)b * max_new + step;
+    }
+    const int lo = head == 0 ? 0 : (head == 1 ? V + 1 : V + 1 + Tv);
+    const int hi = head == 0 ? V + 1 : (head == 1 ? V + 1 + Tv : V + 1 + Tv + Sv);
+    const float lp = token_logprob_row(logits + (size_t)b * ld + lo, hi - lo, id >= lo && id < hi ? id - lo : -1, fbuf, wmax);
+    if (threadIdx.x == 0) out[o] = lp;
+}
+
 }  // namespace
 
 int launch_sample_rows(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const SampleParams& sp, const int32_t* steps,
                        int32_t* out_ids, hipStream_t s) {
     if (B < 1 || B > 65535 || ld < V + 1 + Tv + Sv || V < 1 || Tv < 1 || Sv < 1) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, logits, ld, heads, V, Tv, Sv, sp, steps, out_ids);
+    return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
+}
+
+int launch_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out, hipStream_t s) {
+    if (B < 1 || B > 65535 || ld < V + 1 + Tv + Sv || V < 1 || Tv < 1 || Sv < 1 || !heads) return TRACE_ERR_ARG;
+    hipLaunchKernelGGL(token_logprob_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, logits, ld, heads, V, Tv, Sv, ids, out, nullptr, nullptr, nullptr);
+    return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
+}
+
+int launch_step_logprob(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, float* out_logprobs, hipStream_t s) {
+    if (B < 1 || B > SK_ROWS || !logits || !out_logprobs) return TRACE_ERR_ARG;
+    hipLaunchKernelGGL(token_logprob_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, logits, V + 1 + Tv + Sv, nullptr, V, Tv, Sv, st.out_ids, out_logprobs,
+                       st.step, st.out_len, st.params);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

@@ -10,6 +10,7 @@ from __future__ import annotations
 import os
 from typing import List, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -62,6 +63,51 @@ def gather_outputs(local_ids: Sequence[Sequence[int]], max_new: int, per_rank: i
     dist.all_gather_into_tensor(out, packed) if hasattr(dist, "all_gather_into_tensor") and device.type == "cuda" else \
         dist.all_gather(list(out.unbind(0)), packed)
     return [unpack_ids(out[r]) for r in range(out.shape[0])]
+
+
+def pack_ids_logprobs(ids: Sequence[Sequence[int]], logprobs: Sequence[Sequence[float]], max_new: int) -> torch.Tensor:
+    """[n, 1 + 2 max_new] int32: length, ids (zero padded), then the float32 bits of the per-token log-probabilities bit-cast to int32
+    (zero padded) — one tensor, so the job still does one all-gather; -inf, -0.0 and denormals travel exactly."""
+    out = torch.zeros((len(ids), 1 + 2 * max_new), dtype=torch.int32)
+    for i, (row, lp) in enumerate(zip(ids, logprobs)):
+        row = list(row)[:max_new]
+        n = len(row)
+        bits = np.ascontiguousarray(np.asarray(lp, dtype=np.float32)[:n]).view(np.int32)
+        if len(bits) != n:
+            raise ValueError(f"row {i}: {n} ids but {len(bits)} log-probabilities")
+        out[i, 0] = n
+        out[i, 1:1 + n] = torch.tensor(row, dtype=torch.int32)
+        out[i, 1 + max_new:1 + max_new + n] = torch.from_numpy(bits.copy())
+    return out
+
+
+def unpack_ids_logprobs(packed: torch.Tensor) -> Tuple[List[List[int]], List[np.ndarray]]:
+    """inverse of pack_ids_logprobs: (id lists, float32 arrays of the same lengths)"""
+    packed = packed.cpu()
+    max_new = (packed.shape[1] - 1) // 2
+    ids, lps = [], []
+    for row in packed:
+        n = int(row[0])
+        ids.append(row[1:1 + n].tolist())
+        lps.append(row[1 + max_new:1 + max_new + n].contiguous().numpy().view(np.float32).copy())
+    return ids, lps
+
+
+def gather_outputs_logprobs(local_ids: Sequence[Sequence[int]], local_logprobs: Sequence[Sequence[float]], max_new: int, per_rank: int, device=None):
+    """gather_outputs with the log-probabilities riding in the same packed tensor (ONE all-gather): ([world][per_rank] id lists,
+    [world][per_rank] float32 arrays); ranks with fewer videos pad with empties."""
+    pad = per_rank - len(local_ids)
+    packed = pack_ids_logprobs(list(local_ids) + [[]] * pad, list(local_logprobs) + [[]] * pad, max_new)
+    if not (dist.is_available() and dist.is_initialized()):
+        return tuple([x] for x in unpack_ids_logprobs(packed))
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    packed = packed.to(device)
+    out = torch.empty((dist.get_world_size(),) + tuple(packed.shape), dtype=torch.int32, device=device)
+    dist.all_gather_into_tensor(out, packed) if hasattr(dist, "all_gather_into_tensor") and device.type == "cuda" else \
+        dist.all_gather(list(out.unbind(0)), packed)
+    parts = [unpack_ids_logprobs(out[r]) for r in range(out.shape[0])]
+    return [p[0] for p in parts], [p[1] for p in parts]
 
 
 def merge_round_robin(gathered: List[List[List[int]]], n_items: int) -> List[List[int]]:

@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Iterable, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -422,6 +423,27 @@ class TraceEngine:
         out = [[ids[b * mn + i] for i in range(ln[b])] for b in range(B)]
         return out, list(hd)
 
+    def set_logprobs(self, on: bool):
+        """Per-token log-probabilities for the decode batches begun from now on (trace_decode_set_logprobs): the device computes, inside every
+        decode step, log softmax of the RAW masked logits of the row's active head at the emitted id (sampling.token_logprob_ref, bit for bit)."""
+        _lib.check(self.lib.trace_decode_set_logprobs(self.h, 1 if on else 0))
+
+    def decode_read_logprobs(self, lengths: Optional[Sequence[int]] = None):
+        """float32 [B, max_new] of the current batch (0.0 past a row's length); with `lengths`: one array per row, cut to that row's length"""
+        B, mn = self._B, self._max_new
+        out = np.zeros((B, mn), np.float32)
+        _lib.check(self.lib.trace_decode_read_logprobs(self.h, out.ctypes.data_as(C.c_void_p), _stream()))
+        if lengths is None:
+            return out
+        return [out[b, : int(n)].copy() for b, n in enumerate(lengths)]
+
+    def token_logprob(self, logits: torch.Tensor, heads: Sequence[int], ids: Sequence[int]) -> np.ndarray:
+        """float32 [B]: the log-probability of ids[b] under row b of masked logits [B, NV] fp32 (device) and head heads[b] (trace_op_token_logprob:
+        the device code of the decode step) - the host-driven paths call it on the logits they bring back."""
+        cfg = self.cfg
+        out = ops.token_logprob(logits, heads, ids, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size, element=_lib.element_of(self.dtype))
+        return out.cpu().numpy()
+
     def host_mode(self, on: bool):
         """Host-driven token selection (sampling / stopping criteria): logits come back every step, ids go in via feed()."""
         _lib.check(self.lib.trace_decode_host_mode(self.h, 1 if on else 0))
@@ -548,40 +570,54 @@ class TraceEngine:
         flush()
 
     def decode(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
-               forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None):
+               forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False):
         """Stage 2 of generate(): the decode loop over prefilled KV slots, on the current stream -> (ids per sequence, final heads).
         sampling: None / temperature <= 0 = greedy; otherwise every id is drawn on the device (trace_decode_set_sampling: same graphs, same
-        stepping), or — parameters outside the device sampler's domain — one eager step at a time with the host statement of the same rules."""
-        if sampling is not None and not sampling.greedy:
-            if not sampling.on_device:
-                return self._decode_host_sampled(slots, heads, max_new_tokens, eos, forced, sampling)
+        stepping), or — parameters outside the device sampler's domain — one eager step at a time with the host statement of the same rules.
+        logprobs: the result gains a third element, one float32 array per row as long as that row's ids: the log-probability of every emitted
+        token under the model's own (unwarped) distribution, computed inside the decode step (trace_decode_set_logprobs)."""
+        if sampling is not None and not sampling.greedy and not sampling.on_device:
+            return self._decode_host_sampled(slots, heads, max_new_tokens, eos, forced, sampling, logprobs)
+        on_dev = sampling is not None and not sampling.greedy
+        if on_dev:
             self.set_sampling(sampling)
-            try:
-                return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced)
-            finally:
+        if logprobs:
+            self.set_logprobs(True)
+        try:
+            return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs)
+        finally:
+            if logprobs:
+                self.set_logprobs(False)
+            if on_dev:
                 self.set_sampling(None)
-        return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced)
 
-    def _decode_host_sampled(self, slots, heads, max_new_tokens, eos, forced, sampling: SamplingParams):
+    def _decode_host_sampled(self, slots, heads, max_new_tokens, eos, forced, sampling: SamplingParams, logprobs: bool = False):
         B = len(slots)
         self.host_mode(True)
         try:
             lg = self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, want_logits=True)
             cur = list(heads)
+            lp = np.zeros((B, max_new_tokens), np.float32)
             for step in range(max_new_tokens):
                 tok = self.sample(lg, cur, sampling, [step] * B)
                 if forced is not None:
                     tok = [f[step] if step < len(f) and f[step] >= 0 else t for t, f in zip(tok, forced)]
+                val = self.token_logprob(lg, cur, tok) if logprobs else None       # host-select mode: the fed token, under the head it was drawn from
                 self.feed(tok)
                 ids, cur = self.decode_read()
+                if logprobs:
+                    for b in range(B):
+                        if len(ids[b]) == step + 1:
+                            lp[b, step] = val[b]
                 if step == max_new_tokens - 1 or (eos >= 0 and all(len(x) and x[-1] == eos for x in ids)):
                     break
                 lg = self.decode_steps(1, use_graph=False, want_logits=True)
-            return self.decode_read()
+            ids, hd = self.decode_read()
+            return (ids, hd, [lp[b, : len(x)].copy() for b, x in enumerate(ids)]) if logprobs else (ids, hd)
         finally:
             self.host_mode(False)
 
-    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced):
+    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False):
         self.decode_begin(list(slots), heads, max_new_tokens, eos, forced)
         if max_new_tokens > 1:
             if eos < 0:
@@ -595,20 +631,38 @@ class TraceEngine:
                     ids, _ = self.decode_read()
                     if all(len(x) and x[-1] == eos for x in ids):
                         break
-        return self.decode_read()
+        ids, hd = self.decode_read()
+        return (ids, hd, self.decode_read_logprobs([len(x) for x in ids])) if logprobs else (ids, hd)
 
     def generate(self, videos: Sequence[torch.Tensor], timestamps: Sequence, input_ids: Sequence[Sequence[int]],
                  heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
-                 forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None):
+                 forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False):
         B = len(videos)
         if B > self.decode_batch_max:
             raise ValueError(f"batch {B} exceeds the engine's decode batch {self.decode_batch_max}")
         self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
-        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling)
+        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs)
+
+    def generate_samples(self, video: torch.Tensor, timestamps, prompt_ids: Sequence[int], head: int, n: int, max_new_tokens: int, eos: int = -1,
+                         sampling: Optional[SamplingParams] = None, use_graph: bool = True):
+        """n sampled continuations of ONE prompt from one tower pass and one prefill: the prompt is encoded and prefilled into KV slot 0, its rows
+        are copied to slots 1 .. n - 1 (kv_copy), and slots 0 .. n - 1 decode as one batch with log-probabilities on.  Row r draws with Philox
+        row index r, as any decode batch does, so the result equals generate() of the prompt repeated n times with the same SamplingParams:
+        (ids, heads, logprobs), rows in decode order."""
+        if n < 1 or n > min(self.max_batch, self.decode_batch_max):
+            raise ValueError(f"n = {n} must lie in [1, {min(self.max_batch, self.decode_batch_max)}] (the engine's KV slots / decode batch)")
+        if sampling is None or sampling.greedy:
+            raise ValueError("generate_samples needs sampling parameters with temperature > 0: greedy rows would all be identical")
+        self.encode_video(video, timestamps)
+        L = self.splice(list(prompt_ids))
+        self.prefill(0, L)
+        if n > 1:
+            self.kv_copy(0, list(range(1, n)), L)
+        return self.decode(range(n), [int(head)] * n, max_new_tokens, eos, use_graph, None, sampling, logprobs=True)
 
     def generate_questions(self, video: torch.Tensor, timestamps, prompts: Sequence[Sequence[int]], heads: Sequence[int], max_new_tokens: int,
                            eos: int = -1, sampling: Optional[SamplingParams] = None, use_graph: bool = True,
-                           forced: Optional[Sequence[Sequence[int]]] = None, prefix_key=None):
+                           forced: Optional[Sequence[Sequence[int]]] = None, prefix_key=None, logprobs: bool = False):
         """generate() for Q prompts about ONE video whose ids agree up to and including the <video> placeholder (the reference's per-question
         loops, trace/eval/videomme/evaluate.py:349-386): the tower, the slot pool and the prefill of the common prefix run once (slot 0), the
         prefix's KV rows are copied to the other Q - 1 slots, each prompt's rows after <video> are appended (one pass per group of equal
@@ -639,7 +693,7 @@ class TraceEngine:
                     slot += 1
         if prefix_key is not None:
             self.set_prefix_entry(prefix_key, P)
-        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling)
+        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs)
 
     # ---- two-stage pipeline over a stream of batches ---------------------------------------------------
     def make_streams(self, decode_cus: int = 0):
@@ -660,7 +714,7 @@ class TraceEngine:
         return enc, dec
 
     def generate_stream(self, batches: Iterable, max_new_tokens: int, eos: int = -1, use_graph: bool = True, streams=None,
-                        sampling: Optional[SamplingParams] = None):
+                        sampling: Optional[SamplingParams] = None, logprobs: bool = False):
         """generate() over a stream of batches as a two-stage pipeline: while batch k decodes (HBM-bound) on one stream, batch k+1
         runs its ViT + slot pool + prefill (MFMA-bound) on another, into the other half of the KV slots.  `batches` yields
         (videos, timestamps, input_ids, heads, forced-or-None); yields generate()'s result per batch, in order.  Every batch holds at
@@ -682,7 +736,8 @@ class TraceEngine:
             torch.cuda.set_device(self.device)
             with torch.cuda.stream(dec_s):
                 dec_s.wait_event(ready)
-                return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced, sampling)
+                # (logprobs: read inside this job, right after the ids — decode() returns them, nothing goes through engine state afterwards)
+                return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs)
 
         pending = None                                  # (bank, heads, forced, B, ready event): prefilled, waiting for its decode
         bank = 0
@@ -746,6 +801,20 @@ class ops:
         out = torch.empty(B, dtype=torch.int32, device=dev)
         _lib.check(lib.trace_op_sample(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, float(sampling.temperature), int(sampling.top_k),
                                        float(sampling.top_p), int(sampling.seed), _ptr(st), _ptr(out), _stream()))
+        return out
+
+    @staticmethod
+    def token_logprob(logits, heads, ids, V: int, Tv: int, Sv: int, element=None):
+        """trace_op_token_logprob: logits [B, ld >= V+1+Tv+Sv] fp32 (device) -> fp32 [B] (device): log softmax of row b over head heads[b]'s id
+        range at ids[b] (-inf outside the range), sampling.token_logprob_ref bit for bit.  heads / ids: sequences of ints or int32 device tensors."""
+        lib = _lib.load(element or ops.element)
+        lg = logits.contiguous()
+        B, ld = lg.shape
+        dev = lg.device
+        hd = heads if isinstance(heads, torch.Tensor) else torch.tensor([int(h) for h in heads], dtype=torch.int32, device=dev)
+        ii = ids if isinstance(ids, torch.Tensor) else torch.tensor([int(x) for x in ids], dtype=torch.int32, device=dev)
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+        _lib.check(lib.trace_op_token_logprob(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, _ptr(ii), _ptr(out), _stream()))
         return out
 
     @staticmethod

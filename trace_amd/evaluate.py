@@ -92,11 +92,12 @@ def parse_output_ids(ids: Sequence[int], tokenizer, model, stop_str: Optional[st
 @torch.no_grad()
 def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: str, *, num_frames: Optional[int] = None,
                     max_new_tokens: int = 512, batch_size: Optional[int] = None, conv_mode: str = "llama_2",
-                    device_preprocess: bool = True, pipeline: bool = True, sampling=None) -> List[dict]:
+                    device_preprocess: bool = True, pipeline: bool = True, sampling=None, logprobs: bool = False) -> List[dict]:
     """items: dicts with "video" (decoded frames array / list / a reader with get_batch), optional "fps", "id", "query"
     (formatted into `prompt` as the tvg / vhd tasks do, evaluate.py:303-306).  Returns one result dict per item, in order, on
     every rank: {"video", "id", "timestamps", "scores", "captions", "output_ids"}.  sampling: a trace_amd.engine.SamplingParams (None = greedy),
-    the same params and seed for every chunk."""
+    the same params and seed for every chunk.  logprobs: every result gains "output_logprobs", one float per entry of "output_ids" (the
+    device's per-token log-probabilities; their float bits cross the ranks in the same all-gather as the ids)."""
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
     world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
     eng = model.engine
@@ -110,6 +111,7 @@ def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: 
     aspect = getattr(model.config, "image_aspect_ratio", "pad")
     mine = tdist.shard_indices(len(items), rank, world)
     local: List[List[int]] = []
+    local_lp: list = []
     eos = tokenizer.eos_token_id if getattr(tokenizer, "eos_token_id", None) is not None else -1
 
     def chunks():
@@ -125,18 +127,25 @@ def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: 
             yield vids, tss, idl, [1] * len(chunk), None
 
     if pipelined and len(mine) > bs:
-        for out, _ in eng.generate_stream(chunks(), max_new_tokens, eos=eos, sampling=sampling):
+        for out, _, *lp in eng.generate_stream(chunks(), max_new_tokens, eos=eos, sampling=sampling, logprobs=logprobs):
             local.extend(out)
+            local_lp.extend(lp[0] if logprobs else [])
     else:
         for vids, tss, idl, heads, _ in chunks():
-            out, _ = eng.generate(vids, tss, idl, heads, max_new_tokens, eos=eos, sampling=sampling)
+            out, _, *lp = eng.generate(vids, tss, idl, heads, max_new_tokens, eos=eos, sampling=sampling, logprobs=logprobs)
             local.extend(out)
+            local_lp.extend(lp[0] if logprobs else [])
     per_rank = (len(items) + world - 1) // world
+    all_lp = None
     if torch.distributed.is_initialized():
-        gathered = tdist.gather_outputs(local, max_new_tokens, per_rank, eng.device)
+        if logprobs:
+            gathered, gathered_lp = tdist.gather_outputs_logprobs(local, local_lp, max_new_tokens, per_rank, eng.device)
+            all_lp = tdist.merge_round_robin(gathered_lp, len(items))
+        else:
+            gathered = tdist.gather_outputs(local, max_new_tokens, per_rank, eng.device)
         all_ids = tdist.merge_round_robin(gathered, len(items))
     else:
-        all_ids = local
+        all_ids, all_lp = local, (local_lp if logprobs else None)
     stop = stop_string(conv_mode)
     results = []
     for it, ids in zip(items, all_ids):
@@ -145,6 +154,8 @@ def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: 
         except ValueError as e:       # a malformed number string ('.0.1'): the reference's float() raises here too and its driver
             r = {"timestamps": [], "scores": [], "captions": [], "error": str(e)}      # gives the video up (evaluate.py:413-416)
         r.update({"video": it["video"] if isinstance(it["video"], str) else None, "id": it.get("id"), "output_ids": list(ids)})
+        if all_lp is not None:
+            r["output_logprobs"] = [float(v) for v in all_lp[len(results)]]
         results.append(r)
     return results
 
@@ -161,6 +172,7 @@ def main():
     ap.add_argument("--batch-size", type=int, default=128, help="videos decoded together")
     ap.add_argument("--pipeline", dest="pipeline", action="store_true", default=True, help="(default) two-stage pipeline over the chunks: two banks of KV slots, a chunk decodes while the next is encoded")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="chunk by chunk, one bank of KV slots")
+    ap.add_argument("--logprobs", action="store_true", help='add "output_logprobs" (per-token log-probabilities, aligned with "output_ids") to every result')
     args = ap.parse_args()
     from .mm_utils import get_model_name_from_path
     from .model.builder import load_pretrained_model
@@ -170,7 +182,7 @@ def main():
                                                 max_batch=min(512, (2 if args.pipeline else 1) * args.batch_size), max_new_tokens=args.max_new_tokens)
     items = json.load(open(args.items))
     res = evaluate_videos(model, tok, proc, items, args.prompt, num_frames=args.num_frames, max_new_tokens=args.max_new_tokens,
-                          batch_size=args.batch_size, pipeline=args.pipeline)
+                          batch_size=args.batch_size, pipeline=args.pipeline, logprobs=args.logprobs)
     if rank == 0:
         with open(args.out, "w") as f:
             json.dump(res, f)

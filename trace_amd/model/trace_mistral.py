@@ -8,6 +8,7 @@ from __future__ import annotations
 from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from ..config import TraceConfig
@@ -89,7 +90,7 @@ class TraceMistralForCausalLM:
     def prefix_cache_enabled(self) -> bool:
         return self._prefix_cache
 
-    def _generate_prefix_cached(self, raw, vids, modals, timestamps, id_lists, heads, max_new_tokens, eos, sampling):
+    def _generate_prefix_cached(self, raw, vids, modals, timestamps, id_lists, heads, max_new_tokens, eos, sampling, logprobs=False):
         """generate()'s main path with the cache on; None = this call is not of the cacheable shape (today's path runs)."""
         eng, B = self.engine, len(vids)
         try:
@@ -107,7 +108,8 @@ class TraceMistralForCausalLM:
                 return None
         key = (raw[0], raw[0]._version, ts_key, modals[0], tuple(prefix))
         if B > 1:
-            return eng.generate_questions(vids[0], timestamps[0], id_lists, heads, max_new_tokens, eos=eos, sampling=sampling, prefix_key=key)
+            return eng.generate_questions(vids[0], timestamps[0], id_lists, heads, max_new_tokens, eos=eos, sampling=sampling, prefix_key=key,
+                                          logprobs=logprobs)
         ent = eng.prefix_entry()
         hit = ent is not None and ent[0][0] is key[0] and ent[0][1:] == key[1:]
         if hit:
@@ -119,7 +121,7 @@ class TraceMistralForCausalLM:
             eng.set_prefix_entry(key, P)
         eng.embed_rows(suffixes[0])
         eng.prefill_append(0, P, None, L=len(suffixes[0]))
-        return eng.decode([0], heads, max_new_tokens, eos, sampling=sampling)
+        return eng.decode([0], heads, max_new_tokens, eos, sampling=sampling, logprobs=logprobs)
 
     # ---- nn.Module-like conveniences the drivers call ----
     def get_model(self):
@@ -150,11 +152,14 @@ class TraceMistralForCausalLM:
                  modal_list=None, heads=None, max_new_tokens: int = 128, do_sample: Optional[bool] = None,
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None, generation_config=None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, stopping_criteria=None,
-                 use_cache: bool = True, attention_mask=None, position_ids=None, **kwargs):
+                 use_cache: bool = True, attention_mask=None, position_ids=None, output_logprobs: bool = False, **kwargs):
         """do_sample / temperature / top_k / top_p: explicit values, else `generation_config`'s, else this model's defaults (HF's: greedy,
         1.0, 50, 1.0, or the checkpoint's generation_config.json).  Sampling follows HF's warpers (temperature -> top_k -> top_p ->
         multinomial) on the device (trace_amd/csrc/sample.h); the 64-bit seed is drawn from torch's default generator, so torch.manual_seed
-        makes a call reproducible.  temperature == 0 or do_sample=False: greedy."""
+        makes a call reproducible.  temperature == 0 or do_sample=False: greedy.
+        output_logprobs=True: instead of the id tensor, an object with `.sequences` (exactly that tensor), `.logprobs` (float32 [B, n], zero
+        padded: the log-probability of every emitted token under the model's own, unwarped distribution of the row's active head, computed
+        on the device inside the decode step; a row's sum is its score) and `.heads` (the final heads)."""
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")          # trace_mistral.py:282-283
         sampling = self._sampling_params(do_sample, temperature, top_k, top_p, generation_config, kwargs)
@@ -194,8 +199,8 @@ class TraceMistralForCausalLM:
                 eng.vit_forward(vids[b])
                 eng.stc_connector(None, vids[b].shape[0])
                 eng.prefill(b, eng.splice(id_lists[b]))
-            if sampling is not None:
-                out, new_heads = eng.decode(list(range(B)), [0] * B, max_new_tokens, eos, sampling=sampling)
+            if sampling is not None or output_logprobs:
+                out, new_heads, *lps = eng.decode(list(range(B)), [0] * B, max_new_tokens, eos, sampling=sampling, logprobs=output_logprobs)
             else:
                 eng.decode_begin(list(range(B)), [0] * B, max_new_tokens, eos)
                 if max_new_tokens > 1:
@@ -204,11 +209,13 @@ class TraceMistralForCausalLM:
         elif not stopping_criteria:
             res = None
             if self._prefix_cache and all(isinstance(x, torch.Tensor) for x in images_or_videos):
-                res = self._generate_prefix_cached(list(images_or_videos), vids, modals, video_timestamps, id_lists, list(heads), max_new_tokens, eos, sampling)
-            out, new_heads = res if res is not None else eng.generate(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos=eos, sampling=sampling)
+                res = self._generate_prefix_cached(list(images_or_videos), vids, modals, video_timestamps, id_lists, list(heads), max_new_tokens, eos, sampling,
+                                                   output_logprobs)
+            out, new_heads, *lps = res if res is not None else eng.generate(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos=eos,
+                                                                            sampling=sampling, logprobs=output_logprobs)
         else:
-            out, new_heads = self._generate_stepwise(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos,
-                                                     sampling, stopping_criteria, ids)
+            out, new_heads, *lps = self._generate_stepwise(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos,
+                                                           sampling, stopping_criteria, ids, output_logprobs)
         for b in range(B):                       # the reference mutates `heads` in place (trace_mistral.py:342)
             heads[b] = int(new_heads[b])
         pad = eos if pad_token_id is None else pad_token_id
@@ -216,7 +223,58 @@ class TraceMistralForCausalLM:
         res = torch.full((B, n), pad if pad is not None and pad >= 0 else 0, dtype=torch.long)
         for b, row in enumerate(out):
             res[b, : len(row)] = torch.tensor(row, dtype=torch.long)
-        return res.to(self.device)
+        if not output_logprobs:
+            return res.to(self.device)
+        lp = torch.zeros((B, n), dtype=torch.float32)
+        for b, row in enumerate(lps[0]):
+            lp[b, : len(row)] = torch.from_numpy(np.asarray(row, np.float32))
+        return SimpleNamespace(sequences=res.to(self.device), logprobs=lp.to(self.device), heads=[int(h) for h in new_heads])
+
+    @torch.no_grad()
+    def generate_samples(self, inputs=None, images_or_videos=None, video_timestamps=None, n: int = 1, heads=None, max_new_tokens: int = 128,
+                         temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None, generation_config=None,
+                         eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, modal_list=None, best_first: bool = True, **kwargs):
+        """n sampled continuations of ONE prompt, ranked: the tower, the slot pool and the prefill run once (TraceEngine.generate_samples), the n
+        rows decode as one batch with per-token log-probabilities.  Sampling arguments as generate(do_sample=True) (the seed comes from
+        torch's default generator the same way); greedy parameters are a ValueError.  Returns `.sequences` [n, len] (padded as generate()),
+        `.logprobs` float32 [n, len] (zero padded), `.scores` float64 [n] (each row's sum, accumulated in float64 from the float32 entries),
+        `.order` (the decode-row index of each returned row) and `.heads`.  best_first: rows sorted by descending score, ties to the lower
+        decode row; otherwise decode order."""
+        if images_or_videos is None or video_timestamps is None:
+            raise ValueError("generate_samples takes one video with its timestamps")
+        ids = inputs if isinstance(inputs, torch.Tensor) else torch.tensor(inputs)
+        if ids.dim() == 1:
+            ids = ids.unsqueeze(0)
+        if ids.shape[0] != 1 or len(images_or_videos) != 1 or len(video_timestamps) != 1:
+            raise ValueError("generate_samples takes one prompt (B = 1); use generate() for a batch")
+        if not isinstance(n, int) or isinstance(n, bool) or n < 1:
+            raise ValueError(f"n must be a positive integer, got {n!r}")
+        sampling = self._sampling_params(True, temperature, top_k, top_p, generation_config, kwargs)
+        if sampling is None:
+            raise ValueError("generate_samples needs temperature > 0: greedy rows would all be identical")
+        cfg, eng = self.config, self.engine
+        head = 0 if heads is None else int(heads[0])
+        eng.host_mode(False)
+        self._live_kv = None
+        x = images_or_videos[0]
+        if (modal_list or ["video"])[0] == "image":
+            nf = cfg.num_frames if hasattr(cfg, "num_frames") else NUM_FRAMES
+            x = x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
+        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
+        if eos is None:
+            eos = -1
+        out, new_heads, lps = eng.generate_samples(x, video_timestamps[0], ids[0].tolist(), head, n, max_new_tokens, eos=eos, sampling=sampling)
+        scores = np.array([np.sum(np.asarray(r, np.float32), dtype=np.float64) for r in lps], np.float64)
+        order = rank_samples(scores) if best_first else list(range(n))
+        pad = eos if pad_token_id is None else pad_token_id
+        m = max(len(r) for r in out)
+        seq = torch.full((n, m), pad if pad is not None and pad >= 0 else 0, dtype=torch.long)
+        lp = torch.zeros((n, m), dtype=torch.float32)
+        for j, r in enumerate(order):
+            seq[j, : len(out[r])] = torch.tensor(out[r], dtype=torch.long)
+            lp[j, : len(out[r])] = torch.from_numpy(np.asarray(lps[r], np.float32))
+        return SimpleNamespace(sequences=seq.to(self.device), logprobs=lp.to(self.device), scores=torch.from_numpy(scores[order].copy()),
+                               order=[int(r) for r in order], heads=[int(new_heads[r]) for r in order])
 
     # arguments of HF's generate() this build does not implement, with the value that means "off"
     _UNSUPPORTED = {"num_beams": 1, "num_return_sequences": 1, "typical_p": 1.0, "min_p": None, "repetition_penalty": 1.0}
@@ -246,7 +304,7 @@ class TraceMistralForCausalLM:
         g = torch.randint(0, 1 << 32, (2,), dtype=torch.int64)        # torch's default generator: torch.manual_seed(s) reproduces a call
         return SamplingParams(temperature, int(top_k), top_p, (int(g[0]) << 32) | int(g[1]))
 
-    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, prompt_ids):
+    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, prompt_ids, logprobs=False):
         """Stopping-criteria path: one device step at a time with the masked logits brought back; ids from the device sampler
         (trace_op_sample: the same draw a device decode step makes at that step and row) or the arg-max."""
         eng = self.engine
@@ -256,6 +314,7 @@ class TraceMistralForCausalLM:
             eng.prefill(b, eng.splice(id_lists[b]))
         done = [False] * B
         cur_heads = list(heads)
+        lp = np.zeros((B, max_new), np.float32)
         eng.host_mode(True)
         try:
             lg = eng.decode_begin(list(range(B)), heads, max_new, eos=eos, want_logits=True)
@@ -264,9 +323,14 @@ class TraceMistralForCausalLM:
                     tok = eng.sample(lg, cur_heads, sampling, [step] * B)
                 else:
                     tok = torch.argmax(lg, dim=-1).tolist()
+                val = eng.token_logprob(lg, cur_heads, tok) if logprobs else None      # the loose-row op on the logits this path brings back anyway
                 eng.feed(tok)
-                if sampling is not None:
-                    _, cur_heads = eng.decode_read()
+                if sampling is not None or logprobs:
+                    rec, cur_heads = eng.decode_read()
+                if logprobs:
+                    for b in range(B):
+                        if len(rec[b]) == step + 1:
+                            lp[b, step] = val[b]
                 for b in range(B):
                     done[b] = done[b] or (eos >= 0 and tok[b] == eos)
                 if all(done) or step == max_new - 1:
@@ -286,7 +350,8 @@ class TraceMistralForCausalLM:
                     if all(done):
                         break
                 lg = eng.decode_steps(1, use_graph=False, want_logits=True)
-            return eng.decode_read()
+            out, hd = eng.decode_read()
+            return (out, hd, [lp[b, : len(x)].copy() for b, x in enumerate(out)]) if logprobs else (out, hd)
         finally:
             eng.host_mode(False)
 
@@ -368,6 +433,11 @@ class TraceMistralForCausalLM:
         return SimpleNamespace(logits=logits, past_key_values=self._live_kv, loss=None, hidden_states=None, attentions=None)
 
     __call__ = forward
+
+
+def rank_samples(scores) -> List[int]:
+    """decode-row indices by descending score; equal scores keep the lower row first"""
+    return sorted(range(len(scores)), key=lambda r: (-float(scores[r]), r))
 
 
 class _KVHandle:

@@ -3,7 +3,8 @@
 `SamplingParams` is what Engine.decode / generate / generate_stream and evaluate_videos take.  `sample_row_ref` restates the device
 sampler in float32 numpy, operation by operation (the same exp polynomial, the same run sums and Hillis-Steele scan, the same rank
 arithmetic), so it returns the device's id bit for bit; it also serves as the host path for the parameter combinations the device does not
-take (top_k > 1024, or top_k = 0 with top_p < 1), where it applies the same rules.  `philox_uniform` is the RNG contract in numpy."""
+take (top_k > 1024, or top_k = 0 with top_p < 1), where it applies the same rules.  `philox_uniform` is the RNG contract in numpy.
+`token_logprob_ref` restates the per-token log-probability (sample.h token_logprob_row) the same way: the device's float bits."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -186,6 +187,41 @@ def sample_row_ref(row, temperature, top_k, top_p, u, info=None):
     r = (target - Ak) / wt
     jt = 0 if r <= 0 else (mk - 1 if r >= _F(mk - 1) else int(np.floor(r)))
     return int(ties[jt])
+
+
+def _slog(s):
+    """sample.h sample_log: log(s), s >= 1 finite, every operation rounded in float32"""
+    s = np.asarray(s, np.float32)
+    u = s.view(np.uint32)
+    e = (u >> np.uint32(23)).astype(np.int32) - 127
+    m = ((u & np.uint32(0x007FFFFF)) | np.uint32(0x3F800000)).view(np.float32)
+    big = m > _F(float.fromhex("0x1.6a09e6p+0"))
+    m = np.where(big, m * _F(0.5), m).astype(np.float32)
+    e = e + big.astype(np.int32)
+    f = m - _F(1.0)
+    t = f / (_F(2.0) + f)
+    t2 = t * t
+    p = np.full_like(t, _F(float.fromhex("0x1.c71c72p-4")))
+    for c in ("0x1.24924ap-3", "0x1.99999ap-3", "0x1.555556p-2"):
+        p = p * t2 + _F(float.fromhex(c))
+    p = p * t2 + _F(1.0)
+    lm = (t + t) * p
+    fe = e.astype(np.float32)
+    return (fe * _F(float.fromhex("0x1.62e4p-1")) + (fe * _F(float.fromhex("0x1.7f7d1cp-20")) + lm)).astype(np.float32)
+
+
+def token_logprob_ref(row, i):
+    """The device's log-probability of offset i of one head row (float32 [n], the raw masked logits of the head's range), bit for bit:
+    (x[i] - M) - log(S), M = max x, S = sum exp(x - M) in sample.h's order (runs of C = ceil(n / 256) per thread in id order, then the scan
+    over the 256 run totals).  An offset outside [0, n) gives -inf."""
+    x = np.asarray(row, np.float32)
+    n = len(x)
+    M = x.max()
+    with np.errstate(invalid="ignore"):
+        _, S = _run_sums(_sexp(x - M), (n + _THREADS - 1) // _THREADS)
+        if not 0 <= int(i) < n:
+            return _F(-np.inf)
+        return _F((x[int(i)] - M) - _slog(np.array([S], np.float32))[0])
 
 
 def head_bounds(head: int, V: int, Tv: int, Sv: int):
