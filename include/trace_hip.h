@@ -247,7 +247,7 @@ int trace_op_skinny_ks(int N, int K, int epilogue, int B);
    (ks_in may be 0) + R [B,K] -> xout [B,K]; out = fp32 partial rows [trace_op_skinny_ks(N,K,4,B)][sk_rows][N] of RMSNorm(xout; w, eps) . W^T */
 int trace_op_skinny_fused_norm(const float* part_in, int ks_in, const void* R, void* xout, const void* w, float eps, const void* W, float* out,
                                int B, int N, int K, void* stream);
-int trace_op_sk_rows(void);                 /* row stride of every fp32 partial-row buffer = the largest decode batch (128) */
+int trace_op_sk_rows(void);                 /* row stride of every fp32 partial-row buffer = the largest decode batch (256) */
 /* Decode batches above 64 rows: out = X[M <= 128, K] . W[N, K]^T (row-major W) as fp32 k-chunk partial rows
    [trace_op_gemm_partial_ks(N, K)][trace_op_sk_rows()][N] for trace_op_add_rmsnorm (split-K MFMA GEMM, 128x128 tiles) */
 int trace_op_gemm_partial_ks(int N, int K);
@@ -283,8 +283,27 @@ int trace_op_sample(const float* logits, int ld, int B, const int32_t* heads, in
  * int32 [B] device (active head, global vocabulary id), out fp32 [B] device; an id outside the head's range gives -inf. */
 int trace_op_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out,
                            void* stream);
+/* Single-query decode attention over loose caches (head_dim 128, nq == 4 nkv, nkv <= 64, max_ctx % 32 == 0): kcache [B][nkv][max_ctx][128],
+ * vtcache [B][nkv][128][max_ctx] (V transposed), row b in slot b; pos[b] (device) = index of the newest token, already in the caches (ctx = pos + 1);
+ * q [B][nq * 128] ready (rotated) -> O [B][nq * 128]; ws: B * nq * nsplit * 130 floats.  Cache positions past pos[b] inside a 32-position block are
+ * read and must not count: any finite contents are allowed there.  TRACE_ERR_ARG before any launch: B above trace_op_sk_rows(), a shape outside the
+ * above. */
 int trace_op_attn_decode(const void* q, const void* kcache, const void* vtcache, const int32_t* pos, void* O, float* ws,
                          int B, int nq, int nkv, int max_ctx, int nsplit, float scale, void* stream);
+/* The decode step's qkv epilogue as a kernel of its own (the wide step's form): part = the qkv GEMV's fp32 k-chunk partial rows
+ * [ks][trace_op_sk_rows()][(nq + 2 nkv) * 128] (q heads | k heads | v heads), summed in chunk order and rounded to the element type; rotate-half RoPE of
+ * q and the new k from the caller's tables cos_t / sin_t [max_ctx][64] fp32 at row pos[b]; q_out [B][(nq + 2 nkv) * 128] receives the roped q heads in
+ * its first nq * 128 columns (the rest is not written); the K row and the V^T column are stored at position pos[b] of slot slots[b] of
+ * kcache [num_slots][nkv][max_ctx][128] / vtcache [num_slots][nkv][128][max_ctx] — nothing else of the caches is written.  slots / pos: int32 [B] device.
+ * TRACE_ERR_ARG before any launch: B above trace_op_sk_rows(), a slot outside [0, num_slots) or given twice, a position outside [0, max_ctx). */
+int trace_op_qkv_finish(const float* part, int ks, void* q_out, void* kcache, void* vtcache, const int32_t* slots, const int32_t* pos,
+                        const float* cos_t, const float* sin_t, int B, int nq, int nkv, int num_slots, int max_ctx, void* stream);
+/* The same inputs straight into the decode attention's fused prologue (the narrow step's form): sums, RoPE and the cache append as above, then the
+ * attention over positions 0 .. pos[b] of slot slots[b], the new row included -> O [B][nq * 128].  Same sums and roundings as trace_op_qkv_finish
+ * followed by trace_op_attn_decode.  ws and the errors as above. */
+int trace_op_attn_decode_fused(const float* part, int ks, void* kcache, void* vtcache, const int32_t* slots, const int32_t* pos, const float* cos_t,
+                               const float* sin_t, void* O, float* ws, int B, int nq, int nkv, int num_slots, int max_ctx, int nsplit, float scale,
+                               void* stream);
 
 #ifdef __cplusplus
 }

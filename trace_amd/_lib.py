@@ -91,6 +91,8 @@ SIGNATURES = {
     "trace_op_sample": (I, [P, I, I, P, I, I, I, F, I, F, C.c_uint64, P, P, P]),
     "trace_op_token_logprob": (I, [P, I, I, P, I, I, I, P, P, P]),
     "trace_op_attn_decode": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
+    "trace_op_qkv_finish": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "trace_op_attn_decode_fused": (I, [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P]),
 }
 
 NOT_A_STATUS = {"trace_abi_version", "trace_element_type", "trace_op_skinny_ks", "trace_op_sk_rows", "trace_op_gemm_partial_ks"}   # ints that are values

@@ -1838,20 +1838,66 @@ extern "C" int trace_op_add_rmsnorm(const float* part, int KS, const void* R, vo
 }
 // kcache [B, nkv, max_ctx, 128]; vtcache [B, nkv, 128, max_ctx] (V transposed; max_ctx % 32 == 0); pos[b] = index of the
 // newest token (ctx = pos+1), already in the caches; q [B, nq*128] ready (rotated).  ws: B*nq*nsplit*130 floats.
-extern "C" int trace_op_attn_decode(const void* q, const void* kcache, const void* vcache, const int32_t* pos, void* O, float* ws,
-                                    int B, int nq, int nkv, int max_ctx, int nsplit, float scale, void* stream) {
-    static int32_t* d_slots = nullptr;
-    static unsigned int* d_tickets = nullptr;
-    if (!d_slots) {
+// The identity slots and the ticket counters of the decode-attention hooks hold SK_ROWS rows x OP_ATTN_MAX_KV kv heads: a launch is refused unless it fits them.
+constexpr int OP_ATTN_MAX_KV = 64;
+static int32_t* g_op_slots = nullptr;
+static unsigned int* g_op_tickets = nullptr;
+static int op_attn_decode_state(int B, int nq, int nkv, int max_ctx, int nsplit) {
+    if (B < 1 || B > SK_ROWS) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(SK_ROWS) + " rows)");
+    if (nkv < 1 || nkv > OP_ATTN_MAX_KV || nq != 4 * nkv || max_ctx < 32 || max_ctx % 32 || nsplit < 1) return fail(TRACE_ERR_ARG, "bad decode attention shape");
+    if (!g_op_slots) {
         int32_t h[SK_ROWS];
         for (int i = 0; i < SK_ROWS; ++i) h[i] = i;
-        HIPCHK(hipMalloc((void**)&d_slots, SK_ROWS * 4));
-        HIPCHK(hipMemcpy(d_slots, h, SK_ROWS * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc((void**)&d_tickets, SK_ROWS * 64 * 4));
-        HIPCHK(hipMemset(d_tickets, 0, SK_ROWS * 64 * 4));
+        HIPCHK(hipMalloc((void**)&g_op_slots, SK_ROWS * 4));
+        HIPCHK(hipMemcpy(g_op_slots, h, SK_ROWS * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc((void**)&g_op_tickets, SK_ROWS * OP_ATTN_MAX_KV * 4));
+        HIPCHK(hipMemset(g_op_tickets, 0, SK_ROWS * OP_ATTN_MAX_KV * 4));
     }
+    return TRACE_OK;
+}
+// slots[B] / pos[B] (device) as the appending hooks need them: every slot inside the caches, no slot twice, every position inside a slot.  Read back on
+// `s` (the hooks are test entry points: one stream synchronisation per call), so nothing out of range ever reaches a launch.
+static int op_check_slots_pos(const int32_t* slots, const int32_t* pos, int B, int num_slots, int max_ctx, hipStream_t s) {
+    if (!slots || !pos || num_slots < 1) return fail(TRACE_ERR_ARG, "null slots / pos");
+    std::vector<int32_t> hs(B), hp(B);
+    HIPCHK(hipMemcpyAsync(hs.data(), slots, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hp.data(), pos, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<char> seen(num_slots, 0);
+    for (int b = 0; b < B; ++b) {
+        if (hs[b] < 0 || hs[b] >= num_slots) return fail(TRACE_ERR_ARG, "slot out of range");
+        if (seen[hs[b]]) return fail(TRACE_ERR_ARG, "slot given twice");
+        seen[hs[b]] = 1;
+        if (hp[b] < 0 || hp[b] >= max_ctx) return fail(TRACE_ERR_ARG, "position out of range");
+    }
+    return TRACE_OK;
+}
+extern "C" int trace_op_attn_decode(const void* q, const void* kcache, const void* vcache, const int32_t* pos, void* O, float* ws,
+                                    int B, int nq, int nkv, int max_ctx, int nsplit, float scale, void* stream) {
+    TRY(op_attn_decode_state(B, nq, nkv, max_ctx, nsplit));
     LCHK(launch_attn_decode((const bf16_t*)q, nq * 128, (bf16_t*)kcache, (bf16_t*)vcache, (long)nkv * max_ctx * 128,
-                            (long)max_ctx * 128, max_ctx, d_slots, pos, (bf16_t*)O, nq * 128, ws, d_tickets, B, nq, nkv, 128, nsplit, scale, 0,
+                            (long)max_ctx * 128, max_ctx, g_op_slots, pos, (bf16_t*)O, nq * 128, ws, g_op_tickets, B, nq, nkv, 128, nsplit, scale, 0,
                             nullptr, nullptr, nullptr, 0, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_qkv_finish(const float* part, int ks, void* q_out, void* kcache, void* vtcache, const int32_t* slots, const int32_t* pos,
+                                   const float* cos_t, const float* sin_t, int B, int nq, int nkv, int num_slots, int max_ctx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!part || !q_out || !kcache || !vtcache || !cos_t || !sin_t || ks < 1) return fail(TRACE_ERR_ARG, "null argument");
+    TRY(op_attn_decode_state(B, nq, nkv, max_ctx, 1));
+    TRY(op_check_slots_pos(slots, pos, B, num_slots, max_ctx, s));
+    LCHK(launch_qkv_finish(part, ks, (nq + 2 * nkv) * 128, (bf16_t*)q_out, (bf16_t*)kcache, (bf16_t*)vtcache, (long)nkv * max_ctx * 128, (long)max_ctx * 128,
+                           max_ctx, slots, pos, B, nq, nkv, cos_t, sin_t, s));
+    return TRACE_OK;
+}
+extern "C" int trace_op_attn_decode_fused(const float* part, int ks, void* kcache, void* vtcache, const int32_t* slots, const int32_t* pos,
+                                          const float* cos_t, const float* sin_t, void* O, float* ws, int B, int nq, int nkv, int num_slots,
+                                          int max_ctx, int nsplit, float scale, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!part || !kcache || !vtcache || !cos_t || !sin_t || !O || !ws || ks < 1) return fail(TRACE_ERR_ARG, "null argument");
+    TRY(op_attn_decode_state(B, nq, nkv, max_ctx, nsplit));
+    TRY(op_check_slots_pos(slots, pos, B, num_slots, max_ctx, s));
+    LCHK(launch_attn_decode(nullptr, (nq + 2 * nkv) * 128, (bf16_t*)kcache, (bf16_t*)vtcache, (long)nkv * max_ctx * 128, (long)max_ctx * 128, max_ctx,
+                            slots, pos, (bf16_t*)O, nq * 128, ws, g_op_tickets, B, nq, nkv, 128, nsplit, scale, 1, cos_t, sin_t, part, ks, s));
     return TRACE_OK;
 }

@@ -953,6 +953,35 @@ class ops:
                                             max_ctx, nsplit, scale, _stream()))
         return o
 
+    @staticmethod
+    def sk_rows() -> int:
+        return _lib.load(ops.element).trace_op_sk_rows()
+
+    @staticmethod
+    def qkv_finish(part, kcache, vtcache, slots, pos, cos_t, sin_t, nq):
+        """part fp32 [ks, sk_rows, (nq + 2 nkv) * 128] -> roped q rows [B, nq * 128]; the K row and the V^T column of row b are stored IN PLACE at
+        pos[b] of slot slots[b] of kcache [S, nkv, max_ctx, 128] / vtcache [S, nkv, 128, max_ctx].  slots, pos int32 [B] (device); cos_t, sin_t
+        fp32 [max_ctx, 64]."""
+        lib = _lib.load(ops.element)
+        S, nkv, max_ctx = kcache.shape[0], kcache.shape[1], kcache.shape[2]
+        Bn = pos.shape[0]
+        qkv = torch.zeros((Bn, (nq + 2 * nkv) * 128), dtype=ops.dtype(), device=part.device)
+        _lib.check(lib.trace_op_qkv_finish(_ptr(part), part.shape[0], _ptr(qkv), _ptr(kcache), _ptr(vtcache), _ptr(slots), _ptr(pos), _ptr(cos_t),
+                                           _ptr(sin_t), Bn, nq, nkv, S, max_ctx, _stream()))
+        return qkv[:, :nq * 128].contiguous()
+
+    @staticmethod
+    def attn_decode_fused(part, kcache, vtcache, slots, pos, cos_t, sin_t, nq, nsplit, scale):
+        """The decode attention with its fused prologue: qkv_finish's inputs (caches appended IN PLACE) -> attention output [B, nq * 128]."""
+        lib = _lib.load(ops.element)
+        S, nkv, max_ctx = kcache.shape[0], kcache.shape[1], kcache.shape[2]
+        Bn = pos.shape[0]
+        ws = torch.zeros((Bn * nq * nsplit * 130,), dtype=torch.float32, device=part.device)
+        o = torch.empty((Bn, nq * 128), dtype=ops.dtype(), device=part.device)
+        _lib.check(lib.trace_op_attn_decode_fused(_ptr(part), part.shape[0], _ptr(kcache), _ptr(vtcache), _ptr(slots), _ptr(pos), _ptr(cos_t),
+                                                  _ptr(sin_t), _ptr(o), _ptr(ws), Bn, nq, nkv, S, max_ctx, nsplit, scale, _stream()))
+        return o
+
     # ---- fp8 (e4m3) path pieces ----
     @staticmethod
     def quant_rows_fp8(X):
