@@ -227,10 +227,20 @@ int trace_set_profile_brackets(trace_ctx* ctx, int mask);
 /* ---- kernel-level entry points (unit tests / microbenchmarks; raw device pointers) ---- */
 int trace_op_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, const void* bias, const void* R,
                   int ldr, int M, int N, int K, int epilogue, void* stream);
-/* GEMM kernel selection for tests / microbenchmarks (process-wide): 0 auto, 2 = 128^2 tiles, 3 = 256^2 tiles (gemm.hip), 4 = gemm_ldr.hip, 5-7 = gemm_pers.hip
- * (ticketed / static deal / one tile per workgroup), 8 = gemm_w4.hip.  Other ranges are A/B switches of single kernels (engine.hip trace_op_set_gemm_variant:
- * 300 + opt K-loop builds, 500-501 tile walk, 520-521 residual shapes on the persistent kernel, 530-531 gemm_pers / gemm_w4 in auto mode, 540 + opt gemm_w4 builds, 190-192 ViT attention ...). */
+/* The process-wide A/B switches of the kernel launchers, by name ("gemm.kernel", "decode.wide_min_rows", "attn.vit.big", ...: engine.hip TUNE_ROWS holds
+ * every name with its range, default and meaning; trace_op_tuning_name(i) enumerates them, NULL past the end).  set: TRACE_ERR_ARG for an unknown name or a
+ * value outside the field's range; reset: every field back to its default.  For tests and tools: not while launches are in flight. */
+int trace_op_tuning_set(const char* name, int value);
+int trace_op_tuning_get(const char* name, int* value);
+int trace_op_tuning_reset(void);
+const char* trace_op_tuning_name(int i);
+/* The same switches by their older numeric codes: 0-8 = gemm.kernel (0 auto, 2 = 128^2 tiles, 3 = 256^2 tiles (gemm.hip), 4 = gemm_ldr.hip, 5-7 = gemm_pers.hip
+ * ticketed / static deal / one tile per workgroup, 8 = gemm_w4.hip); every other range is a row of engine.hip LEGACY_CODES. */
 int trace_op_set_gemm_variant(int variant);
+/* Which kernel trace_op_gemm runs this shape on under the current tuning values, without launching (no GPU needed): 0 = 128^2 tiles, 1 = 256^2 tiles (gemm.hip),
+ * 2 = gemm_ldr.hip, 3 = gemm_pers.hip, 4 = gemm_w4.hip, | the persistent kernels' tile walk << 8 (0 ticketed, 1 static deal, 2 one workgroup per tile);
+ * TRACE_ERR_ARG for a shape trace_op_gemm rejects. */
+int trace_op_gemm_route(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int epilogue, int fp8);
 /* profiling: device buffer of 8 x uint64 per workgroup receiving phase time stamps of every later GEMM launch (NULL = off) */
 int trace_op_set_gemm_trace(void* buf);
 int trace_op_layernorm(const void* x, void* y, const void* w, const void* b, int rows, int D, float eps, void* stream);

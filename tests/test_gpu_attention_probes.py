@@ -106,11 +106,8 @@ def test_decode_probes_ctx_4096(B):
 
 @pytest.mark.parametrize("B", [8, 128])
 def test_decode_probes_three_wave_build(B):
-    try:
-        ops.set_gemm_variant(761)
+    with ops.tuned(attn__decode__waves=1):
         check_decode(B, 2048, sorted({P.decode_nsplit(B), 16}), kernel="attn_decode(3w)")
-    finally:
-        ops.set_gemm_variant(762)
 
 
 def test_decode_probes_fp16_library():
@@ -383,12 +380,9 @@ def test_vit_probes(n):
     for pn, (q, k, v) in probes.items():
         r = P.reference(q, k, v, vis, scale, True)
         outs = {}
-        try:
-            for var in (190, 191, 192):
-                ops.set_gemm_variant(var)
+        for var in (190, 191, 192):
+            with ops.tuned(attn__vit__big=var - 190):
                 outs[var] = run_attention(q, k, v, False, scale)
-        finally:
-            ops.set_gemm_variant(192)
         for var in (190, 191, 192):
             judge(vit_kernel(n, var), pn, outs[var], r, f"variant {var} n {n} B {B} heads {H}")
         assert torch.equal(outs[191], outs[192]), f"{pn} n {n}: the ring depth changed the arithmetic"

@@ -85,16 +85,13 @@ def test_prefill_last_rows_shortcut_bit_identical_at_full_size(big):
     _, e1 = eng.splice(ids, want_output=True)
     e1 = e1.clone()
     res = {}
-    try:
-        for mode in (0, 1):
-            ops.set_gemm_variant(750 + mode)
+    for mode in (0, 1):
+        with ops.tuned(prefill__last_rows=mode):
             eng.prefill_pair(0, e0, e1)
             lg = [eng.decode_begin([0, 1], [1, 1], eng.n_new, eos=-1, want_logits=True).clone()]
             for _ in range(2):
                 lg.append(eng.decode_steps(1, use_graph=False, want_logits=True).clone())
             res[mode] = torch.stack(lg)
-    finally:
-        ops.set_gemm_variant(751)
     assert torch.equal(res[0], res[1]), f"max |d| {(res[0] - res[1])[torch.isfinite(res[0])].abs().max().item()}"
 
 

@@ -42,9 +42,8 @@ def check(name, got, ref, atol, rtol):
 
 @pytest.fixture(params=[0, 2, 3, 4, 5, 8], ids=["auto", "tile128", "tile256", "ldr", "persistent", "w4"])
 def gemm_variant(request):
-    ops.set_gemm_variant(request.param)
-    yield request.param
-    ops.set_gemm_variant(0)
+    with ops.tuned(gemm__kernel=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (200, 256, 128), (577, 384, 1024), (1, 128, 64), (1000, 1024, 640),
@@ -99,23 +98,20 @@ def test_gemm_persistent_equals_loader_wave_kernel(M, N, K):
     re-arm themselves at the end of every launch)."""
     A, W, b, R = rnd(M, K), rnd(N, K, scale=0.05), rnd(N, scale=0.5), rnd(M, N)
     lib = E._lib.load()
-    try:
-        for epi, kw in ((E.EPI_NONE, dict(bias=b)), (E.EPI_QUICKGELU, dict(bias=b)), (E.EPI_RESIDUAL, dict(bias=b, R=R)), (E.EPI_SWIGLU, {})):
-            ops.set_gemm_variant(4)
+    for epi, kw in ((E.EPI_NONE, dict(bias=b)), (E.EPI_QUICKGELU, dict(bias=b)), (E.EPI_RESIDUAL, dict(bias=b, R=R)), (E.EPI_SWIGLU, {})):
+        with ops.tuned(gemm__kernel=4):
             ref = ops.gemm(A, W, epilogue=epi, **kw)
-            for v in (5, 6):
-                ops.set_gemm_variant(v)
+        for v in (5, 6):
+            with ops.tuned(gemm__kernel=v):
                 for rep in range(3):
                     got = ops.gemm(A, W, epilogue=epi, **kw)
                     assert torch.equal(got, ref), (epi, v, rep, (got.float() - ref.float()).abs().max().item())
-        ops.set_gemm_variant(4)
+    with ops.tuned(gemm__kernel=4):
         ref = ops.gemm(A, W, R=R, epilogue=E.EPI_RESIDUAL)
-        ops.set_gemm_variant(5)
+    with ops.tuned(gemm__kernel=5):
         Rc = R.clone()
         E._lib.check(lib.trace_op_gemm(E._ptr(A), K, E._ptr(W), K, E._ptr(Rc), N, None, E._ptr(Rc), N, M, N, K, E.EPI_RESIDUAL, E._stream()))
         assert torch.equal(Rc, ref)
-    finally:
-        ops.set_gemm_variant(0)
 
 
 @pytest.mark.parametrize("M,N,K", [(300, 256, 192), (9000, 2048, 256), (70000, 1024, 192), (66000, 512, 320), (3934, 6144, 1024)])
@@ -126,61 +122,47 @@ def test_gemm_four_wave_kernel_equals_loader_wave_kernel(M, N, K):
     stream (the two kernels share the stream's ticket counters)."""
     A, W, b, R = rnd(M, K), rnd(N, K, scale=0.05), rnd(N, scale=0.5), rnd(M, N)
     lib = E._lib.load()
-    try:
-        for epi, kw in ((E.EPI_NONE, dict(bias=b)), (E.EPI_NONE, {}), (E.EPI_QUICKGELU, dict(bias=b)), (E.EPI_RESIDUAL, dict(bias=b, R=R)), (E.EPI_SWIGLU, {})):
-            ops.set_gemm_variant(4)
+    for epi, kw in ((E.EPI_NONE, dict(bias=b)), (E.EPI_NONE, {}), (E.EPI_QUICKGELU, dict(bias=b)), (E.EPI_RESIDUAL, dict(bias=b, R=R)), (E.EPI_SWIGLU, {})):
+        with ops.tuned(gemm__kernel=4):
             ref = ops.gemm(A, W, epilogue=epi, **kw)
-            for walk, opt in ((500, 0), (501, 0), (500, 1), (500, 4), (500, 5), (500, 2)):      # (opt 2: the check build whose counted waits are all vmcnt(0))
-                ops.set_gemm_variant(walk)
-                ops.set_gemm_variant(540 + opt)
+        for walk, opt in ((0, 0), (1, 0), (0, 1), (0, 4), (0, 5), (0, 2)):      # (opt 2: the check build whose counted waits are all vmcnt(0))
+            with ops.tuned(gemm__pers__walk=walk, gemm__w4__opt=opt):
                 for rep in range(3):
-                    ops.set_gemm_variant(8)
-                    got = ops.gemm(A, W, epilogue=epi, **kw)
+                    with ops.tuned(gemm__kernel=8):
+                        got = ops.gemm(A, W, epilogue=epi, **kw)
                     assert torch.equal(got, ref), (epi, walk, opt, rep, (got.float() - ref.float()).abs().max().item())
                     if rep == 1:
-                        ops.set_gemm_variant(5)
-                        assert torch.equal(ops.gemm(A, W, epilogue=epi, **kw), ref)
-            ops.set_gemm_variant(500)
-            ops.set_gemm_variant(540)
-        ops.set_gemm_variant(4)
+                        with ops.tuned(gemm__kernel=5):
+                            assert torch.equal(ops.gemm(A, W, epilogue=epi, **kw), ref)
+    with ops.tuned(gemm__kernel=4):
         ref = ops.gemm(A, W, R=R, epilogue=E.EPI_RESIDUAL)
-        ops.set_gemm_variant(8)
+    with ops.tuned(gemm__kernel=8):
         Rc = R.clone()
         E._lib.check(lib.trace_op_gemm(E._ptr(A), K, E._ptr(W), K, E._ptr(Rc), N, None, E._ptr(Rc), N, M, N, K, E.EPI_RESIDUAL, E._stream()))
         assert torch.equal(Rc, ref)
-    finally:
-        ops.set_gemm_variant(500)
-        ops.set_gemm_variant(540)
-        ops.set_gemm_variant(0)
 
 
 def test_gemm_auto_routing_takes_the_four_wave_kernel_and_can_be_switched_back():
-    """auto mode (what the engine runs): shapes without a residual go to gemm_w4.hip, trace_op_set_gemm_variant(530) sends them back to gemm_pers.hip —
+    """auto mode (what the engine runs): shapes without a residual go to gemm_w4.hip, gemm.w4 = 0 sends them back to gemm_pers.hip —
     same bits either way, and equal to the forced kernels"""
     M, N, K = 20000, 1024, 512
     A, W, b = rnd(M, K), rnd(N, K, scale=0.05), rnd(N, scale=0.5)
-    try:
-        ops.set_gemm_variant(4)
+    with ops.tuned(gemm__kernel=4):
         ref = ops.gemm(A, W, bias=b, epilogue=E.EPI_QUICKGELU)
-        ops.set_gemm_variant(0)
-        for sw in (531, 530, 531):
-            ops.set_gemm_variant(sw)
+    for sw in (1, 0, 1):
+        with ops.tuned(gemm__kernel=0, gemm__w4=sw):
             assert torch.equal(ops.gemm(A, W, bias=b, epilogue=E.EPI_QUICKGELU), ref), sw
-    finally:
-        ops.set_gemm_variant(531)
-        ops.set_gemm_variant(0)
 
 
 def test_gemm_persistent_two_streams():
     """Two persistent launches in flight on different streams: each stream has its own ticket counters (both persistent kernels)."""
     M, N, K = 40000, 1024, 256
     A1, W1, A2, W2 = rnd(M, K), rnd(N, K, scale=0.05), rnd(M, K, seed=3), rnd(N, K, scale=0.05, seed=4)
-    try:
-        ops.set_gemm_variant(4)
+    with ops.tuned(gemm__kernel=4):
         r1, r2 = ops.gemm(A1, W1), ops.gemm(A2, W2)
-        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
-        for v in (5, 8):                               # gemm_pers.hip, gemm_w4.hip
-            ops.set_gemm_variant(v)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    for v in (5, 8):                               # gemm_pers.hip, gemm_w4.hip
+        with ops.tuned(gemm__kernel=v):
             torch.cuda.synchronize()
             outs = []
             for _ in range(4):
@@ -192,8 +174,6 @@ def test_gemm_persistent_two_streams():
             torch.cuda.synchronize()
             for o1, o2 in outs:
                 assert torch.equal(o1, r1) and torch.equal(o2, r2), v
-    finally:
-        ops.set_gemm_variant(0)
 
 
 @pytest.mark.parametrize("rows,D", [(5, 128), (577, 1024), (33, 4096), (4618, 1024)])
@@ -228,16 +208,12 @@ def test_attention_vit(Bn, n, heads):
 
 def test_attention_vit_rowmajor_v_equals_transposed_v():
     """Round 3: the LDS-DMA ViT attention reads V row-major (ds_read_b64_tr_b16) instead of a transposed, permuted copy: the same values
-    in the same MFMA k-slots, so the two paths agree bit for bit (trace_op_set_gemm_variant(116) = the transposed-V path)."""
+    in the same MFMA k-slots, so the two paths agree bit for bit (attn.prefill.debug = 6: the transposed-V path)."""
     q, k, v = rnd(3, 577, 16, 64, seed=4), rnd(3, 577, 16, 64, seed=5), rnd(3, 577, 16, 64, seed=6)
-    try:
-        ops.set_gemm_variant(190)                  # the 4 x 32-row kernel (577 tokens go to the 192-row kernel since round 5)
+    with ops.tuned(attn__vit__big=0):              # the 4 x 32-row kernel (577 tokens go to the 192-row kernel since round 5)
         a = ops.attention(q, k, v, False, 0.125)
-        ops.set_gemm_variant(116)
-        b = ops.attention(q, k, v, False, 0.125)
-    finally:
-        ops.set_gemm_variant(110)
-        ops.set_gemm_variant(192)
+        with ops.tuned(attn__prefill__debug=6):
+            b = ops.attention(q, k, v, False, 0.125)
     assert torch.equal(a, b)
     check("attn vit 577 keys", a, _attn_ref(q, k, v, False, 0.125), 2e-2, 2e-2)
 
@@ -250,14 +226,11 @@ def test_attention_vit_192_row_kernel(Bn, n, heads, ring):
     key tail (384) and a key tail (the others), head counts that leave the last quad of (frame, head) pairs partly empty; both ring depths."""
     q, k, v = rnd(Bn, n, heads, 64, seed=11), rnd(Bn, n, heads, 64, seed=12), rnd(Bn, n, heads, 64, seed=13)
     ref = _attn_ref(q, k, v, False, 0.125)
-    try:
-        ops.set_gemm_variant(ring)
+    with ops.tuned(attn__vit__big=ring - 190):
         got = ops.attention(q, k, v, False, 0.125)
         again = ops.attention(q, k, v, False, 0.125)
-        ops.set_gemm_variant(190)
+    with ops.tuned(attn__vit__big=0):
         old = ops.attention(q, k, v, False, 0.125)
-    finally:
-        ops.set_gemm_variant(192)
     assert torch.equal(got, again)
     check("attn vit 192-row", got, ref, 2e-2, 2e-2)
     check("attn vit 192-row vs 32-row kernel", got, old, 2e-2, 2e-2)
@@ -275,12 +248,9 @@ def test_attention_vit_192_row_kernel_moves_its_reference():
         k[:, key] = q[:, row] * gain
     k[:, 0] = q[:, 300] * 3.0                       # row 300: its largest score is the very first key
     outs = {}
-    try:
-        for var in (191, 192, 190):
-            ops.set_gemm_variant(var)
+    for var in (191, 192, 190):
+        with ops.tuned(attn__vit__big=var - 190):
             outs[var] = ops.attention(q, k, v, False, 0.125)
-    finally:
-        ops.set_gemm_variant(192)
     ref = _attn_ref(q, k, v, False, 0.125)
     for var in (191, 192, 190):
         check(f"attn vit spikes, variant {var}", outs[var], ref, 5e-2, 2e-2)

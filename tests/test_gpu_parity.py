@@ -153,9 +153,8 @@ def test_prefill_last_layer_rows_shortcut_is_bit_identical(setup):
     L, emb = eng.splice(E["input_ids"].tolist(), want_output=True)
     embs = [emb.clone(), (emb.float() * 0.5).to(emb.dtype), (emb.float() * -0.25).to(emb.dtype), (emb.float() * 0.75).to(emb.dtype)]
     res = {}
-    try:
-        for mode in (0, 1):
-            ops.set_gemm_variant(750 + mode)
+    for mode in (0, 1):
+        with ops.tuned(prefill__last_rows=mode):
             out = []
             for nb in (1, 2, 4):
                 if nb == 1:
@@ -169,8 +168,6 @@ def test_prefill_last_layer_rows_shortcut_is_bit_identical(setup):
                     lg.append(eng.decode_steps(1, use_graph=False, want_logits=True).clone())
                 out.append(torch.stack(lg))
             res[mode] = out
-    finally:
-        ops.set_gemm_variant(751)
     eng.close()
     for a, b in zip(res[0], res[1]):
         assert torch.isfinite(a[torch.isfinite(b)]).all()
@@ -621,17 +618,14 @@ def test_batch1_swiglu_fold_is_bit_identical(golden_dir):
         forced = M["forced_ids"].tolist()[:20]
         n = len(forced) + 1
         runs = {}
-        try:
-            for fold in (1, 0):
-                ops.set_gemm_variant(180 + fold)
+        for fold in (1, 0):
+            with ops.tuned(decode__fuse_swiglu=fold):
                 eng.encode_video(frames, M["timestamps"].tolist())
                 eng.prefill(0, eng.splice(M["input_ids"].tolist()))
                 lgs = [eng.decode_begin([0], [1], n, eos=-1, forced=[forced], want_logits=True).float().cpu()]
                 for _ in range(n - 1):
                     lgs.append(eng.decode_steps(1, use_graph=False, want_logits=True).float().cpu())
                 runs[fold] = (torch.stack(lgs), eng.decode_read()[0])
-        finally:
-            ops.set_gemm_variant(181)
         assert torch.equal(runs[1][0], runs[0][0]), (runs[1][0] - runs[0][0]).abs().max()
         assert runs[1][1] == runs[0][1]
         eng.close()
@@ -641,7 +635,7 @@ def test_batch1_swiglu_fold_is_bit_identical(golden_dir):
 def test_fused_patch_embed_matches_three_pass_front_end(geometry):
     """Round 4: the ViT front end as one kernel — patches read straight from the frame tensor (no im2col matrix), MFMA GEMM, CLS / position
     embeddings and pre_layrnorm in the epilogue (patch_embed.hip) — against the round-1 path it replaces (im2col -> GEMM -> assemble,
-    trace_op_set_gemm_variant(160)).  Same rounding points, another fp32 summation order: through ONE encoder layer the features agree to a bf16
+    vit.patch_fused = 0).  Same rounding points, another fp32 summation order: through ONE encoder layer the features agree to a bf16
     ulp here and there.  Both frame dtypes the ABI takes (16-bit, fp32), a small call (128-wide tiles) and a 24-frame call (the 256-wide kernels)."""
     import dataclasses
     from trace_amd.engine import ops
@@ -658,14 +652,11 @@ def test_fused_patch_embed_matches_three_pass_front_end(geometry):
     want = ora.vit_forward(frames[:3].float()).reshape(3, cfg.vision_patches, cfg.vision_hidden_size)
     for n in (3, 24):
         got = {}
-        try:
-            for fused in (1, 0):
-                ops.set_gemm_variant(160 + fused)
+        for fused in (1, 0):
+            with ops.tuned(vit__patch_fused=fused):
                 got[fused] = eng.vit_forward(frames[:n]).float().cpu()
                 if fused:
                     got["fp32 frames"] = eng.vit_forward(frames[:n].float()).float().cpu()
-        finally:
-            ops.set_gemm_variant(161)
         assert torch.isfinite(got[1]).all()
         assert torch.equal(got[1], got["fp32 frames"]), n                    # bf16-representable pixels: the fp32 path rounds them back to the same bits
         d = (got[1] - got[0]).abs()

@@ -91,12 +91,9 @@ def test_persistent_gemm_capped_grid_is_bit_identical():
     W = (torch.randn(4096, 1024, device="cuda") * 0.05).to(torch.bfloat16)
     bias = (torch.randn(4096, device="cuda") * 0.1).to(torch.bfloat16)
     ref = ops.gemm(A, W, bias=bias, epilogue=2)
-    try:
-        for cap in (192, 104, 9, 3):
-            ops.set_gemm_variant(1000 + cap)
+    for cap in (192, 104, 9, 3):
+        with ops.tuned(gemm__pers__grid_cap=cap):
             assert torch.equal(ops.gemm(A, W, bias=bias, epilogue=2), ref), cap
-    finally:
-        ops.set_gemm_variant(1000)
 
 
 def test_pipelined_full_size_steps_repeat_exactly_under_overlap():

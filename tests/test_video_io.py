@@ -174,7 +174,8 @@ def test_containers_that_need_a_codec_say_so(tmp_path):
 def test_a_reader_that_fails_while_parsing_leaves_no_descriptor_behind(tmp_path):
     """A stream header cut short makes AviReader raise from inside its parse (struct.error): the map, the view and the file must be closed by then —
     open_container() hands such files to decord, and a long evaluation would otherwise run out of descriptors."""
-    import os, struct
+    import gc, os, struct
+    gc.collect()                     # descriptors that earlier tests' garbage still holds must not close in the middle of the count below
     strh = b"strh" + struct.pack("<I", 56) + b"vids" + b"MJPG" + b"\0" * 8            # 'vids' header whose scale / rate fields lie past the end of the file
     strl = b"LIST" + struct.pack("<I", 4 + len(strh)) + b"strl" + strh
     hdrl = b"LIST" + struct.pack("<I", 4 + len(strl)) + b"hdrl" + strl

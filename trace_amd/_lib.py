@@ -70,6 +70,11 @@ SIGNATURES = {
     "trace_set_profile_brackets": (I, [P, I]),
     "trace_op_gemm": (I, [P, I, P, I, P, I, P, P, I, I, I, I, I, P]),
     "trace_op_set_gemm_variant": (I, [I]),
+    "trace_op_tuning_set": (I, [C.c_char_p, I]),
+    "trace_op_tuning_get": (I, [C.c_char_p, C.POINTER(I)]),
+    "trace_op_tuning_reset": (I, []),
+    "trace_op_tuning_name": (C.c_char_p, [I]),
+    "trace_op_gemm_route": (I, [I, I, I, I, I, I, I, I, I]),
     "trace_op_layernorm": (I, [P, P, P, P, I, I, F, P]),
     "trace_op_rmsnorm": (I, [P, P, P, I, I, F, P]),
     "trace_op_attention": (I, [P, P, P, P, P, I, I, I, I, I, I, I, F, P]),

@@ -1064,27 +1064,25 @@ int launch_attn(const AttnArgs& a, hipStream_t s) {
 }
 }  // namespace
 
-int g_attn_pf_debug = 0;   // microbenchmark-only knock-outs of the prefill-shaped kernels: 1 = no K/V loads after tile 0, 2 = no tile math
-
 // The LDS-DMA kernel takes V^T in transpose_v's permuted layout (v_perm = 1) or V row-major (v_perm = 2, attn_vit_rowmajor_v()) and needs
 // whole key tiles plus at most TAILV trailing keys
-bool attn_vit_rowmajor_v() { return g_attn_pf_debug != 6; }    // trace_op_set_gemm_variant(116): the transposed-V path, for A/B runs
+bool attn_vit_rowmajor_v() { return g_tune.attn_prefill_debug != 6; }    // attn.prefill.debug = 6: the transposed-V path, for A/B runs
 bool attn_vit_wants_perm(int nkv_rows, bool has_vrow) {
     const int rem = nkv_rows % BKV;
-    return (g_attn_pf_debug < 5 || g_attn_pf_debug == 6) && nkv_rows >= 2 * BKV && (rem == 0 || (has_vrow && rem <= TAILV));
+    return (g_tune.attn_prefill_debug < 5 || g_tune.attn_prefill_debug == 6) && nkv_rows >= 2 * BKV && (rem == 0 || (has_vrow && rem <= TAILV));
 }
 
-int g_attn_vit_big = 2;    // the round-5 192-row kernel for shapes it takes (trace_op_set_gemm_variant(190 + x): 0 = the 4 x 32-row kernel, 1 = 4-stage ring (two workgroups
-                           // per CU), 2 = 3-stage ring (three per CU: the default))
+// attn.vit.big: the round-5 192-row kernel for shapes it takes: 0 = the 4 x 32-row kernel, 1 = 4-stage ring (two workgroups per CU), 2 = 3-stage ring (three
+// per CU: the default)
 // v_perm == 2 (row-major V), >= 192 query rows of which 192 leaves at most BIG_MAXLEFT over, whole key tiles + a short tail, keys fit the leftover path's LDS rows
 static bool attn_vit_big_ok(const AttnArgs& a) {
-    return g_attn_vit_big && a.v_perm == 2 && !a.causal && a.nq_rows >= BIG_ROWS && a.nq_rows % BIG_ROWS <= BIG_MAXLEFT && a.nkv_rows >= BKV &&
+    return g_tune.attn_vit_big && a.v_perm == 2 && !a.causal && a.nq_rows >= BIG_ROWS && a.nq_rows % BIG_ROWS <= BIG_MAXLEFT && a.nkv_rows >= BKV &&
            a.nkv_rows % BKV <= TAILV && a.nkv_rows <= BIG_MAXKV && !(a.q_rs % 8) && !(a.q_hs % 8) && !(a.q_bs % 8) && !(a.k_rs % 8) && !(a.k_hs % 8) &&
            !(a.k_bs % 8) && !(a.o_rs % 8) && !(a.o_hs % 8) && !(a.o_bs % 8);
 }
 int launch_attn_vit(const AttnArgs& a_, hipStream_t s) {
     AttnArgs a = a_;
-    a.dbg = g_attn_pf_debug;
+    a.dbg = g_tune.attn_prefill_debug;
     if (a.heads != a.kv_heads || a.nq_rows <= 0 || a.nkv_rows <= 0 || (a.v_rs % 64)) return TRACE_ERR_ARG;
     if (a.v_perm) {
         if (a.causal || !attn_vit_wants_perm(a.nkv_rows, a.Vrow != nullptr)) return TRACE_ERR_ARG;
@@ -1094,7 +1092,7 @@ int launch_attn_vit(const AttnArgs& a_, hipStream_t s) {
             const long nblk = (long)(((long)a.batch * a.kv_heads + 3) / 4) * per;
             if (nblk > 0x7fffffffL) return TRACE_ERR_ARG;
             static LdsGrant grant3, grant4;
-            if (g_attn_vit_big == 2) {
+            if (g_tune.attn_vit_big == 2) {
                 if (!grant_dynamic_lds(grant3, reinterpret_cast<const void*>(attn_vit_big_kernel<3>), 3 * BSTAGE)) return TRACE_ERR_HIP;
                 hipLaunchKernelGGL(attn_vit_big_kernel<3>, dim3((unsigned)nblk), dim3(256), 3 * BSTAGE, s, a);
             } else {

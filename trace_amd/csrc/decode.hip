@@ -1013,7 +1013,6 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
 }
 }  // namespace
 
-int g_skinny_debug = 0;   // microbenchmark-only: 3 = stop before the epilogue, 4 = stop after the partial stores (ticket path)
 // Partition for skinny_lds (see the kernel header): KS k-chunks x row-groups of T tiles, WPT waves per tile.
 struct SkinnyPlan { int KS, chunk_units, T, WPT, ntiles, grid, threads; };
 static int skinny_num_cus() {
@@ -1074,7 +1073,7 @@ static int skinny_lds_launch(const SkinnyPlan& p, const bf16_t* X, int ldx, cons
     static LdsGrantSized grant;
     if (!grant_dynamic_lds(grant, reinterpret_cast<const void*>(skinny_lds_kernel<EPI, NB, NT, PRO>), lds)) return TRACE_ERR_HIP;
     hipLaunchKernelGGL((skinny_lds_kernel<EPI, NB, NT, PRO>), dim3(p.grid), dim3(p.threads), lds, s, X, ldx, W, ldw, out, ldo, R, ldr, B, K,
-                       p.chunk_units, p.KS, p.T, p.WPT, p.ntiles, ws, tickets, tiled, g_skinny_debug, pro);
+                       p.chunk_units, p.KS, p.T, p.WPT, p.ntiles, ws, tickets, tiled, g_tune.skinny_debug, pro);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
 
@@ -1216,28 +1215,20 @@ int launch_qkv_finish(const float* part, int ks, int ldq, bf16_t* qout, bf16_t* 
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
 
-int g_attn_debug = 0;   // microbenchmark-only phase cut-offs (0 = full kernel)
-int g_attn_decode_w3 = -1;  // waves per decode-attention workgroup (A/B: trace_op_set_gemm_variant(760 + x)): 0 / 2 (-1) = 4 (ships), 1 = 3, 3 = 6, 4 = 8
-int g_attn_decode_lds_pad = 0;   // KB of unused dynamic LDS per decode-attention workgroup (A/B: trace_op_set_gemm_variant(780 + KB / 8))
-int g_attn_decode_nt = 0;   // non-temporal cache loads in the decode attention (A/B: trace_op_set_gemm_variant(770 + x))
 int launch_attn_decode(const bf16_t* qkv, int ldq, bf16_t* kcache, bf16_t* vtcache, long slot_stride, long kv_head_stride,
                        int ctx_stride, const int32_t* slots, const int32_t* pos, bf16_t* O, int ldo, float* ws, unsigned int* tickets, int B,
                        int nq, int nkv, int hd, int nsplit, float scale, int fuse_rope, const float* cos_t, const float* sin_t,
                        const float* qpart, int qks, hipStream_t s) {
     if (hd != 128 || nq != 4 * nkv || nsplit < 1 || B < 1 || !tickets || ctx_stride % 32) return TRACE_ERR_ARG;
-    // 3-wave workgroups when the 4-wave form would not be resident in one round (3 x #CUs slots) but the 3-wave form is (4 x #CUs)
-    const long wgs = (long)nsplit * nkv * B;
-    const int ncu = skinny_num_cus();
-    const int nw = g_attn_decode_w3 < 0 ? 4 : g_attn_decode_w3 == 1 ? 3 : g_attn_decode_w3 == 3 ? 6 : g_attn_decode_w3 == 4 ? 8 : 4;
-    (void)wgs; (void)ncu;
-    const size_t pad = (size_t)g_attn_decode_lds_pad * 1024;       // A/B: dynamic LDS nobody uses, caps the workgroups per CU
+    const int w = g_tune.attn_decode_waves, nw = w == 1 ? 3 : w == 3 ? 6 : w == 4 ? 8 : 4;
+    const size_t pad = (size_t)g_tune.attn_decode_lds_pad_kb * 1024;       // A/B: dynamic LDS nobody uses, caps the workgroups per CU
 #define ATTN_DEC(NW_, NT_) do { static LdsGrantSized grant_; if (pad && !grant_dynamic_lds(grant_, reinterpret_cast<const void*>(attn_decode_kernel<NW_, NT_>), pad)) return TRACE_ERR_HIP; \
     hipLaunchKernelGGL((attn_decode_kernel<NW_, NT_>), dim3(nsplit, nkv, B), dim3(NW_ * 64), pad, s, qkv, ldq, kcache, vtcache, slot_stride, \
-                       kv_head_stride, ctx_stride, slots, pos, ws, tickets, O, ldo, nq, nkv, nsplit, scale, fuse_rope, cos_t, sin_t, qpart, qks, g_attn_debug); } while (0)
-    if (nw == 3) { if (g_attn_decode_nt) ATTN_DEC(3, true); else ATTN_DEC(3, false); }
+                       kv_head_stride, ctx_stride, slots, pos, ws, tickets, O, ldo, nq, nkv, nsplit, scale, fuse_rope, cos_t, sin_t, qpart, qks, g_tune.attn_decode_debug); } while (0)
+    if (nw == 3) { if (g_tune.attn_decode_nt) ATTN_DEC(3, true); else ATTN_DEC(3, false); }
     else if (nw == 6) ATTN_DEC(6, false);
     else if (nw == 8) ATTN_DEC(8, false);
-    else { if (g_attn_decode_nt) ATTN_DEC(4, true); else ATTN_DEC(4, false); }
+    else { if (g_tune.attn_decode_nt) ATTN_DEC(4, true); else ATTN_DEC(4, false); }
 #undef ATTN_DEC
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

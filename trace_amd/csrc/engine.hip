@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -163,6 +164,121 @@ static int dalloc(trace_ctx* c, T** p, size_t n_elems) {
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 extern "C" const char* trace_last_error(void) { return g_err.c_str(); }
+
+// ------------------------------------------------------------------------------------------------ tuning table (tuning.h)
+// One row per field of Tuning: its dotted name, the values trace_op_tuning_set accepts, the default, what it does (and the measurements behind it).
+struct TuneRow { const char* name; int Tuning::*field; int lo, hi, dflt; const char* doc; };
+static const TuneRow TUNE_ROWS[] = {
+    {"gemm.kernel", &Tuning::gemm_kernel, 0, 8, 0, "0 = auto routing, 2 = 128^2 tiles, 3 = gemm.hip's 256^2 kernel, 4 = loader-wave kernel, 5 / 6 / 7 = persistent kernel ticketed / static deal / one workgroup per tile, 8 = its 4-wave form"},
+    {"gemm.w4", &Tuning::gemm_w4, 0, 1, 1, "auto routing: non-residual 256^2 shapes on gemm_w4.hip (1) or gemm_pers.hip (0); TRACE_GEMM_W4 sets the initial value"},
+    {"gemm.resid_pers", &Tuning::gemm_resid_pers, 0, 1, 0, "auto routing: 1 = residual shapes run on the persistent kernel too"},
+    {"gemm.pers.walk", &Tuning::gemm_pers_walk, 0, 1, 0, "tile walk of every persistent route: 0 = tickets with atomic re-arm, 1 = static deal"},
+    {"gemm.pers.opt", &Tuning::gemm_pers_opt, 0, 63, 0, "A/B builds of the gemm_pers.hip K loop (2, 4, 8; anything else = the shipped one)"},
+    {"gemm.pers.grid_cap", &Tuning::gemm_pers_grid_cap, 0, 1024, 0, "at most this many workgroups per persistent launch (0 = #CUs); a stream's own cap (trace_set_gemm_cus) comes first"},
+    {"gemm.ldr.opt", &Tuning::gemm_ldr_opt, 0, 3, 0, "gemm_ldr.hip: bit 0 = no residual touches, bit 1 = no A-panel touches"},
+    {"gemm.w4.opt", &Tuning::gemm_w4_opt, 0, 7, 0, "gemm_w4.hip: bit 0 = without the re-aligning barrier, bit 2 = with the L2 touches of the A panel; 2 = the check build (vmcnt(0) waits)"},
+    {"decode.wide_min_rows", &Tuning::decode_wide_min_rows, 17, 65, 32, "smallest batch that takes the wide (GEMM) decode step (65 = only above the GEMV's 64 rows) — ms per step, GEMV path vs wide step (r03_decode_gemm_ab.txt): 32 rows 5.39 / 5.30, 48 rows 7.19 / 6.51, 64 rows 7.88 / 7.11"},
+    {"decode.wide_fuse_qkv", &Tuning::decode_wide_fuse_qkv, 0, 1, 0, "wide decode step: 1 = the attention's fused prologue sums the qkv partial rows, applies RoPE and appends k / v itself (no qkv_finish launch; same sums and roundings, bit-identical)"},
+    {"decode.gemm_tiled", &Tuning::decode_gemm_tiled, 0, 31, 21, "wide decode step, GemmArgs::w_tiled: bit 0 = weights from the decode tile copies (0 = row-major prefill copies), bit 2 = 4-stage K-tile ring, bit 4 = partial rows stored write-through (sc1): the consumer's kernel boundary has no dirty partial bytes to write back (round 6, same bits: 10.41 -> 10.33 ms per 128-sequence step; bit 1 = nt weight DMA +2.7 %, bit 3 = nt partial stores +0.4 %: off)"},
+    {"decode.fuse_norm_rows", &Tuning::decode_fuse_norm_rows, 0, 4, 1, "batches up to this size take decode_step_fused (0 = never).  Measured, ms per step, unfused / fused (profiles/r03_decode_small_ab.txt): batch 1 3.596 / 3.531, batch 2 3.698 / 3.781, batch 4 3.888 / 4.327 — every workgroup redoes the row sums, which only a single row repays"},
+    {"decode.fuse_swiglu", &Tuning::decode_fuse_swiglu, 0, 1, 1, "decode_step_fused: SwiGLU inside the down GEMV (bit-identical to swiglu_combine + GEMV)"},
+    {"decode.unfused_qkv", &Tuning::decode_unfused_qkv, 0, 2, 0, "RoPE + cache append as a kernel of its own before the decode attention: 0 = from batch 32 up (bit-identical to the fused prologue, 1 % faster per 64-sequence step, one launch more — which batch 1 would feel), 1 = always, 2 = never (tools/decode_variant_ab.py --variants 122,121)"},
+    {"decode.partial_cfg", &Tuning::decode_partial_cfg, 0, 3, 0, "tile of the decode partial-row GEMM: 0 = 128 x 128 on 2 x 2 waves, 1 / 2 / 3 = 128 x 64 on 4 x 1 waves with a 5- / 3- / 4-stage ring"},
+    {"decode.partial_wgs", &Tuning::decode_partial_wgs, 0, 1024, 192, "workgroup target of gemm_partial_ks (0 = the initial value); TRACE_PARTIAL_WGS sets the initial value"},
+    {"attn.decode.debug", &Tuning::attn_decode_debug, 0, 9, 0, "microbenchmark-only phase cut-offs of the decode attention (0 = full kernel; 8: V^T read as contiguous blocks, timing only)"},
+    {"attn.decode.waves", &Tuning::attn_decode_waves, -1, 4, -1, "waves per decode-attention workgroup: -1 / 0 / 2 = 4 (ships), 1 = 3, 3 = 6, 4 = 8"},
+    {"attn.decode.nt", &Tuning::attn_decode_nt, 0, 1, 0, "non-temporal cache loads in the decode attention"},
+    {"attn.decode.lds_pad_kb", &Tuning::attn_decode_lds_pad_kb, 0, 152, 0, "KB of unused dynamic LDS per decode-attention workgroup (caps the workgroups per CU)"},
+    {"attn.decode.nsplit", &Tuning::attn_decode_nsplit, 0, 16, 0, "context splits of the decode attention forced to this number (0 = decode_nsplit's rule)"},
+    {"attn.prefill.debug", &Tuning::attn_prefill_debug, 0, 9, 0, "microbenchmark-only knock-outs of the prefill-shaped kernels: 1 = no K/V loads after tile 0, 2 = no tile math, 5 = no LDS-DMA ViT kernel, 6 = its transposed-V path"},
+    {"attn.vit.big", &Tuning::attn_vit_big, 0, 2, 2, "ViT attention: 0 = the 4 x 32-row kernel, 1 = the 192-row kernel with a 4-stage ring, 2 = with a 3-stage ring"},
+    {"skinny.debug", &Tuning::skinny_debug, 0, 9, 0, "microbenchmark-only, decode GEMV: 3 = stop before the epilogue, 4 = stop after the partial stores (ticket path)"},
+    {"prefill.last_rows", &Tuning::prefill_last_rows, 0, 1, 1, "0 = the last decoder layer of a prefill runs over all rows like the others (bit-identical)"},
+    {"vit.patch_fused", &Tuning::vit_patch_fused, 0, 1, 1, "0 = im2col matrix -> GEMM -> assemble instead of the fused ViT front end"},
+};
+const Tuning& tuning_initial() {
+    static const Tuning init = [] {
+        Tuning t{};
+        for (const TuneRow& r : TUNE_ROWS) t.*r.field = r.dflt;
+        if (const char* e = getenv("TRACE_GEMM_W4")) t.gemm_w4 = atoi(e) != 0;
+        if (const char* e = getenv("TRACE_PARTIAL_WGS")) t.decode_partial_wgs = atoi(e);
+        return t;
+    }();
+    return init;
+}
+Tuning g_tune = tuning_initial();
+
+static int tune_row(const char* name, const TuneRow** row) {
+    for (const TuneRow& r : TUNE_ROWS) if (name && !strcmp(name, r.name)) { *row = &r; return TRACE_OK; }
+    return fail(TRACE_ERR_ARG, std::string("unknown tuning value: ") + (name ? name : "(null)"));
+}
+extern "C" int trace_op_tuning_set(const char* name, int value) {
+    const TuneRow* r;
+    TRY(tune_row(name, &r));
+    if (value < r->lo || value > r->hi) return fail(TRACE_ERR_ARG, std::string(r->name) + " must be " + std::to_string(r->lo) + ".." + std::to_string(r->hi));
+    g_tune.*r->field = value;
+    return TRACE_OK;
+}
+extern "C" int trace_op_tuning_get(const char* name, int* value) {
+    const TuneRow* r;
+    if (!value) return fail(TRACE_ERR_ARG, "null pointer");
+    TRY(tune_row(name, &r));
+    *value = g_tune.*r->field;
+    return TRACE_OK;
+}
+extern "C" int trace_op_tuning_reset(void) { g_tune = tuning_initial(); return TRACE_OK; }
+extern "C" const char* trace_op_tuning_name(int i) { return i >= 0 && i < (int)(sizeof(TUNE_ROWS) / sizeof(TUNE_ROWS[0])) ? TUNE_ROWS[i].name : nullptr; }
+
+// The numeric codes of trace_op_set_gemm_variant (bench.py, tools/*, DESIGN.md and the profiles speak in them): code in [lo, hi] stores
+// base + (code - lo) * scale.  The only place these numbers live.
+struct LegacyCode { int lo, hi; int Tuning::*field; int scale, base; };
+static const LegacyCode LEGACY_CODES[] = {
+    {0, 8, &Tuning::gemm_kernel, 1, 0},
+    {100, 109, &Tuning::attn_decode_debug, 1, 0},
+    {110, 119, &Tuning::attn_prefill_debug, 1, 0},
+    {120, 122, &Tuning::decode_unfused_qkv, 1, 0},
+    {130, 137, &Tuning::decode_gemm_tiled, 1, 0},           // the low three bits of the word 700+ sets
+    {140, 140, &Tuning::decode_wide_min_rows, 0, SKINNY_ROWS + 1},
+    {141, 141, &Tuning::decode_wide_min_rows, 0, 33},
+    {142, 142, &Tuning::decode_wide_min_rows, 0, 17},
+    {143, 143, &Tuning::decode_wide_min_rows, 0, 32},
+    {144, 145, &Tuning::decode_wide_fuse_qkv, 1, 0},
+    {160, 161, &Tuning::vit_patch_fused, 1, 0},
+    {170, 174, &Tuning::decode_fuse_norm_rows, 1, 0},
+    {180, 181, &Tuning::decode_fuse_swiglu, 1, 0},
+    {190, 192, &Tuning::attn_vit_big, 1, 0},
+    {200, 209, &Tuning::skinny_debug, 1, 0},
+    {300, 363, &Tuning::gemm_pers_opt, 1, 0},
+    {400, 403, &Tuning::gemm_ldr_opt, 1, 0},
+    {500, 501, &Tuning::gemm_pers_walk, 1, 0},
+    {520, 521, &Tuning::gemm_resid_pers, 1, 0},
+    {530, 531, &Tuning::gemm_w4, 1, 0},
+    {540, 547, &Tuning::gemm_w4_opt, 1, 0},
+    {700, 731, &Tuning::decode_gemm_tiled, 1, 0},
+    {740, 743, &Tuning::decode_partial_cfg, 1, 0},
+    {750, 751, &Tuning::prefill_last_rows, 1, 0},
+    {760, 761, &Tuning::attn_decode_waves, 1, 0},
+    {762, 762, &Tuning::attn_decode_waves, 0, -1},
+    {763, 764, &Tuning::attn_decode_waves, 1, 3},
+    {770, 771, &Tuning::attn_decode_nt, 1, 0},
+    {780, 799, &Tuning::attn_decode_lds_pad_kb, 8, 0},
+    {800, 832, &Tuning::decode_partial_wgs, 32, 0},
+    {850, 866, &Tuning::attn_decode_nsplit, 1, 0},
+    {1000, 2024, &Tuning::gemm_pers_grid_cap, 1, 0},
+};
+extern "C" int trace_op_set_gemm_variant(int variant) {
+    for (const LegacyCode& r : LEGACY_CODES)
+        if (variant >= r.lo && variant <= r.hi) { g_tune.*r.field = r.base + (variant - r.lo) * r.scale; return TRACE_OK; }
+    return fail(TRACE_ERR_ARG, "variant must be 0..8");
+}
+extern "C" int trace_op_gemm_route(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int epilogue, int fp8) {
+    GemmArgs g{};
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr; g.fp8 = fp8;
+    if (!gemm_shape_ok(g, epilogue)) return fail(TRACE_ERR_ARG, "launch_gemm_bf16 does not take this shape");
+    const GemmRoute r = gemm_route(g, epilogue, g_tune);
+    return (int)r.k | r.walk << 8;
+}
+
 extern "C" int trace_abi_version(void) { return TRACE_ABI_VERSION; }
 extern "C" int trace_element_type(void) { return TRACE_ELEMENT_TYPE; }
 
@@ -580,15 +696,17 @@ extern "C" int trace_ctx_finalize(trace_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------------ ViT
-int g_vit_patch_fused = 1;  // 0: im2col matrix -> GEMM -> assemble instead of the fused front end (A/B: trace_op_set_gemm_variant(160 + x))
 static unsigned long long* g_gemm_trace = nullptr;      // tools/gemm_trace.py
 extern "C" int trace_op_set_gemm_trace(void* buf) { g_gemm_trace = (unsigned long long*)buf; return TRACE_OK; }
+static int gemm_checked(const GemmArgs& g, int epi, hipStream_t s, const char* what) {       // launch_gemm_bf16, a failure recorded with its shape
+    const int rc = launch_gemm_bf16(g, epi, s);
+    if (rc != TRACE_OK) return fail(rc, std::string(what) + " launch failed (M=" + std::to_string(g.M) + " N=" + std::to_string(g.N) + " K=" + std::to_string(g.K) + ")");
+    return TRACE_OK;
+}
 static int gemm(const bf16_t* A, int lda, const bf16_t* W, int ldw, bf16_t* C, int ldc, const bf16_t* bias, const bf16_t* R,
                 int ldr, int M, int N, int K, int epi, hipStream_t s) {
     GemmArgs g{A, lda, W, ldw, C, ldc, bias, R, ldr, M, N, K, g_gemm_trace, 0, nullptr, nullptr};
-    const int rc = launch_gemm_bf16(g, epi, s);
-    if (rc != TRACE_OK) return fail(rc, "gemm launch failed (M=" + std::to_string(M) + " N=" + std::to_string(N) + " K=" + std::to_string(K) + ")");
-    return TRACE_OK;
+    return gemm_checked(g, epi, s, "gemm");
 }
 
 // C = (quantise_rows(A) . W8^T) * scales (+ epilogue): A [M,K] bf16 is quantised row-wise into c->pA8 / c->psa first
@@ -596,9 +714,7 @@ static int gemm_fp8(trace_ctx* c, const bf16_t* A, int lda, const uint8_t* W8, c
                     int M, int N, int K, int epi, hipStream_t s) {
     LCHK(launch_quant_rows_fp8(A, lda, c->pA8, K, c->psa, M, K, s));
     GemmArgs g{reinterpret_cast<const bf16_t*>(c->pA8), K, reinterpret_cast<const bf16_t*>(W8), K, C, ldc, nullptr, R, ldr, M, N, K, nullptr, 1, c->psa, sw};
-    const int rc = launch_gemm_bf16(g, epi, s);
-    if (rc != TRACE_OK) return fail(rc, "fp8 gemm launch failed (M=" + std::to_string(M) + " N=" + std::to_string(N) + " K=" + std::to_string(K) + ")");
-    return TRACE_OK;
+    return gemm_checked(g, epi, s, "fp8 gemm");
 }
 
 extern "C" int trace_vit_forward(trace_ctx* c, const void* frames, int frames_dtype, int T, void* feats_out, void* stream) {
@@ -607,9 +723,9 @@ extern "C" int trace_vit_forward(trace_ctx* c, const void* frames, int frames_dt
     hipStream_t s = (hipStream_t)stream;
     const int vh = c->vh, vi = c->vi, NT = c->NT, GG = c->GG, Mv = T * NT;
     // front end: one kernel reads the frame tensor, multiplies the patches on the MFMA, adds CLS / position embeddings and applies
-    // pre_layrnorm (patch_embed.hip).  g_vit_patch_fused = 0 (A/B) or a patch size / width the kernel does not take: the round-1 path,
+    // pre_layrnorm (patch_embed.hip).  vit.patch_fused = 0 (A/B) or a patch size / width the kernel does not take: the round-1 path,
     // im2col matrix -> GEMM -> assemble.
-    const bool fused_pe = g_vit_patch_fused && c->patch_wp;
+    const bool fused_pe = g_tune.vit_patch_fused && c->patch_wp;
     if (fused_pe) {
         LCHK(launch_patch_embed(frames, frames_dtype == 1, c->patch_wp, c->pos_emb, c->pre_w, c->pre_b, c->cls_row, c->vX, T, c->c.v_image, c->P, vh,
                                 c->c.v_eps, s));
@@ -969,7 +1085,6 @@ extern "C" int trace_preprocess_frames(trace_ctx* c, const void* frames_u8, int 
 // nb equal-length sequences laid end to end in pX (rows [b*L, (b+1)*L)) -> slots slot0 .. slot0+nb-1.  Two 1967-row
 // prompts give the GEMMs M = 3934: 16 row tiles fill the 256x256 tile grid in whole rounds (gate|up 1792 tiles = 7.0
 // rounds instead of 896 = 3.5) and o-proj / down-proj reach the 256^2 kernel.
-int g_prefill_last_rows = 1;   // 0: the last decoder layer of a prefill runs over all rows like the others (A/B and the bit-identity test: trace_op_set_gemm_variant(750 + x))
 // past > 0 (trace_llm_prefill_append): every target slot already holds `past` rows; the nb x L new rows take positions past .. past + L - 1
 // (RoPE, cache rows) and attend the cached rows 0 .. past - 1 as well: query row i of a prompt sees keys <= i + past.  Every kernel is the one
 // the past == 0 call runs, every per-row sum in the same order: a row's bits do not depend on where the prompt was cut (tests/test_gpu_prefix_reuse.py).
@@ -993,7 +1108,7 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
         // everything, trace_mistral.py:190-200, and then uses logits[:, -1]) — so: the k | v slice of the qkv projection over all M rows, and q,
         // attention, o-proj and the MLP for the nb last rows, on the same kernels reading / writing those rows in place (row stride L x width).
         // Same MFMA tile kernels, same K order, same epilogues: bit-identical to the full layer (tests/test_gpu_parity.py), ~3 % of a prefill saved.
-        if (g_prefill_last_rows && l == c->NL - 1 && !hidden_out && !c->fp8 && L > 1) {
+        if (g_tune.prefill_last_rows && l == c->NL - 1 && !hidden_out && !c->fp8 && L > 1) {
             const int KV = 2 * c->NKV * HD, QW = c->NQ * HD;
             const size_t last = (size_t)(L - 1);
             TRY(gemm(c->pH, H, W.wqkv + (size_t)QW * H, H, c->pQKV + QW, QKV, nullptr, nullptr, 0, M, KV, H, EPI_NONE, s));
@@ -1171,19 +1286,34 @@ static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* l
 
 // decode attention context split: ~256-320 workgroups (8 kv heads x B x nsplit) fill the CUs; more splits only add
 // partial-result traffic and ticket latency (measured, ctx 2100: B=1 16 splits 10.4 us, B=4 8 -> 13 us, B=16 2 -> 26 us,
-// B=32 1 -> 45 us; B=32 with 16 splits: 79 us)
-int g_attn_decode_nsplit = 0;   // A/B: context splits of the decode attention forced to this number (0 = the rule below; trace_op_set_gemm_variant(850 + n))
-static int decode_nsplit(int B) { if (g_attn_decode_nsplit > 0) return g_attn_decode_nsplit; const int n = (40 + B / 2) / B; return n < 1 ? 1 : n > 16 ? 16 : n; }
+// B=32 1 -> 45 us; B=32 with 16 splits: 79 us).  attn.decode.nsplit > 0 forces the number (A/B).
+static int decode_nsplit(int B) { if (g_tune.attn_decode_nsplit > 0) return g_tune.attn_decode_nsplit; const int n = (40 + B / 2) / B; return n < 1 ? 1 : n > 16 ? 16 : n; }
 
-static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* logits_out, hipStream_t s);
-int g_decode_wide_min = 32;   // smallest batch that takes the wide (GEMM) decode step — ms per step, GEMV path vs wide step (r03_decode_gemm_ab.txt): 32 rows 5.39 / 5.30, 48 rows
-                                 // 7.19 / 6.51, 64 rows 7.88 / 7.11; A/B: trace_op_set_gemm_variant(140 + x): 65 / 33 / 17 / 32
-int g_decode_wide_fuse_qkv = 0; // wide decode step: 1 = the attention's fused prologue sums the qkv partial rows, applies RoPE and appends k / v itself (no qkv_finish launch;
-                               // same sums and roundings, bit-identical; A/B: trace_op_set_gemm_variant(144 + x))
-int g_decode_gemm_tiled = 21;  // wide decode step, GemmArgs::w_tiled: bit 0 = weights from the decode tile copies (0 = row-major prefill copies), bit 2 = 4-stage
-                               // K-tile ring, bit 4 = partial rows stored write-through (sc1): the consumer's kernel boundary has no dirty partial bytes to write back
-                               // (round 6, same bits: 10.41 -> 10.33 ms per 128-sequence step; bit 1 = nt weight DMA +2.7 %, bit 3 = nt partial stores +0.4 %: off)
-                               // (A/B: trace_op_set_gemm_variant(700 + x), 130 + x for the low three bits)
+// Roofline probe (profile == 2): HIP events around ONE launch per step, layer 0's dominant kernel, for the scope this object lives in; `kind` says
+// which launch took the bracket (prof[8]).  Eager launches only: event-record nodes captured into a hipGraph do not yield usable timestamps on ROCm 7.2.
+struct StepBracket {
+    hipEvent_t e1 = nullptr; hipStream_t s;
+    StepBracket(trace_ctx* c, int l, int kind, hipStream_t s_) : s(s_) {
+        if (l != 0 || c->profile != 2 || !(c->bracket_mask & 2) || s == c->cap_stream || c->kev_used + 2 > (int)c->kev.size()) return;
+        hipEventRecord(c->kev[c->kev_used], s);
+        e1 = c->kev[c->kev_used + 1]; c->kev_used += 2; c->bracket_kind = kind;
+    }
+    ~StepBracket() { if (e1) hipEventRecord(e1, s); }
+};
+
+// The decode attention of layer l.  fused: its prologue sums the qkv partial rows part [ks][SK_ROWS][QKV], applies RoPE and appends k / v to the cache;
+// otherwise dQKV holds ready q rows and the cache the new row (qkv_finish_layer ran).
+static int attn_decode_layer(trace_ctx* c, int l, bool fused, const float* part, int ks, hipStream_t s) {
+    return launch_attn_decode(c->dQKV, c->QKV, c->kcache + (size_t)l * c->layer_stride, c->vcache + (size_t)l * c->layer_stride, (long)c->slot_stride,
+                              (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->dO, c->H, c->attn_ws, c->tickets, c->B, c->NQ, c->NKV, c->HD,
+                              decode_nsplit(c->B), 1.0f / sqrtf((float)c->HD), fused ? 1 : 0, fused ? c->rope_cos : nullptr, fused ? c->rope_sin : nullptr,
+                              fused ? part : nullptr, fused ? ks : 0, s);
+}
+// that prologue as a launch of its own: the qkv partial rows in sk_ws -> roped q rows in dQKV, k / v of layer l appended
+static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s) {
+    return launch_qkv_finish(c->sk_ws, ks, c->QKV, c->dQKV, c->kcache + (size_t)l * c->layer_stride, c->vcache + (size_t)l * c->layer_stride,
+                             (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->B, c->NQ, c->NKV, c->rope_cos, c->rope_sin, s);
+}
 
 // One decode step for SKINNY_ROWS < B <= SK_ROWS sequences.  A GEMV that parks its activations in LDS cannot hold more than 64 rows x 1024 k, and
 // its fp32 partial rows would grow with the row count; above 64 rows the four projections are small-M GEMMs on the MFMA tile kernel instead
@@ -1195,42 +1325,27 @@ static int decode_step_wide(trace_ctx* c, float* logits_out, hipStream_t s) {
     const int H = c->H, I = c->I, HD = c->HD, QKV = c->QKV, B = c->B;
     if (c->fp8) return fail(TRACE_ERR_STATE, "the fp8 weight path decodes at most 64 sequences together");
     const int ks_q = gemm_partial_ks(QKV, H), ks_o = gemm_partial_ks(H, H), ks_d = gemm_partial_ks(H, I);
-    const int wt = g_decode_gemm_tiled;      // bit 0: weights from the decode tile copies, bit 1: non-temporal weight loads
+    const int wt = g_tune.decode_gemm_tiled;
+    const bool fq = g_tune.decode_wide_fuse_qkv != 0;
     auto pgemm = [&](const bf16_t* A, int lda, const bf16_t* Wrow, const bf16_t* Wtile, int ldw, int N, int K, int ks) -> int {
         GemmArgs g{A, lda, (wt & 1) ? Wtile : Wrow, ldw, nullptr, 0, nullptr, nullptr, 0, B, N, K, nullptr, 0, nullptr, nullptr, 0, c->sk_ws, ks, (wt & 1) ? wt : 0};
         if ((size_t)ks * SK_ROWS * N > c->sk_ws_floats) return fail(TRACE_ERR_STATE, "partial-row workspace too small");
-        const int rc = launch_gemm_bf16(g, EPI_PARTIAL, s);
-        if (rc != TRACE_OK) return fail(rc, "partial GEMM launch failed (N=" + std::to_string(N) + " K=" + std::to_string(K) + ")");
-        return TRACE_OK;
+        return gemm_checked(g, EPI_PARTIAL, s, "partial GEMM");
     };
     LCHK(launch_rmsnorm(c->dX, H, c->dH, H, c->llm[0].rms1, B, H, c->c.rms_eps, s));
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
-        bf16_t* kc = c->kcache + (size_t)l * c->layer_stride;
-        bf16_t* vc = c->vcache + (size_t)l * c->layer_stride;
         TRY(pgemm(c->dH, H, W.wqkv, W.wqkv_d, H, QKV, H, ks_q));
-        const bool fq = g_decode_wide_fuse_qkv != 0;
-        if (!fq) LCHK(launch_qkv_finish(c->sk_ws, ks_q, QKV, c->dQKV, kc, vc, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots,
-                                        c->d_pos, B, c->NQ, c->NKV, c->rope_cos, c->rope_sin, s));
-        // roofline probe (profile == 2, eager launches): HIP events around ONE launch of the step's dominant kernel — the layer-0 decode
-        // attention, which streams the batch's whole KV cache of that layer
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (l == 0 && c->profile == 2 && (c->bracket_mask & 2) && s != c->cap_stream && c->kev_used + 2 <= (int)c->kev.size()) {
-            e0 = c->kev[c->kev_used]; e1 = c->kev[c->kev_used + 1]; c->kev_used += 2;
-            c->kbytes_sum += (double)(c->pos_sum + (long)B * (c->step_in_call + 1)) * c->NKV * HD * 2 * 2;   // K + V^T rows of every sequence, bf16
-            c->bracket_kind = 3;
+        if (!fq) LCHK(qkv_finish_layer(c, l, ks_q, s));
+        {   // bracketed: the layer-0 decode attention, which streams the batch's whole KV cache of that layer
+            StepBracket br(c, l, 3, s);
+            if (br.e1) c->kbytes_sum += (double)(c->pos_sum + (long)B * (c->step_in_call + 1)) * c->NKV * HD * 2 * 2;   // K + V^T rows of every sequence, bf16
+            LCHK(attn_decode_layer(c, l, fq, c->sk_ws, ks_q, s));
         }
-        if (e0) hipEventRecord(e0, s);
-        LCHK(launch_attn_decode(c->dQKV, QKV, kc, vc, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->dO,
-                                H, c->attn_ws, c->tickets, B, c->NQ, c->NKV, HD, decode_nsplit(B), 1.0f / sqrtf((float)HD), fq ? 1 : 0,
-                                fq ? c->rope_cos : nullptr, fq ? c->rope_sin : nullptr, fq ? c->sk_ws : nullptr, fq ? ks_q : 0, s));
-        if (e1) hipEventRecord(e1, s);
         TRY(pgemm(c->dO, H, W.wo, W.wo_d, H, H, H, ks_o));
         LCHK(launch_add_rmsnorm(c->sk_ws, ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s));
-        if (wt & 1) {
-            GemmArgs g{c->dH, H, W.wgu_d, H, c->dACT, I, nullptr, nullptr, 0, B, 2 * I, H, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, wt};
-            if (launch_gemm_bf16(g, EPI_SWIGLU, s) != TRACE_OK) return fail(TRACE_ERR_HIP, "gate|up GEMM launch failed");
-        } else TRY(gemm(c->dH, H, W.wgu, H, c->dACT, I, nullptr, nullptr, 0, B, 2 * I, H, EPI_SWIGLU, s));
+        GemmArgs gu{c->dH, H, (wt & 1) ? W.wgu_d : W.wgu, H, c->dACT, I, nullptr, nullptr, 0, B, 2 * I, H, (wt & 1) ? nullptr : g_gemm_trace, 0, nullptr, nullptr, 0, nullptr, 0, (wt & 1) ? wt : 0};
+        TRY(gemm_checked(gu, EPI_SWIGLU, s, "gate|up GEMM"));
         TRY(pgemm(c->dACT, I, W.wd, W.wd_d, I, H, I, ks_d));
         const bf16_t* nw = l + 1 < c->NL ? c->llm[l + 1].rms1 : c->final_norm;
         LCHK(launch_add_rmsnorm(c->sk_ws, ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s));
@@ -1238,10 +1353,6 @@ static int decode_step_wide(trace_ctx* c, float* logits_out, hipStream_t s) {
     return head_and_select(c, c->dH, 1, logits_out, s);
 }
 
-int g_decode_fuse_swiglu = 1;      // decode_step_fused: SwiGLU inside the down GEMV (bit-identical to swiglu_combine + GEMV; A/B: trace_op_set_gemm_variant(180 + x))
-int g_decode_fuse_norm_rows = 1;   // batches up to this size take decode_step_fused (0 = never; A/B: trace_op_set_gemm_variant(170 + rows)).  Measured, ms per step,
-                                   // unfused / fused (profiles/r03_decode_small_ab.txt): batch 1 3.596 / 3.531, batch 2 3.698 / 3.781, batch 4 3.888 / 4.327 — every
-                                   // workgroup redoes the row sums, which only a single row repays
 // One decode step for 1..4 sequences (the reference drivers' own call shape is 1): the two "sum the partial rows + residual -> new residual, RMSNorm"
 // kernels of a layer are folded into the GEMVs that consume their output (decode.hip, SkinnyPro), and (round 4) the SwiGLU combine into the down
 // GEMV — 4 launches per layer instead of 7:
@@ -1250,31 +1361,23 @@ int g_decode_fuse_norm_rows = 1;   // batches up to this size take decode_step_f
 // Partial rows alternate between sk_ws (written by o / down, read by the fused GEMVs) and sk_ws2 (written by the fused GEMVs, read by the attention /
 // the combine); the residual rows alternate between dX and dX2 (a fused GEMV reads one and writes the other: its workgroups all read the whole row).
 static int decode_step_fused(trace_ctx* c, float* logits_out, hipStream_t s) {
-    const int H = c->H, I = c->I, HD = c->HD, QKV = c->QKV, B = c->B;
+    const int H = c->H, I = c->I, QKV = c->QKV, B = c->B;
     const int ks_q = skinny_ks(QKV, H, EPI_PARTIAL, B), ks_o = skinny_ks(H, H, EPI_PARTIAL, B);
     const int ks_g = skinny_ks(2 * I, H, EPI_PARTIAL, B), ks_d = skinny_ks(H, I, EPI_PARTIAL, B);
     bf16_t *xa = c->dX, *xb = c->dX2;             // current / next residual rows
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
-        bf16_t* kc = c->kcache + (size_t)l * c->layer_stride;
-        bf16_t* vc = c->vcache + (size_t)l * c->layer_stride;
         LCHK(launch_skinny_gemm_fused_norm(l ? c->sk_ws : nullptr, l ? ks_d : 0, xa, H, xb, H, W.rms1, c->c.rms_eps, W.wqkv_d, B, QKV, H, c->sk_ws2,
                                            c->sk_ws_floats, s));
         std::swap(xa, xb);
-        LCHK(launch_attn_decode(c->dQKV, QKV, kc, vc, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->dO,
-                                H, c->attn_ws, c->tickets, B, c->NQ, c->NKV, HD, decode_nsplit(B), 1.0f / sqrtf((float)HD), 1,
-                                c->rope_cos, c->rope_sin, c->sk_ws2, ks_q, s));
+        LCHK(attn_decode_layer(c, l, true, c->sk_ws2, ks_q, s));
         LCHK(launch_skinny_gemm(c->dO, H, W.wo_d, H, nullptr, H, nullptr, 0, B, H, H, EPI_PARTIAL, 1, SKWS(c), s));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (l == 0 && c->profile == 2 && (c->bracket_mask & 2) && s != c->cap_stream && c->kev_used + 2 <= (int)c->kev.size()) {
-            e0 = c->kev[c->kev_used]; e1 = c->kev[c->kev_used + 1]; c->kev_used += 2;
-            c->bracket_kind = 2;
+        {
+            StepBracket br(c, l, 2, s);
+            LCHK(launch_skinny_gemm_fused_norm(c->sk_ws, ks_o, xa, H, xb, H, W.rms2, c->c.rms_eps, W.wgu_d, B, 2 * I, H, c->sk_ws2, c->sk_ws_floats, s));
         }
-        if (e0) hipEventRecord(e0, s);
-        LCHK(launch_skinny_gemm_fused_norm(c->sk_ws, ks_o, xa, H, xb, H, W.rms2, c->c.rms_eps, W.wgu_d, B, 2 * I, H, c->sk_ws2, c->sk_ws_floats, s));
-        if (e1) hipEventRecord(e1, s);
         std::swap(xa, xb);
-        if (g_decode_fuse_swiglu) {        // SwiGLU folded into the down GEMV's parking step (round 4): 4 launches per layer
+        if (g_tune.decode_fuse_swiglu) {        // SwiGLU folded into the down GEMV's parking step (round 4, bit-identical to swiglu_combine + GEMV): 4 launches per layer
             LCHK(launch_skinny_gemm_fused_swiglu(c->sk_ws2, ks_g, W.wd_d, B, H, I, c->sk_ws, c->sk_ws_floats, s));
         } else {
             LCHK(launch_swiglu_combine(c->sk_ws2, ks_g, 2 * I, c->dACT, I, B, s));
@@ -1286,77 +1389,52 @@ static int decode_step_fused(trace_ctx* c, float* logits_out, hipStream_t s) {
     return head_and_select(c, c->dH, 1, logits_out, s);
 }
 
-int g_decode_unfused = 0;   // RoPE + cache append as a kernel of its own before the decode attention: 0 = from batch 32 up (bit-identical to the fused
-                            // prologue, 1 % faster per 64-sequence step, one launch more — which batch 1 would feel), 1 = always, 2 = never
-                            // (trace_op_set_gemm_variant(120 + x), tools/decode_variant_ab.py --variants 122,121)
 // one decode step for the current batch: consumes dX (embedding of the last token), leaves the next one in dX
 static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
-    const int H = c->H, I = c->I, HD = c->HD, QKV = c->QKV, B = c->B;
+    const int H = c->H, I = c->I, QKV = c->QKV, B = c->B;
+    if (B > SKINNY_ROWS || (B >= g_tune.decode_wide_min_rows && !c->fp8)) return decode_step_wide(c, logits_out, s);      // (fp8 contexts: at most 64 rows, checked at begin)
+    if (B <= g_tune.decode_fuse_norm_rows && !c->fp8 && skinny_fused_norm_ok(QKV, H, B) && skinny_fused_norm_ok(2 * I, H, B)) return decode_step_fused(c, logits_out, s);
     // Every GEMV leaves fp32 k-chunk partial rows in sk_ws and its consumer sums them on load (an in-kernel merge costs
     // 5-8 us of dependent round trips per GEMV): qkv -> attention (RoPE + cache append + attention) -> o -> [sum + residual
     // -> new residual, RMSNorm] -> gate|up -> [sum, SwiGLU] -> down -> [sum + residual, next layer's / the final RMSNorm].
-    if (B > SKINNY_ROWS || (B >= g_decode_wide_min && !c->fp8)) return decode_step_wide(c, logits_out, s);      // (fp8 contexts: at most 64 rows, checked at begin)
-    if (B <= g_decode_fuse_norm_rows && !c->fp8 && skinny_fused_norm_ok(QKV, H, B) && skinny_fused_norm_ok(2 * I, H, B)) return decode_step_fused(c, logits_out, s);
     const bool wo = c->fp8 && c->fp8_wonly;          // weight-only decode GEMVs: bf16 activations straight from dH / dO / dACT, no quantiser launches
     const bool f8 = c->fp8 && !wo;
     auto ksf = [&](int N, int K) { return wo ? skinny_w8_ks(N, K, B) : f8 ? skinny_fp8_ks(N, K, B) : skinny_ks(N, K, EPI_PARTIAL, B); };
     const int ks_q = ksf(QKV, H), ks_o = ksf(H, H), ks_g = ksf(2 * I, H), ks_d = ksf(H, I);
-#define GEMVW(X_, W8D_, SW_, N_, K_) LCHK(launch_skinny_w8((X_), (K_), (W8D_), (SW_), B, (N_), (K_), c->sk_ws, c->sk_ws_floats, s));
-    // fp8: the GEMV's activations are quantised row-wise first (quant_rows_fp8: [B, K] bf16 -> e4m3 + per-row scale), the weights come
-    // from the e4m3 tile copy; partial rows, their consumers and the attention are the bf16 path's
-#define GEMV8(X_, W8D_, SW_, N_, K_)                                                                           \
-    LCHK(launch_quant_rows_fp8((X_), (K_), c->dA8, (K_), c->dsa, B, (K_), s));                                  \
-    LCHK(launch_skinny_fp8(c->dA8, (K_), c->dsa, (W8D_), (SW_), B, (N_), (K_), c->sk_ws, c->sk_ws_floats, s));
-    // the normed hidden rows arrive already quantised (dH8 / dsh) from add_rmsnorm; only the step's first norm needs the quantiser
-#define GEMV8H(W8D_, SW_, N_) LCHK(launch_skinny_fp8(c->dH8, H, c->dsh, (W8D_), (SW_), B, (N_), H, c->sk_ws, c->sk_ws_floats, s));
+    // One projection of the step, X [B, K] -> partial rows in sk_ws, on the step's kind of weights: bf16 tile copies (Wd), or the e4m3 tile copy (W8d, scales
+    // sw) with bf16 activations (weight-only) or with activations quantised row-wise first (quant_rows_fp8: [B, K] bf16 -> e4m3 + per-row scale).  The
+    // normed hidden rows dH arrive already quantised (dH8 / dsh) from add_rmsnorm; only the step's first norm needs the quantiser.  Partial rows, their
+    // consumers and the attention are the bf16 path's.
+    auto gemv = [&](const bf16_t* X, const bf16_t* Wd, const uint8_t* W8d, const float* sw, int N, int K) -> int {
+        if (wo) return launch_skinny_w8(X, K, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
+        if (!f8) return launch_skinny_gemm(X, K, Wd, K, nullptr, N, nullptr, 0, B, N, K, EPI_PARTIAL, 1, SKWS(c), s);
+        if (X == c->dH) return launch_skinny_fp8(c->dH8, K, c->dsh, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
+        const int rc = launch_quant_rows_fp8(X, K, c->dA8, K, c->dsa, B, K, s);
+        return rc != TRACE_OK ? rc : launch_skinny_fp8(c->dA8, K, c->dsa, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
+    };
+    const bool unfused = g_tune.decode_unfused_qkv == 1 || (g_tune.decode_unfused_qkv == 0 && B >= 32);
     LCHK(launch_rmsnorm(c->dX, H, c->dH, H, c->llm[0].rms1, B, H, c->c.rms_eps, s));
     if (f8) LCHK(launch_quant_rows_fp8(c->dH, H, c->dH8, H, c->dsh, B, H, s));
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
-        bf16_t* kc = c->kcache + (size_t)l * c->layer_stride;
-        bf16_t* vc = c->vcache + (size_t)l * c->layer_stride;
         // (fusing the RMSNorm into the GEMV itself was tried: re-scaling the same activations in every workgroup cost
         //  more than a row kernel — 65 us vs 52 + 6 us for the gate|up GEMV)
-        if (wo) { GEMVW(c->dH, W.wqkv8_d, W.sqkv, QKV, H) }
-        else if (f8) { GEMV8H(W.wqkv8_d, W.sqkv, QKV) }
-        else LCHK(launch_skinny_gemm(c->dH, H, W.wqkv_d, H, nullptr, QKV, nullptr, 0, B, QKV, H, EPI_PARTIAL, 1, SKWS(c), s));
-        if (g_decode_unfused == 1 || (g_decode_unfused == 0 && B >= 32)) {
-            LCHK(launch_qkv_finish(c->sk_ws, ks_q, QKV, c->dQKV, kc, vc, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots,
-                                   c->d_pos, B, c->NQ, c->NKV, c->rope_cos, c->rope_sin, s));
-            LCHK(launch_attn_decode(c->dQKV, QKV, kc, vc, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->dO,
-                                    H, c->attn_ws, c->tickets, B, c->NQ, c->NKV, HD, decode_nsplit(B), 1.0f / sqrtf((float)HD), 0,
-                                    nullptr, nullptr, nullptr, 0, s));
-        } else
-        LCHK(launch_attn_decode(c->dQKV, QKV, kc, vc, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->dO,
-                                H, c->attn_ws, c->tickets, B, c->NQ, c->NKV, HD, decode_nsplit(B), 1.0f / sqrtf((float)HD), 1,
-                                c->rope_cos, c->rope_sin, c->sk_ws, ks_q, s));
-        if (wo) { GEMVW(c->dO, W.wo8_d, W.so, H, H) }
-        else if (f8) { GEMV8(c->dO, W.wo8_d, W.so, H, H) }
-        else LCHK(launch_skinny_gemm(c->dO, H, W.wo_d, H, nullptr, H, nullptr, 0, B, H, H, EPI_PARTIAL, 1, SKWS(c), s));
+        LCHK(gemv(c->dH, W.wqkv_d, W.wqkv8_d, W.sqkv, QKV, H));
+        if (unfused) LCHK(qkv_finish_layer(c, l, ks_q, s));
+        LCHK(attn_decode_layer(c, l, !unfused, c->sk_ws, ks_q, s));
+        LCHK(gemv(c->dO, W.wo_d, W.wo8_d, W.so, H, H));
         LCHK(launch_add_rmsnorm(c->sk_ws, ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
-        // roofline probe: HIP events around ONE launch of the dominant kernel (layer 0 gate|up GEMV) per step
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (l == 0 && c->profile == 2 && (c->bracket_mask & 2)) {
-            // (event-record nodes captured into a hipGraph do not yield usable timestamps on ROCm 7.2: eager launches only)
-            if (s != c->cap_stream && c->kev_used + 2 <= (int)c->kev.size()) { e0 = c->kev[c->kev_used]; e1 = c->kev[c->kev_used + 1]; c->kev_used += 2; c->bracket_kind = 1; }
+        {   // bracketed: the layer-0 gate|up GEMV (fp8: the bracket spans what the projection launches)
+            StepBracket br(c, l, 1, s);
+            LCHK(gemv(c->dH, W.wgu_d, W.wgu8_d, W.sgu, 2 * I, H));
         }
-        if (e0) hipEventRecord(e0, s);
-        if (wo) { GEMVW(c->dH, W.wgu8_d, W.sgu, 2 * I, H) }
-        else if (f8) { GEMV8H(W.wgu8_d, W.sgu, 2 * I) }
-        else LCHK(launch_skinny_gemm(c->dH, H, W.wgu_d, H, nullptr, 2 * I, nullptr, 0, B, 2 * I, H, EPI_PARTIAL, 1, SKWS(c), s));
-        if (e1) hipEventRecord(e1, s);
         // (SwiGLU inside the gate|up GEMV at batch <= 16 — one K chunk, no combine kernel — measured 3.73 vs 3.5 ms per batch-1 step: its 224
         //  workgroups leave 32 CUs without a weight stream)
         LCHK(launch_swiglu_combine(c->sk_ws, ks_g, 2 * I, c->dACT, I, B, s));
-        if (wo) { GEMVW(c->dACT, W.wd8_d, W.sd, H, I) }
-        else if (f8) { GEMV8(c->dACT, W.wd8_d, W.sd, H, I) }
-        else LCHK(launch_skinny_gemm(c->dACT, I, W.wd_d, I, nullptr, H, nullptr, 0, B, H, I, EPI_PARTIAL, 1, SKWS(c), s));
+        LCHK(gemv(c->dACT, W.wd_d, W.wd8_d, W.sd, H, I));
         const bf16_t* nw = l + 1 < c->NL ? c->llm[l + 1].rms1 : c->final_norm;
         LCHK(launch_add_rmsnorm(c->sk_ws, ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
     }
-#undef GEMV8
-#undef GEMV8H
-#undef GEMVW
     return head_and_select(c, c->dH, 1, logits_out, s);
 }
 
@@ -1451,7 +1529,7 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
         c->prof[2] = c->ksamples ? (float)(c->ksum_ms / c->ksamples) : 0.f;
         c->prof[3] = (float)c->ksamples;
         // algorithmic bytes of the bracketed launch, by WHICH launch took the bracket (bracket_kind — not by the batch size: the wide step starts at
-        // g_decode_wide_min rows, below SKINNY_ROWS): the gate|up weights (fp8: the bracket also spans the activation quantiser), or the layer-0
+        // decode.wide_min_rows rows, below SKINNY_ROWS): the gate|up weights (fp8: the bracket also spans the activation quantiser), or the layer-0
         // attention's KV rows averaged over the bracketed steps
         c->prof[4] = (float)(2.0 * c->I * c->H * (c->fp8 ? 1.0 : 2.0));
         if (c->bracket_kind == 3 && c->ksamples) c->prof[4] = (float)(c->kbytes_sum / c->ksamples);
@@ -1554,7 +1632,6 @@ extern "C" int trace_decode_feed(trace_ctx* c, const int32_t* tokens, int B, voi
 }
 
 // ------------------------------------------------------------------------------------------------ pipeline streams
-extern int g_gemm_pers_grid_cap;
 extern "C" int trace_stream_create(trace_ctx* c, int cu_first, int cu_count, void** stream_out) {
     if (!c || !stream_out) return fail(TRACE_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->dev));
@@ -1629,53 +1706,6 @@ extern "C" int trace_op_gemm(const void* A, int lda, const void* W, int ldw, voi
     return gemm((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (bf16_t*)C, ldc, (const bf16_t*)bias, (const bf16_t*)R, ldr, M, N, K,
                 epilogue, (hipStream_t)stream);
 }
-extern int g_gemm_variant;
-extern int g_attn_debug;
-extern int g_attn_pf_debug;
-extern int g_skinny_debug;
-extern int g_gemm_pers_opt;
-extern int g_gemm_ldr_opt;
-extern int g_gemm_pers_walk;
-extern int g_gemm_resid_pers;
-extern int g_gemm_w4;
-extern int g_gemm_w4_opt;
-extern int g_attn_vit_big;
-extern int g_partial_cfg;
-extern int g_attn_decode_w3;
-extern int g_attn_decode_nt;
-extern int g_attn_decode_lds_pad;
-extern int g_partial_wgs;
-extern "C" int trace_op_set_gemm_variant(int variant) {
-    if (variant >= 1000 && variant <= 1000 + 1024) { g_gemm_pers_grid_cap = variant - 1000; return TRACE_OK; }   // persistent GEMM: at most n workgroups (0 = #CUs)
-    if (variant >= 100 && variant < 110) { g_attn_debug = variant - 100; return TRACE_OK; }      // decode attention knock-outs (108: V^T read as contiguous blocks, timing only)
-    if (variant >= 110 && variant < 120) { g_attn_pf_debug = variant - 110; return TRACE_OK; }
-    if (variant >= 120 && variant <= 122) { g_decode_unfused = variant - 120; return TRACE_OK; }
-    if (variant >= 130 && variant <= 137) { g_decode_gemm_tiled = variant - 130; return TRACE_OK; }
-    if (variant >= 760 && variant <= 764) { g_attn_decode_w3 = variant == 762 ? -1 : variant - 760; return TRACE_OK; }
-    if (variant >= 780 && variant <= 799) { g_attn_decode_lds_pad = (variant - 780) * 8; return TRACE_OK; }
-    if (variant >= 770 && variant <= 771) { g_attn_decode_nt = variant - 770; return TRACE_OK; }
-    if (variant >= 750 && variant <= 751) { g_prefill_last_rows = variant - 750; return TRACE_OK; }
-    if (variant >= 740 && variant <= 743) { g_partial_cfg = variant - 740; return TRACE_OK; }        // tile shape of the decode partial-row GEMM (gemm.hip)
-    if (variant >= 800 && variant <= 832) { g_partial_wgs = (variant - 800) * 32; return TRACE_OK; }   // its workgroup target (0 = default 256)
-    if (variant >= 700 && variant < 732) { g_decode_gemm_tiled = variant - 700; return TRACE_OK; }   // the same word with its round-6 bits: 2 = nt weight DMA, 8 / 16 = nt / write-through partial-row stores
-    if (variant >= 160 && variant <= 161) { g_vit_patch_fused = variant - 160; return TRACE_OK; }
-    if (variant >= 170 && variant <= 174) { g_decode_fuse_norm_rows = variant - 170; return TRACE_OK; }
-    if (variant >= 180 && variant <= 181) { g_decode_fuse_swiglu = variant - 180; return TRACE_OK; }
-    if (variant >= 190 && variant <= 192) { g_attn_vit_big = variant - 190; return TRACE_OK; }   // ViT attention: 0 = the 4 x 32-row kernel, 1 = the 192-row kernel (4-stage ring), 2 = (3-stage ring)
-    if (variant >= 850 && variant <= 866) { g_attn_decode_nsplit = variant - 850; return TRACE_OK; }
-    if (variant >= 144 && variant <= 145) { g_decode_wide_fuse_qkv = variant - 144; return TRACE_OK; }
-    if (variant >= 140 && variant <= 143) { g_decode_wide_min = variant == 140 ? SKINNY_ROWS + 1 : variant == 141 ? 33 : variant == 142 ? 17 : 32; return TRACE_OK; }
-    if (variant >= 200 && variant < 210) { g_skinny_debug = variant - 200; return TRACE_OK; }
-    if (variant >= 300 && variant < 364) { g_gemm_pers_opt = variant - 300; return TRACE_OK; }
-    if (variant >= 500 && variant <= 501) { g_gemm_pers_walk = variant - 500; return TRACE_OK; }   // the persistent GEMM's tile walk on every route (gemm_pers.hip)
-    if (variant >= 520 && variant <= 521) { g_gemm_resid_pers = variant - 520; return TRACE_OK; }
-    if (variant >= 530 && variant <= 531) { g_gemm_w4 = variant - 530; return TRACE_OK; }
-    if (variant >= 540 && variant < 548) { g_gemm_w4_opt = variant - 540; return TRACE_OK; }   // gemm_w4.hip A/B builds: bit 0 = one barrier per K-tile, bit 2 = L2 touches of the A panel   // non-residual 256^2 shapes: 0 = gemm_pers.hip, 1 = gemm_w4.hip (auto routing)   // residual GEMMs on the persistent kernel too (auto routing)
-    if (variant >= 400 && variant < 404) { g_gemm_ldr_opt = variant - 400; return TRACE_OK; }   // gemm_ldr A/B: bit 0 = no residual touches, bit 1 = no A-panel touches
-    if (variant < 0 || variant > 8) return fail(TRACE_ERR_ARG, "variant must be 0..8");
-    g_gemm_variant = variant;
-    return TRACE_OK;
-}
 extern "C" int trace_op_layernorm(const void* x, void* y, const void* w, const void* b, int rows, int D, float eps, void* stream) {
     LCHK(launch_layernorm((const bf16_t*)x, D, (bf16_t*)y, D, (const bf16_t*)w, (const bf16_t*)b, rows, D, eps, (hipStream_t)stream));
     return TRACE_OK;
@@ -1737,17 +1767,13 @@ extern "C" int trace_op_sk_rows(void) { return SK_ROWS; }
 // gate|up of a wide decode step: X [M <= 128, K] . Wt (the 16-row interleaved gate|up matrix in the decode tile layout) -> SwiGLU -> out [M, N/2] bf16
 extern "C" int trace_op_gemm_swiglu_tiled(const void* X, const void* Wt, void* out, int M, int N, int K, int ring, void* stream) {
     GemmArgs g{(const bf16_t*)X, K, (const bf16_t*)Wt, K, (bf16_t*)out, N / 2, nullptr, nullptr, 0, M, N, K, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, ring ? 5 : 1};
-    const int rc = launch_gemm_bf16(g, EPI_SWIGLU, (hipStream_t)stream);
-    if (rc != TRACE_OK) return fail(rc, "tiled SwiGLU GEMM launch failed");
-    return TRACE_OK;
+    return gemm_checked(g, EPI_SWIGLU, (hipStream_t)stream, "tiled SwiGLU GEMM");
 }
 // [M <= 128, K] x [N, K]^T as fp32 k-chunk partial rows [trace_op_gemm_partial_ks(N, K)][trace_op_sk_rows()][N] (decode batches above 64 rows)
 extern "C" int trace_op_gemm_partial_ks(int N, int K) { return gemm_partial_ks(N, K); }
 extern "C" int trace_op_gemm_partial(const void* A, const void* W, float* part, int M, int N, int K, int w_tiled, void* stream) {
     GemmArgs g{(const bf16_t*)A, K, (const bf16_t*)W, K, nullptr, 0, nullptr, nullptr, 0, M, N, K, nullptr, 0, nullptr, nullptr, 0, part, gemm_partial_ks(N, K), w_tiled};
-    const int rc = launch_gemm_bf16(g, EPI_PARTIAL, (hipStream_t)stream);
-    if (rc != TRACE_OK) return fail(rc, "partial GEMM launch failed");
-    return TRACE_OK;
+    return gemm_checked(g, EPI_PARTIAL, (hipStream_t)stream, "partial GEMM");
 }
 // ---- fp8 path hooks (tests/test_gpu_fp8.py) ----
 extern "C" int trace_op_quant_rows_fp8(const void* X, void* X8, float* sx, int rows, int K, void* stream) {
@@ -1758,42 +1784,20 @@ extern "C" int trace_op_gemm_fp8(const void* A8, const float* sa, const void* W8
                                  int epilogue, void* stream) {
     const int No = epilogue == EPI_SWIGLU ? N / 2 : N;
     GemmArgs g{(const bf16_t*)A8, K, (const bf16_t*)W8, K, (bf16_t*)C, No, nullptr, (const bf16_t*)R, No, M, N, K, nullptr, 1, sa, sw};
-    const int rc = launch_gemm_bf16(g, epilogue, (hipStream_t)stream);
-    if (rc != TRACE_OK) return fail(rc, "fp8 gemm launch failed");
-    return TRACE_OK;
+    return gemm_checked(g, epilogue, (hipStream_t)stream, "fp8 gemm");
 }
-// X8 [B,K] e4m3 + sx, W8 [N,K] e4m3 row-major + sw -> out fp32 [B,N] (the k-chunk partial rows summed here, in chunk order)
-extern "C" int trace_op_skinny_fp8(const void* X8, const float* sx, const void* W8, const float* sw, float* out, int B, int N, int K, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
+// X [B,K] (e4m3 bytes + sx, or bf16 with sx null: the weight-only form), W8 [N,K] e4m3 row-major + sw -> out fp32 [B,N] (the k-chunk partial rows summed
+// here, in chunk order)
+static int op_skinny_e4m3(const void* X, const float* sx, const void* W8, const float* sw, float* out, int B, int N, int K, hipStream_t s) {
     static uint8_t* wt = nullptr; static size_t wt_bytes = 0;
     static float* ws = nullptr; static size_t ws_floats = 0;
-    const size_t need_w = (size_t)N * K, need_ws = (size_t)skinny_fp8_ks(N, K, B) * SK_ROWS * N;
-    if (need_w > wt_bytes) { HIPCHK(hipDeviceSynchronize()); if (wt) hipFree(wt); HIPCHK(hipMalloc((void**)&wt, need_w)); wt_bytes = need_w; }
-    if (need_ws > ws_floats) { HIPCHK(hipDeviceSynchronize()); if (ws) hipFree(ws); HIPCHK(hipMalloc((void**)&ws, need_ws * 4)); ws_floats = need_ws; }
-    LCHK(launch_tile_pack_fp8((const uint8_t*)W8, K, wt, N, K, s));
-    LCHK(launch_skinny_fp8((const uint8_t*)X8, K, sx, wt, sw, B, N, K, ws, ws_floats, s));
-    const int KS = skinny_fp8_ks(N, K, B);
-    std::vector<float> h((size_t)KS * SK_ROWS * N), o((size_t)B * N, 0.f);
-    HIPCHK(hipMemcpyAsync(h.data(), ws, h.size() * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int ks = 0; ks < KS; ++ks)
-        for (int b = 0; b < B; ++b)
-            for (int n = 0; n < N; ++n) o[(size_t)b * N + n] += h[((size_t)ks * SK_ROWS + b) * N + n];
-    HIPCHK(hipMemcpy(out, o.data(), o.size() * 4, hipMemcpyHostToDevice));
-    return TRACE_OK;
-}
-
-// weight-only form: X bf16 [B,K], W8 [N,K] e4m3 row-major + sw -> out fp32 [B,N] (the k-chunk partial rows summed here, in chunk order)
-extern "C" int trace_op_skinny_w8(const void* X, const void* W8, const float* sw, float* out, int B, int N, int K, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    static uint8_t* wt = nullptr; static size_t wt_bytes = 0;
-    static float* ws = nullptr; static size_t ws_floats = 0;
-    const int KS = skinny_w8_ks(N, K, B);
+    const int KS = sx ? skinny_fp8_ks(N, K, B) : skinny_w8_ks(N, K, B);
     const size_t need_w = (size_t)N * K, need_ws = (size_t)KS * SK_ROWS * N;
     if (need_w > wt_bytes) { HIPCHK(hipDeviceSynchronize()); if (wt) hipFree(wt); HIPCHK(hipMalloc((void**)&wt, need_w)); wt_bytes = need_w; }
     if (need_ws > ws_floats) { HIPCHK(hipDeviceSynchronize()); if (ws) hipFree(ws); HIPCHK(hipMalloc((void**)&ws, need_ws * 4)); ws_floats = need_ws; }
     LCHK(launch_tile_pack_fp8((const uint8_t*)W8, K, wt, N, K, s));
-    LCHK(launch_skinny_w8((const bf16_t*)X, K, wt, sw, B, N, K, ws, ws_floats, s));
+    if (sx) LCHK(launch_skinny_fp8((const uint8_t*)X, K, sx, wt, sw, B, N, K, ws, ws_floats, s));
+    else LCHK(launch_skinny_w8((const bf16_t*)X, K, wt, sw, B, N, K, ws, ws_floats, s));
     std::vector<float> h((size_t)KS * SK_ROWS * N), o((size_t)B * N, 0.f);
     HIPCHK(hipMemcpyAsync(h.data(), ws, h.size() * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -1802,6 +1806,13 @@ extern "C" int trace_op_skinny_w8(const void* X, const void* W8, const float* sw
             for (int n = 0; n < N; ++n) o[(size_t)b * N + n] += h[((size_t)ks * SK_ROWS + b) * N + n];
     HIPCHK(hipMemcpy(out, o.data(), o.size() * 4, hipMemcpyHostToDevice));
     return TRACE_OK;
+}
+extern "C" int trace_op_skinny_fp8(const void* X8, const float* sx, const void* W8, const float* sw, float* out, int B, int N, int K, void* stream) {
+    if (!sx) return fail(TRACE_ERR_ARG, "null activation scales");
+    return op_skinny_e4m3(X8, sx, W8, sw, out, B, N, K, (hipStream_t)stream);
+}
+extern "C" int trace_op_skinny_w8(const void* X, const void* W8, const float* sw, float* out, int B, int N, int K, void* stream) {
+    return op_skinny_e4m3(X, nullptr, W8, sw, out, B, N, K, (hipStream_t)stream);
 }
 
 // the fused-norm decode GEMV of small batches: part_in [ks_in][sk_rows][K] fp32 + R [B,K] -> xout [B,K] (new residual), out = fp32 partial rows

@@ -384,16 +384,6 @@ int launch_glds(const GemmArgs& p, int epi, hipStream_t s) {
 
 }  // namespace
 
-int g_gemm_variant = 0;   // 0 = auto, 2 = 128^2 tiles, 3 = this file's 256^2 kernel, 4 = the loader-wave 256^2 kernel, 5 / 6 = the persistent one
-                          // (gemm_pers.hip; 6 = static tile deal) — tests / microbench
-extern std::atomic<int> g_gemm_pers_static;   // (written on the launch path by both pipeline host threads, always with the value it holds: atomic so that this is defined behaviour)
-int g_gemm_w4 = -1;          // non-residual 256^2 shapes on gemm_w4.hip in auto mode: 1 / 0 (trace_op_set_gemm_variant(530 + x)); -1 = TRACE_GEMM_W4 from the environment, else on
-static bool gemm_w4_enabled() {
-    static const int env = getenv("TRACE_GEMM_W4") ? (atoi(getenv("TRACE_GEMM_W4")) != 0) : 1;      // (read once; the pipeline's two host threads both come through here)
-    return g_gemm_w4 < 0 ? env != 0 : g_gemm_w4 != 0;
-}
-int g_gemm_resid_pers = 0;   // 1: residual shapes also run on the persistent kernel in auto mode (trace_op_set_gemm_variant(520 + x); A/B runs)
-
 // split-K partial-row GEMM for decode batches above SKINNY_ROWS: M <= 128 rows (one row panel), 128 x BN tiles, ks chunks of K
 template <int EPI, bool WT, int NSTAGE, int BN = 128, int WM = 2, int WN = 2>
 static int launch_dec(const GemmArgs& p, int nblk, hipStream_t s) {
@@ -403,19 +393,17 @@ static int launch_dec(const GemmArgs& p, int nblk, hipStream_t s) {
     hipLaunchKernelGGL((gemm_glds_kernel<128, BN, WM, WN, EPI, false, WT, NSTAGE>), dim3(nblk), dim3(256), LDSB, s, p);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
-// Tile shape of the partial-row GEMM (A/B: trace_op_set_gemm_variant(740 + x)): 0 = 128 x 128 on 2 x 2 waves, 4-stage ring (round 3); 1 / 2 / 3 = 128 x 64 on
+// Tile shape of the partial-row GEMM (decode.partial_cfg): 0 = 128 x 128 on 2 x 2 waves, 4-stage ring (round 3); 1 / 2 / 3 = 128 x 64 on
 // 4 x 1 waves with a 5- / 3- / 4-stage ring (24 KB stages: half the partial-row bytes per product at the same number of workgroups, K loops twice as long;
 // the 3-stage form fits two workgroups per CU)
-int g_partial_cfg = 0;
-int g_partial_wgs = 0;      // workgroup target of gemm_partial_ks (0 = TRACE_PARTIAL_WGS from the environment, else 192; A/B: trace_op_set_gemm_variant(800 + n / 32))
-static int partial_bn() { return g_partial_cfg ? 64 : 128; }
+static int partial_bn() { return g_tune.decode_partial_cfg ? 64 : 128; }
 static int launch_partial(const GemmArgs& p, hipStream_t s) {
     const int bn = (p.w_tiled & 1) ? partial_bn() : 128;
     if (p.M < 1 || p.M > SK_ROWS || p.N % bn || p.K % BK || p.fp8 || !p.part || p.ks < 1 || (p.K / BK) % p.ks) return TRACE_ERR_ARG;
     if ((p.lda % 8) || (p.ldw % 8)) return TRACE_ERR_ARG;
     const int nblk = ((p.M + 127) / 128) * (p.N / bn) * p.ks;      // above 128 rows: two row panels (neighbours in the tile order: the second reads its weight tile from L2)
     if (!(p.w_tiled & 1)) return launch_dec<EPI_PARTIAL, false, 2>(p, nblk, s);
-    if (bn == 64) return g_partial_cfg == 1 ? launch_dec<EPI_PARTIAL, true, 5, 64, 4, 1>(p, nblk, s) : g_partial_cfg == 2 ? launch_dec<EPI_PARTIAL, true, 3, 64, 4, 1>(p, nblk, s)
+    if (bn == 64) return g_tune.decode_partial_cfg == 1 ? launch_dec<EPI_PARTIAL, true, 5, 64, 4, 1>(p, nblk, s) : g_tune.decode_partial_cfg == 2 ? launch_dec<EPI_PARTIAL, true, 3, 64, 4, 1>(p, nblk, s)
                                                                                                   : launch_dec<EPI_PARTIAL, true, 4, 64, 4, 1>(p, nblk, s);
     return (p.w_tiled & 4) ? launch_dec<EPI_PARTIAL, true, 4>(p, nblk, s) : launch_dec<EPI_PARTIAL, true, 2>(p, nblk, s);
 }
@@ -429,63 +417,70 @@ static int launch_swiglu_tiled(const GemmArgs& p, hipStream_t s) {
 // K-tiles per chunk (a shorter K loop is all prologue).  Target 192 since round 6 (was 256): the 7B qkv product (48 column tiles) is then cut in 4 chunks = 192 workgroups
 // in one round instead of 8 = 384 in one and a half, with half the partial-row bytes; o / down (32 tiles) keep 8 chunks = 256.  Wide step, ms per 128-sequence step at
 // ctx 1968 (profiles/r06_decode_splitk_ab.txt): target 256 11.01, 192 10.59, 160 10.41 (= 192), 128 (o / down at 4 chunks) 10.72, 96 10.96, 64 12.27.
-// TRACE_PARTIAL_WGS overrides the workgroup target (tuning runs).
+// decode.partial_wgs is the workgroup target (TRACE_PARTIAL_WGS sets its initial value: tuning runs); 0 = that initial value.
 int gemm_partial_ks(int N, int K) {
-    static const int env_target = getenv("TRACE_PARTIAL_WGS") ? atoi(getenv("TRACE_PARTIAL_WGS")) : 192;
-    const int target = g_partial_wgs > 0 ? g_partial_wgs : env_target;
+    const int target = g_tune.decode_partial_wgs > 0 ? g_tune.decode_partial_wgs : tuning_initial().decode_partial_wgs;
     const int tiles = N / partial_bn(), nk = K / BK;
     int ks = 1;
     while (tiles * ks < target && nk % (ks * 2) == 0 && nk / (ks * 2) >= 4) ks *= 2;
     return ks;
 }
 
+// the shape and stride rules of launch_gemm_bf16 (not the EPI_PARTIAL / w_tiled paths)
+bool gemm_shape_ok(const GemmArgs& p, int epi) {
+    if (epi < EPI_NONE || epi > EPI_SWIGLU || p.M <= 0 || p.N % BN || p.K % BK || p.K < BK) return false;
+    if (p.fp8 && (p.K % 128 || (p.lda % 16) || (p.ldw % 16) || epi == EPI_QUICKGELU)) return false;
+    if ((p.lda % 8) || (p.ldw % 8) || (p.ldc % 8)) return false;
+    return epi != EPI_RESIDUAL || !(p.ldr % 8);
+}
+
+// Which kernel a valid shape runs on: no side effects, no HIP calls (trace_op_gemm_route shows it to host tests).
+// gemm.kernel: 0 = auto, 2 = 128^2 tiles, 3 = this file's 256^2 kernel, 4 = the loader-wave 256^2 kernel, 5 / 6 / 7 = the persistent one
+// (gemm_pers.hip) ticketed / static deal / one workgroup per tile, 8 = its 4-wave form (gemm_w4.hip) — tests / microbench.
+GemmRoute gemm_route(const GemmArgs& p, int epi, const Tuning& t) {
+    const int k = t.gemm_kernel;
+    const bool n256 = p.N % 256 == 0;
+    // auto: 256^2 tiles (one workgroup per CU, loader-wave kernel) when they fill at least 70 % of their rounds of the 256 CUs;
+    // otherwise the 128^2 kernel (two workgroups per CU).  Measured (us, 128^2 vs loader-wave 256^2; tools/gemm_variant_check.py):
+    // 192 tiles = 0.75 round (single-prompt qkv) 101 vs 84; 384 = 1.5 rounds (paired qkv) 182 vs 176; 128 = half a round
+    // (single-prompt o / down) 64 vs 79 and 211 vs 250.  All three kernels give the same bits (same K order).
+    const long blocks256 = (long)((p.M + 255) / 256) * (p.N / 256);
+    const long rounds = (blocks256 + 255) / 256;
+    const bool big = n256 && p.M >= 1024 && blocks256 * 10 >= rounds * 256 * 7;
+    // 256^2 tiles run on the loader-wave kernels (same results bit for bit as this file's kernel, which gemm.kernel = 3 forces for A/B runs):
+    // gemm_ldr.hip (+20-24 % on the K = 1024 ViT shapes) and, where there is no residual to fetch, its persistent form gemm_pers.hip
+    // (tools/gemm_pers_ab.py, interleaved medians vs gemm_ldr over several boxes, both with their L2 touches: fc1 + QuickGELU -8 .. -11 %,
+    // ViT qkv -4 .. -6 %, prefill gate|up -3 .. -7 %, prefill qkv 0 .. -5 %).  With a residual the one-workgroup-per-tile kernel stays: its
+    // LDS-staged epilogue reads the touched residual lines as full rows; the persistent kernel's two-pass register epilogue measured
+    // -5 .. +14 % against it depending on the box (gemm.resid_pers = 1 sends residual shapes there too: A/B runs).
+    const bool pers_ok = n256 && !p.fp8 && p.K >= 128 && (long)p.M * p.ldc < (1L << 30) && (epi != EPI_RESIDUAL || (long)p.M * p.ldr < (1L << 30));
+    const bool w4_ok = pers_ok && p.K >= 192 && (long)p.M * p.lda < (1L << 31) && (long)p.N * p.ldw < (1L << 31);
+    // the walk of a persistent route: 0 = ticketed, 1 = static deal (gemm.pers.walk = 1 forces it on every route), 2 = one workgroup per tile
+    auto pers = [&](GemmKernel g, int walk) { return GemmRoute{g, walk == 0 && t.gemm_pers_walk == 1 ? 1 : walk}; };
+    if (k == 8 && w4_ok) return pers(GK_W4, 0);
+    if (k >= 5 && k <= 7 && pers_ok) return pers(GK_PERS, k - 5);
+    if (n256 && (k == 4 || (k == 0 && big))) {
+        if (k != 0 || !pers_ok || (epi == EPI_RESIDUAL && !t.gemm_resid_pers)) return {GK_LDR, 0};
+        // without a residual: the 4-wave form of the persistent kernel (same bits), unless gemm.w4 = 0 (TRACE_GEMM_W4=0: A/B runs)
+        return pers(t.gemm_w4 && epi != EPI_RESIDUAL && w4_ok ? GK_W4 : GK_PERS, 0);
+    }
+    return {k == 3 && n256 ? GK_GLDS256 : GK_GLDS128, 0};
+}
+
 int launch_gemm_bf16(const GemmArgs& p, int epi, hipStream_t s) {
     if (epi == EPI_PARTIAL) return launch_partial(p, s);
     if (p.w_tiled) return epi == EPI_SWIGLU ? launch_swiglu_tiled(p, s) : TRACE_ERR_ARG;
-    if (p.M <= 0 || p.N % BN || p.K % BK || p.K < BK) return TRACE_ERR_ARG;
-    if (p.fp8 && (p.K % 128 || (p.lda % 16) || (p.ldw % 16) || !p.sa || !p.sw || p.bias || epi == EPI_QUICKGELU)) return TRACE_ERR_ARG;
-    if ((p.lda % 8) || (p.ldw % 8) || (p.ldc % 8)) return TRACE_ERR_ARG;
-    if (epi == EPI_RESIDUAL && (!p.R || (p.ldr % 8))) return TRACE_ERR_ARG;
-    {
-        int v = g_gemm_variant;
-        if (v == 0) {
-            // 256^2 tiles (one workgroup per CU, loader-wave kernel) when they fill at least 70 % of their rounds of the 256 CUs;
-            // otherwise the 128^2 kernel (two workgroups per CU).  Measured (us, 128^2 vs loader-wave 256^2; tools/gemm_variant_check.py):
-            // 192 tiles = 0.75 round (single-prompt qkv) 101 vs 84; 384 = 1.5 rounds (paired qkv) 182 vs 176; 128 = half a round
-            // (single-prompt o / down) 64 vs 79 and 211 vs 250.  All three kernels give the same bits (same K order).
-            const long blocks256 = (long)((p.M + 255) / 256) * (p.N / 256);
-            const long rounds = (blocks256 + 255) / 256;
-            v = (p.N % 256 == 0 && p.M >= 1024 && blocks256 * 10 >= rounds * 256 * 7) ? 3 : 2;
-        }
-        // 256^2 tiles run on the loader-wave kernels (same results bit for bit as this file's kernel, which variant 3 forces for A/B runs):
-        // gemm_ldr.hip (+20-24 % on the K = 1024 ViT shapes) and, where there is no residual to fetch, its persistent form gemm_pers.hip
-        // (tools/gemm_pers_ab.py, interleaved medians vs gemm_ldr over several boxes, both with their L2 touches: fc1 + QuickGELU -8 .. -11 %,
-        // ViT qkv -4 .. -6 %, prefill gate|up -3 .. -7 %, prefill qkv 0 .. -5 %).  With a residual the one-workgroup-per-tile kernel stays: its
-        // LDS-staged epilogue reads the touched residual lines as full rows; the persistent kernel's two-pass register epilogue measured
-        // -5 .. +14 % against it depending on the box.
-        const bool pers_ok = p.N % 256 == 0 && !p.fp8 && p.K >= 128 && (long)p.M * p.ldc < (1L << 30) &&
-                             (epi != EPI_RESIDUAL || (long)p.M * p.ldr < (1L << 30));
-        if (g_gemm_variant == 8 && pers_ok && p.K >= 192 && (long)p.M * p.lda < (1L << 31) && (long)p.N * p.ldw < (1L << 31)) {
-            g_gemm_pers_static = 0;
-            return launch_gemm_w4(p, epi, s);                  // the 4-wave persistent kernel (A/B runs)
-        }
-        if ((g_gemm_variant >= 5 && g_gemm_variant <= 7) && pers_ok) {
-            g_gemm_pers_static = g_gemm_variant - 5;        // 5 ticketed, 6 static deal, 7 one workgroup per tile
-            return launch_gemm_pers(p, epi, s);
-        }
-        if (p.N % 256 == 0 && (g_gemm_variant == 4 || (g_gemm_variant == 0 && v == 3))) {
-            if (g_gemm_variant == 0 && pers_ok && (epi != EPI_RESIDUAL || g_gemm_resid_pers)) {
-                g_gemm_pers_static = 0;
-                // without a residual: the 4-wave form of the persistent kernel (gemm_w4.hip; same bits), unless switched off
-                // (trace_op_set_gemm_variant(530) / TRACE_GEMM_W4=0: A/B runs)
-                const bool w4 = gemm_w4_enabled() && epi != EPI_RESIDUAL && p.K >= 192 && (long)p.M * p.lda < (1L << 31) && (long)p.N * p.ldw < (1L << 31);
-                const int rc = w4 ? launch_gemm_w4(p, epi, s) : launch_gemm_pers(p, epi, s);
-                // no ticket counters for this stream and none can be made inside a capture: the one-workgroup-per-tile kernel gives the same bits
-                if (rc != TRACE_ERR_STATE) return rc;
-            }
-            return launch_gemm_ldr(p, epi, s);
-        }
-        if (v == 3 && p.N % 256 == 0) return p.fp8 ? launch_glds<256, 256, 2, 4, true>(p, epi, s) : launch_glds<256, 256, 2, 4, false>(p, epi, s);
+    if (!gemm_shape_ok(p, epi)) return TRACE_ERR_ARG;
+    if (p.fp8 && (!p.sa || !p.sw || p.bias)) return TRACE_ERR_ARG;
+    if (epi == EPI_RESIDUAL && !p.R) return TRACE_ERR_ARG;
+    const GemmRoute r = gemm_route(p, epi, g_tune);
+    if (r.k == GK_W4 || r.k == GK_PERS) {
+        const int rc = r.k == GK_W4 ? launch_gemm_w4(p, epi, r.walk, s) : launch_gemm_pers(p, epi, r.walk, s);
+        // auto routing: no ticket counters for this stream and none can be made inside a capture: the one-workgroup-per-tile kernel gives the same bits
+        if (rc != TRACE_ERR_STATE || g_tune.gemm_kernel != 0) return rc;
+        return launch_gemm_ldr(p, epi, s);
     }
+    if (r.k == GK_LDR) return launch_gemm_ldr(p, epi, s);
+    if (r.k == GK_GLDS256) return p.fp8 ? launch_glds<256, 256, 2, 4, true>(p, epi, s) : launch_glds<256, 256, 2, 4, false>(p, epi, s);
     return p.fp8 ? launch_glds<128, 128, 2, 2, true>(p, epi, s) : launch_glds<128, 128, 2, 2, false>(p, epi, s);
 }

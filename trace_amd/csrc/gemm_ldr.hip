@@ -287,10 +287,9 @@ void launch_one(const GemmArgs& p, int nblk, size_t lds, hipStream_t s) {
 
 }  // namespace
 
-int g_gemm_ldr_opt = 0;            // A/B: bit 0 = no residual touches, bit 1 = no A-panel touches (trace_op_set_gemm_variant(400 + opt))
 int launch_gemm_ldr(const GemmArgs& p0, int epi, hipStream_t s) {
     GemmArgs p = p0;
-    p.opt = g_gemm_ldr_opt;
+    p.opt = g_tune.gemm_ldr_opt;      // A/B: bit 0 = no residual touches, bit 1 = no A-panel touches
     if (p.M < 1 || p.N % BN || p.K % BK) return TRACE_ERR_ARG;
     constexpr size_t LOOPB = 2 * STAGE, OBYTES = (size_t)TOUCH_OFF + 4 * 256;      // staged tile + the fp8 scale rows + the touch scratch
     const size_t lds = LOOPB > OBYTES ? LOOPB : OBYTES;

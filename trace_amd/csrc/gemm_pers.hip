@@ -546,10 +546,9 @@ void launch_opt(const GemmArgs& p, int nblk, int dynamic, int* ctr, hipStream_t 
     (void)grant_dynamic_lds(grant, reinterpret_cast<const void*>(gemm_pers_kernel<EPI, OPT>), LDS_BYTES);       // a refusal shows as the launch error the caller checks
     hipLaunchKernelGGL((gemm_pers_kernel<EPI, OPT>), dim3(nblk), dim3(NTHR), LDS_BYTES, s, p, ctr, dynamic);
 }
-int g_opt = 0;
 template <int EPI>
 void launch_one(const GemmArgs& p, int nblk, int dynamic, int* ctr, hipStream_t s) {
-    switch (g_opt) {
+    switch (g_tune.gemm_pers_opt) {          // A/B builds of the K loop
         case 2: launch_opt<EPI, 2>(p, nblk, dynamic, ctr, s); break;
         case 4: launch_opt<EPI, 4>(p, nblk, dynamic, ctr, s); break;
         case 8: launch_opt<EPI, 8>(p, nblk, dynamic, ctr, s); break;
@@ -558,13 +557,6 @@ void launch_one(const GemmArgs& p, int nblk, int dynamic, int* ctr, hipStream_t 
 }
 
 }  // namespace
-
-int g_gemm_pers_opt = 0;           // A/B builds of the K loop (trace_op_set_gemm_variant(300 + opt))
-std::atomic<int> g_gemm_pers_static{0};        // 1: tiles dealt round-robin instead of by ticket (A/B runs)
-int g_gemm_pers_walk = 0;          // every route (trace_op_set_gemm_variant(500 + w)): 0 = tickets, atomic re-arm; 1 = static deal
-
-int g_gemm_pers_grid_cap = 0;      // tuning knob (trace_op_set_gemm_variant(1000 + n)); streams carry their own cap: gemm_pers_set_cap.  > 0: at most this many workgroups per launch (a stream confined to part of the CUs by a CU mask: the
-                                   // persistent grid must not exceed the CUs it can run on, or the surplus workgroups wait for a second round)
 
 // Creates the ticket counters of a stream ahead of its first launch (an allocation + a memset: not something to meet inside a timed or
 // captured region); launch_gemm_pers does it on demand otherwise.
@@ -604,33 +596,28 @@ int gemm_pers_plan(hipStream_t s, int total, int** ctr, int* nblk) {
     if (!st) return TRACE_ERR_STATE;
     int stream_cap;
     { std::lock_guard<std::mutex> lk(g_ctr_mu); stream_cap = st->cap; }
-    const int cap = stream_cap > 0 ? stream_cap : g_gemm_pers_grid_cap;
-    if (cap > 0 && cap < ncu) ncu = cap < 8 ? 8 : cap;
+    // the stream's own cap (CU-masked streams), else the process-wide tuning value gemm.pers.grid_cap: the persistent grid must not exceed the CUs it can
+    // run on, or the surplus workgroups wait for a second round
+    const int cap = stream_cap > 0 ? stream_cap : g_tune.gemm_pers_grid_cap;
+    if (cap > 0 && cap < ncu) ncu = cap < 8 ? 8 : cap;                 // every XCD keeps a workgroup: tiles are dealt per XCD
     *ctr = st->ctr;
     *nblk = total < ncu ? total : ncu;
     return TRACE_OK;
 }
 
 // TRACE_ERR_STATE: no ticket counters for this stream and none can be made now (capturing): the caller falls back to gemm_ldr
-int launch_gemm_pers(const GemmArgs& p0, int epi, hipStream_t s) {
+int launch_gemm_pers(const GemmArgs& p0, int epi, int walk, hipStream_t s) {
     GemmArgs p = p0;
     p.opt = 0;
     if (p.M < 1 || p.N % BN || p.K % BK || p.K < 2 * BK || p.fp8) return TRACE_ERR_ARG;
     if ((long)p.M * p.ldc >= (1L << 30) || (epi == EPI_RESIDUAL && (long)p.M * p.ldr >= (1L << 30))) return TRACE_ERR_ARG;   // 32-bit byte offsets
-    int ncu = 0;
-    CtrState* st = counters_for(s, &ncu);
-    if (!st) return TRACE_ERR_STATE;
-    int* ctr = st->ctr;
-    int stream_cap;
-    { std::lock_guard<std::mutex> lk(g_ctr_mu); stream_cap = st->cap; }
-    const int cap = stream_cap > 0 ? stream_cap : g_gemm_pers_grid_cap;      // the stream's own cap (CU-masked streams), else the process-wide tuning knob
-    if (cap > 0 && cap < ncu) ncu = cap < 8 ? 8 : cap;                 // every XCD keeps a workgroup: tiles are dealt per XCD
     const int total = ((p.M + BM - 1) / BM) * (p.N / BN);
-    // g_gemm_pers_static == 2: one workgroup per tile (the dispatcher places them as CUs free up, nothing persists): this kernel's K loop and
-    // register epilogue without the tile walk (A/B runs)
-    const int nblk = g_gemm_pers_static == 2 ? total : (total < ncu ? total : ncu);
-    const int dynamic = (g_gemm_pers_static || g_gemm_pers_walk == 1) ? 0 : 1;
-    g_opt = g_gemm_pers_opt;
+    int *ctr = nullptr, nblk = 0;
+    const int rc = gemm_pers_plan(s, total, &ctr, &nblk);
+    if (rc != TRACE_OK) return rc;
+    // walk 2: one workgroup per tile (the dispatcher places them as CUs free up, nothing persists): this K loop and register epilogue without the tile walk (A/B runs)
+    if (walk == 2) nblk = total;
+    const int dynamic = walk ? 0 : 1;
     switch (epi) {
         case EPI_NONE: launch_one<EPI_NONE>(p, nblk, dynamic, ctr, s); break;
         case EPI_RESIDUAL: launch_one<EPI_RESIDUAL>(p, nblk, dynamic, ctr, s); break;

@@ -399,7 +399,7 @@ bool launch_opt(const GemmArgs& p, int nblk, int dynamic, int* ctr, hipStream_t 
 }
 template <int EPI>
 bool launch_one(const GemmArgs& p, int nblk, int dynamic, int* ctr, hipStream_t s) {
-    switch (p.opt & 7) {          // A/B builds (trace_op_set_gemm_variant(540 + opt)): bit 0 = without the re-aligning barrier, bit 2 = with the L2 touches of the A panel; 2 = the check build (vmcnt(0) waits)
+    switch (p.opt & 7) {          // A/B builds (gemm.w4.opt): bit 0 = without the re-aligning barrier, bit 2 = with the L2 touches of the A panel; 2 = the check build (vmcnt(0) waits)
         case 1: return launch_opt<EPI, 1>(p, nblk, dynamic, ctr, s);
         case 2: return launch_opt<EPI, 2>(p, nblk, dynamic, ctr, s);
         case 4: return launch_opt<EPI, 4>(p, nblk, dynamic, ctr, s);
@@ -410,23 +410,18 @@ bool launch_one(const GemmArgs& p, int nblk, int dynamic, int* ctr, hipStream_t 
 
 }  // namespace
 
-extern std::atomic<int> g_gemm_pers_static;
-extern int g_gemm_pers_walk;
-int g_gemm_w4_opt = 0;             // A/B builds of this kernel (trace_op_set_gemm_variant(540 + opt)): bit 0 = without the re-aligning barrier, bit 2 = with the L2 touches of the A panel
-
 // TRACE_ERR_STATE: no ticket counters for this stream and none can be made now (capturing): the caller falls back
-int launch_gemm_w4(const GemmArgs& p0, int epi, hipStream_t s) {
+int launch_gemm_w4(const GemmArgs& p0, int epi, int walk, hipStream_t s) {
     GemmArgs p = p0;
-    p.opt = g_gemm_w4_opt;
+    p.opt = g_tune.gemm_w4_opt;
     if (p.M < 1 || p.N % BN || p.K % BK || p.K < 3 * BK || p.fp8) return TRACE_ERR_ARG;
     if ((long)p.M * p.ldc >= (1L << 30) || (epi == EPI_RESIDUAL && (long)p.M * p.ldr >= (1L << 30))) return TRACE_ERR_ARG;   // 32-bit byte offsets
     if ((long)p.M * p.lda >= (1L << 31) || (long)p.N * p.ldw >= (1L << 31)) return TRACE_ERR_ARG;                            // 32-bit piece offsets
     const int total = ((p.M + BM - 1) / BM) * (p.N / BN);
-    int* ctr = nullptr;
-    int nblk = 0;
+    int *ctr = nullptr, nblk = 0;
     const int rc = gemm_pers_plan(s, total, &ctr, &nblk);
     if (rc != TRACE_OK) return rc;
-    const int dynamic = (g_gemm_pers_static || g_gemm_pers_walk == 1) ? 0 : 1;
+    const int dynamic = walk ? 0 : 1;
     bool granted = false;
     switch (epi) {
         case EPI_NONE: granted = launch_one<EPI_NONE>(p, nblk, dynamic, ctr, s); break;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <atomic>
 #include "common.h"
+#include "tuning.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel: one process may hold contexts on several GPUs, so the grant is
 // tracked per device (a bit per device id), not once per process; safe from both launch threads of the pipeline (a double grant is idempotent).
@@ -57,10 +58,15 @@ struct GemmArgs {
     int w_tiled;
 };
 int launch_gemm_bf16(const GemmArgs& p, int epi, hipStream_t s);
+// the kernel launch_gemm_bf16 runs a shape on (gemm.hip; the EPI_PARTIAL / w_tiled paths are not routed) and, for the persistent two, the tile walk:
+enum GemmKernel { GK_GLDS128, GK_GLDS256, GK_LDR, GK_PERS, GK_W4 };
+struct GemmRoute { GemmKernel k; int walk; };                     // 0 = ticketed, 1 = static deal, 2 = one workgroup per tile (gemm_pers only)
+bool gemm_shape_ok(const GemmArgs& p, int epi);                   // false: launch_gemm_bf16 answers TRACE_ERR_ARG
+GemmRoute gemm_route(const GemmArgs& p, int epi, const Tuning& t);
 int gemm_partial_ks(int N, int K);                                // K-chunks launch_gemm_bf16(EPI_PARTIAL) should be given for an [<= 128, K] x [N, K]^T product
 int launch_gemm_ldr(const GemmArgs& p, int epi, hipStream_t s);    // gemm_ldr.hip: 256x256 tiles, 8 MFMA + 4 loader waves (N % 256 == 0)
-int launch_gemm_pers(const GemmArgs& p, int epi, hipStream_t s);   // gemm_pers.hip: the same tile, persistent workgroups, register epilogue (bf16, K >= 128)
-int launch_gemm_w4(const GemmArgs& p, int epi, hipStream_t s);     // gemm_w4.hip: the persistent 256x256 tile on 4 waves of 128x128 (bf16, K >= 192)
+int launch_gemm_pers(const GemmArgs& p, int epi, int walk, hipStream_t s);   // gemm_pers.hip: the same tile, persistent workgroups, register epilogue (bf16, K >= 128)
+int launch_gemm_w4(const GemmArgs& p, int epi, int walk, hipStream_t s);     // gemm_w4.hip: the persistent 256x256 tile on 4 waves of 128x128 (bf16, K >= 192)
 int gemm_pers_plan(hipStream_t s, int total, int** ctr, int* nblk);   // the stream's ticket counters + persistent grid size (shared by gemm_pers / gemm_w4)
 int gemm_pers_init(hipStream_t s);                                 // creates the (current device, stream) ticket counters ahead of its first launch (optional)
 int gemm_pers_set_cap(hipStream_t s, int cap);                       // at most `cap` workgroups per persistent launch on this stream (0 = #CUs)

@@ -2,6 +2,7 @@
 tensors the caller hands in/out, and the current HIP stream.  All arithmetic happens in the C-ABI library."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -820,6 +821,39 @@ class ops:
     @staticmethod
     def set_gemm_variant(v: int):
         _lib.check(_lib.load(ops.element).trace_op_set_gemm_variant(v))
+
+    @staticmethod
+    def tuning_names() -> List[str]:
+        """the names of the library's tuning table (csrc/engine.hip TUNE_ROWS), e.g. "gemm.kernel" """
+        lib, names = _lib.load(ops.element), []
+        while (n := lib.trace_op_tuning_name(len(names))) is not None:
+            names.append(n.decode())
+        return names
+
+    @staticmethod
+    def tune(name: str, value: int):
+        """sets one tuning value by its dotted name; not while launches are in flight"""
+        _lib.check(_lib.load(ops.element).trace_op_tuning_set(name.encode(), int(value)))
+
+    @staticmethod
+    @contextlib.contextmanager
+    def tuned(**values):
+        """`with ops.tuned(gemm__kernel=8, gemm__w4__opt=1):` sets tuning values (a double underscore stands for the dot) and, on exit, restores the
+        values it found — on the library of ops.element at entry."""
+        element = ops.element
+        lib = _lib.load(element)
+        found = {}
+        try:
+            for key, value in values.items():
+                name = key.replace("__", ".")
+                v = C.c_int(0)
+                _lib.check(lib.trace_op_tuning_get(name.encode(), C.byref(v)))
+                found.setdefault(name, v.value)
+                _lib.check(lib.trace_op_tuning_set(name.encode(), int(value)))
+            yield
+        finally:
+            for name, value in found.items():
+                _lib.check(lib.trace_op_tuning_set(name.encode(), value))
 
     @staticmethod
     def gemm(A, W, bias=None, R=None, epilogue=EPI_NONE):
