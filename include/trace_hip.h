@@ -253,6 +253,17 @@ int trace_op_attention(const void* Q, const void* K, const void* V, void* O, voi
 int trace_op_skinny_gemm(const void* X, const void* W, void* out, const void* R, int B, int N, int K, int epilogue,
                          int w_tiled, void* stream);
 int trace_op_skinny_ks(int N, int K, int epilogue, int B);
+/* How the decode GEMV of one kind (0 = bf16 weights: trace_op_skinny_gemm, 1 = e4m3 weights and activations: trace_op_skinny_fp8, 2 = e4m3 weights, bf16
+   activations: trace_op_skinny_w8; these two take epilogue 4 only) is cut into workgroups, without launching (no GPU needed; without one the plan is the
+   256-CU MI355X's): out[0..11) = k-chunks KS (= trace_op_skinny_ks for kind 0), k-units per chunk (64 k of bf16, 128 k of e4m3), tiles per workgroup T,
+   waves per tile, tiles, grid, threads, 16-row output tiles per task NT, 16-row activation groups NB, dynamic LDS bytes, and the floats of partial rows
+   that hold epilogue 4's product of this N, K at any B (KS * trace_op_sk_rows() * N at its largest).  TRACE_ERR_ARG for a shape the kind's GEMV rejects. */
+int trace_op_skinny_plan(int kind, int N, int K, int epilogue, int B, int64_t* out);
+/* What one decode step of B sequences does on a decoder of this geometry (fp8_scheme: trace_config.llm_weights_fp8) under the current tuning values,
+   without launching: out[0..8) = the step body (1 GEMV step, 2 fused-norm GEMV step, 3 wide GEMM step: trace_get_profile's [8]), the GEMV kind as above,
+   1 if RoPE + cache append run as a launch of their own, the k-chunks of the qkv / o / gate|up / down partial rows (gate|up: 0 on the wide step), the
+   attention's context splits.  TRACE_ERR_ARG for B outside 1..trace_op_sk_rows() and for an fp8 scheme with B > 64. */
+int trace_op_decode_route(int B, int fp8_scheme, int H, int I, int QKV, int32_t* out);
 /* Decode GEMV of 1..4 rows with the preceding "sum the partial rows + residual -> new residual, RMSNorm" folded in: part_in [ks_in][sk_rows][K] fp32
    (ks_in may be 0) + R [B,K] -> xout [B,K]; out = fp32 partial rows [trace_op_skinny_ks(N,K,4,B)][sk_rows][N] of RMSNorm(xout; w, eps) . W^T */
 int trace_op_skinny_fused_norm(const float* part_in, int ks_in, const void* R, void* xout, const void* w, float eps, const void* W, float* out,

@@ -81,6 +81,8 @@ SIGNATURES = {
     "trace_op_skinny_gemm": (I, [P, P, P, P, I, I, I, I, I, P]),
     "trace_op_set_gemm_trace": (I, [P]),
     "trace_op_skinny_ks": (I, [I, I, I, I]),
+    "trace_op_skinny_plan": (I, [I, I, I, I, I, C.POINTER(C.c_int64)]),
+    "trace_op_decode_route": (I, [I, I, I, I, I, C.POINTER(C.c_int32)]),
     "trace_op_sk_rows": (I, []),
     "trace_op_skinny_fused_norm": (I, [P, I, P, P, P, F, P, P, I, I, I, P]),
     "trace_op_gemm_partial_ks": (I, [I, I]),

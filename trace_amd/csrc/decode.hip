@@ -1013,9 +1013,9 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
 }
 }  // namespace
 
-// Partition for skinny_lds (see the kernel header): KS k-chunks x row-groups of T tiles, WPT waves per tile.
-struct SkinnyPlan { int KS, chunk_units, T, WPT, ntiles, grid, threads; };
-static int skinny_num_cus() {
+// The partition of every decode GEMV (skinny_lds here, skinny_fp8 in fp8.hip): KS k-chunks x row-groups of T tiles, WPT waves per tile.  K is counted
+// in units of 2 KB of weights per 16 rows: 64 k of bf16, 128 k of e4m3.  B enters through NB alone (its 16-row activation groups: 1, 2 or 4).
+int skinny_num_cus() {
     static int n = 0;
     if (!n) {
         int dev = 0;
@@ -1025,17 +1025,24 @@ static int skinny_num_cus() {
     }
     return n;
 }
-static int skinny_nt(int N, int epi) { return epi == EPI_SWIGLU || (epi == EPI_PARTIAL && N >= 16384 && N % 32 == 0) ? 2 : 1; }
-static int skinny_nb(int B) { return B > 32 ? 4 : B > 16 ? 2 : 1; }       // 16-row activation groups
-static SkinnyPlan skinny_plan(int N, int K, int epi, int B) {
+static int skinny_unit(SkinnyKind kind) { return kind == SK_BF16 ? 64 : 128; }
+bool skinny_shape_ok(SkinnyKind kind, int N, int K, int epi, int B) {
+    if (B < 1 || B > SKINNY_ROWS || N < 16 || K < skinny_unit(kind) || K % skinny_unit(kind)) return false;
+    if (kind != SK_BF16) return epi == EPI_PARTIAL && N % 16 == 0;
+    if (epi != EPI_NONE && epi != EPI_RESIDUAL && epi != EPI_SWIGLU && epi != EPI_PARTIAL) return false;
+    return N % (epi == EPI_SWIGLU ? 32 : 16) == 0;
+}
+static SkinnyPlan skinny_plan_nb(SkinnyKind kind, int N, int K, int epi, int NB) {
     SkinnyPlan p{};
-    const int NT = skinny_nt(N, epi), NB = skinny_nb(B);
-    const int U = K / 64;
-    static const int cap1 = getenv("TRACE_SK_CAP") ? atoi(getenv("TRACE_SK_CAP")) : 64;    // tuning knob (microbenchmarks)
-    const int cap = NB == 1 ? cap1 : 64 / NB;             // units of X that fit 128 KB of LDS
+    p.NB = NB;
+    p.NT = epi == EPI_SWIGLU || (epi == EPI_PARTIAL && N >= 16384 && N % 32 == 0) ? 2 : 1;
+    const int U = K / skinny_unit(kind);
+    static const int cap1 = getenv("TRACE_SK_CAP") ? atoi(getenv("TRACE_SK_CAP")) : 64;    // tuning knob (microbenchmarks): bf16, one row group
+    // units of X that fit 128 KB of LDS: 2 KB a unit and row group as bf16 or e4m3 images, 4 KB as bf16 rows beside e4m3 weights
+    const int cap = kind == SK_BF16 && NB == 1 ? cap1 : (kind == SK_W8A16 ? 32 : 64) / NB;
     const int ks_min = (U + cap - 1) / cap;
     const int ks_max = epi == EPI_PARTIAL ? std::min(U, ks_min + 4) : ks_min;    // extra chunks are free only without the ticket merge
-    p.ntiles = N / (16 * NT);
+    p.ntiles = N / (16 * p.NT);
     const int ncu = skinny_num_cus();
     long best = -1;
     for (int ks = ks_min; ks <= ks_max; ++ks) {
@@ -1049,37 +1056,41 @@ static SkinnyPlan skinny_plan(int N, int K, int epi, int B) {
     }
     p.WPT = 1;
     // T*WPT <= 8 waves; the LDS reduction scratch (T*WPT*NT*NB KB) must fit beside the 128 KB of parked activations
-    while (p.WPT * 2 * p.T <= 8 && p.WPT * 2 * p.T * NT * NB <= 28 && p.WPT * 2 <= p.chunk_units) p.WPT *= 2;
+    while (p.WPT * 2 * p.T <= 8 && p.WPT * 2 * p.T * p.NT * NB <= 28 && p.WPT * 2 <= p.chunk_units) p.WPT *= 2;
     p.threads = std::min(p.T, 8) * p.WPT * 64;          // T > 8: every wave takes two tasks in turn
+    p.lds_bytes = (size_t)p.chunk_units * (kind == SK_W8A16 ? 4 : 2) * NB * 1024 + (p.WPT > 1 ? (size_t)p.T * p.WPT * p.NT * NB * 1024 : 0);
     return p;
 }
-static size_t skinny_plan_ws(const SkinnyPlan& p, int N, int epi, int B) {
+SkinnyPlan skinny_plan(SkinnyKind kind, int N, int K, int epi, int B) { return skinny_plan_nb(kind, N, K, epi, B > 32 ? 4 : B > 16 ? 2 : 1); }
+int skinny_ks(SkinnyKind kind, int N, int K, int epi, int B) { return skinny_plan(kind, N, K, epi, B).KS; }
+// Workspace floats of one plan: the partial rows of EPI_PARTIAL, else what the ticket merge parks.  Sized for any batch by the maximum over the three
+// NB classes, which are all the plans there are.
+static size_t skinny_plan_ws(const SkinnyPlan& p, int N, int epi) {
     if (epi == EPI_PARTIAL) return (size_t)p.KS * SK_ROWS * N;
-    const int NT = skinny_nt(N, epi), NB = skinny_nb(B);
-    return p.KS > 1 ? (size_t)p.ntiles * p.KS * NT * NB * 256 : 0;
+    return p.KS > 1 ? (size_t)p.ntiles * p.KS * p.NT * p.NB * 256 : 0;
 }
-size_t skinny_ws_floats(int N, int K, int epi) {
+static size_t skinny_max_ws(SkinnyKind kind, int N, int K, int epi) {
     size_t f = 0;
-    for (int B : {1, 32, 64}) f = std::max(f, skinny_plan_ws(skinny_plan(N, K, epi, B), N, epi, B));
+    for (int NB : {1, 2, 4}) f = std::max(f, skinny_plan_ws(skinny_plan_nb(kind, N, K, epi, NB), N, epi));
     return f;
 }
-int skinny_ks(int N, int K, int epi, int B) { return skinny_plan(N, K, epi, B).KS; }
+size_t skinny_partial_floats(SkinnyKind kind, int N, int K) { return skinny_max_ws(kind, N, K, EPI_PARTIAL); }
+size_t skinny_ws_floats(int N, int K, int epi) { return skinny_max_ws(SK_BF16, N, K, epi); }
 
 template <int EPI, int NB, int NT, int PRO = 0>
 static int skinny_lds_launch(const SkinnyPlan& p, const bf16_t* X, int ldx, const bf16_t* W, int ldw, bf16_t* out, int ldo,
                              const bf16_t* R, int ldr, int B, int K, float* ws, unsigned int* tickets, int tiled, hipStream_t s,
                              const SkinnyPro& pro = SkinnyPro{}) {
-    const size_t lds = (size_t)p.chunk_units * 2 * NB * 1024 + (p.WPT > 1 ? (size_t)p.T * p.WPT * NT * NB * 1024 : 0);
     static LdsGrantSized grant;
-    if (!grant_dynamic_lds(grant, reinterpret_cast<const void*>(skinny_lds_kernel<EPI, NB, NT, PRO>), lds)) return TRACE_ERR_HIP;
-    hipLaunchKernelGGL((skinny_lds_kernel<EPI, NB, NT, PRO>), dim3(p.grid), dim3(p.threads), lds, s, X, ldx, W, ldw, out, ldo, R, ldr, B, K,
+    if (!grant_dynamic_lds(grant, reinterpret_cast<const void*>(skinny_lds_kernel<EPI, NB, NT, PRO>), p.lds_bytes)) return TRACE_ERR_HIP;
+    hipLaunchKernelGGL((skinny_lds_kernel<EPI, NB, NT, PRO>), dim3(p.grid), dim3(p.threads), p.lds_bytes, s, X, ldx, W, ldw, out, ldo, R, ldr, B, K,
                        p.chunk_units, p.KS, p.T, p.WPT, p.ntiles, ws, tickets, tiled, g_tune.skinny_debug, pro);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
 
 bool skinny_fused_norm_ok(int N, int K, int B) {
     if (B < 1 || B > SKINNY_PRO_ROWS || K % 64 || K > 16384 || N % 16) return false;
-    return (K >> 3) <= 2 * skinny_plan(N, K, EPI_PARTIAL, B).threads;
+    return (K >> 3) <= 2 * skinny_plan(SK_BF16, N, K, EPI_PARTIAL, B).threads;
 }
 // The fused form (see SkinnyPro): out-partials[ks][SK_ROWS][N] = RMSNorm(sum_k part_in + R; w) . Wtiled^T, new residual rows to xout.  B <= SKINNY_PRO_ROWS,
 // K <= 16384, tiled weights, part_in / ws and R / xout must not alias.
@@ -1087,47 +1098,46 @@ int launch_skinny_gemm_fused_norm(const float* part_in, int ks_in, const bf16_t*
                                   const bf16_t* Wtiled, int B, int N, int K, float* ws, size_t ws_floats, hipStream_t s) {
     if (B < 1 || B > SKINNY_PRO_ROWS || K % 64 || K > 16384 || N % 16 || ks_in < 0 || (ks_in > 0 && !part_in) || !R || !xout || R == xout || !w) return TRACE_ERR_ARG;
     if (part_in == ws || (ldr % 8) || (ldx % 8)) return TRACE_ERR_ARG;
-    const SkinnyPlan p = skinny_plan(N, K, EPI_PARTIAL, B);
-    if (!ws || ws_floats < skinny_plan_ws(p, N, EPI_PARTIAL, B)) return TRACE_ERR_ARG;
+    const SkinnyPlan p = skinny_plan(SK_BF16, N, K, EPI_PARTIAL, B);
+    if (!ws || ws_floats < skinny_plan_ws(p, N, EPI_PARTIAL)) return TRACE_ERR_ARG;
     if ((K >> 3) > 2 * p.threads) return TRACE_ERR_STATE;                     // MAXG groups per thread: the caller keeps the unfused pair for this shape
     const SkinnyPro pro{part_in, ks_in, R, ldr, xout, ldx, w, eps};
-    return skinny_nt(N, EPI_PARTIAL) == 2 ? skinny_lds_launch<EPI_PARTIAL, 1, 2, 1>(p, nullptr, K, Wtiled, K, nullptr, N, nullptr, 0, B, K, ws, nullptr, 1, s, pro)
-                                           : skinny_lds_launch<EPI_PARTIAL, 1, 1, 1>(p, nullptr, K, Wtiled, K, nullptr, N, nullptr, 0, B, K, ws, nullptr, 1, s, pro);
+    return p.NT == 2 ? skinny_lds_launch<EPI_PARTIAL, 1, 2, 1>(p, nullptr, K, Wtiled, K, nullptr, N, nullptr, 0, B, K, ws, nullptr, 1, s, pro)
+                    : skinny_lds_launch<EPI_PARTIAL, 1, 1, 1>(p, nullptr, K, Wtiled, K, nullptr, N, nullptr, 0, B, K, ws, nullptr, 1, s, pro);
 }
 
 // The down GEMV with the SwiGLU prologue (SkinnyPro, PRO == 2): out-partials[ks][SK_ROWS][N] = (silu(sum_k gate) * sum_k up) . Wtiled^T from the
 // gate|up GEMV's partial rows part_gu [ks_gu][SK_ROWS][2 K].  B <= SKINNY_PRO_ROWS, tiled weights, part_gu and ws must not alias.
 int launch_skinny_gemm_fused_swiglu(const float* part_gu, int ks_gu, const bf16_t* Wtiled, int B, int N, int K, float* ws, size_t ws_floats, hipStream_t s) {
     if (B < 1 || B > SKINNY_PRO_ROWS || K % 64 || N % 16 || ks_gu < 1 || !part_gu || part_gu == ws) return TRACE_ERR_ARG;
-    const SkinnyPlan p = skinny_plan(N, K, EPI_PARTIAL, B);
-    if (!ws || ws_floats < skinny_plan_ws(p, N, EPI_PARTIAL, B)) return TRACE_ERR_ARG;
+    const SkinnyPlan p = skinny_plan(SK_BF16, N, K, EPI_PARTIAL, B);
+    if (!ws || ws_floats < skinny_plan_ws(p, N, EPI_PARTIAL)) return TRACE_ERR_ARG;
     const SkinnyPro pro{part_gu, ks_gu, nullptr, 0, nullptr, 0, nullptr, 0.f};
-    return skinny_nt(N, EPI_PARTIAL) == 2 ? skinny_lds_launch<EPI_PARTIAL, 1, 2, 2>(p, nullptr, K, Wtiled, K, nullptr, N, nullptr, 0, B, K, ws, nullptr, 1, s, pro)
-                                           : skinny_lds_launch<EPI_PARTIAL, 1, 1, 2>(p, nullptr, K, Wtiled, K, nullptr, N, nullptr, 0, B, K, ws, nullptr, 1, s, pro);
+    return p.NT == 2 ? skinny_lds_launch<EPI_PARTIAL, 1, 2, 2>(p, nullptr, K, Wtiled, K, nullptr, N, nullptr, 0, B, K, ws, nullptr, 1, s, pro)
+                    : skinny_lds_launch<EPI_PARTIAL, 1, 1, 2>(p, nullptr, K, Wtiled, K, nullptr, N, nullptr, 0, B, K, ws, nullptr, 1, s, pro);
 }
 
 // EPI_PARTIAL: `out` is unused, ldo = N, the fp32 partial rows [KS = skinny_ks()][SK_ROWS][N] land in ws.
 int launch_skinny_gemm(const bf16_t* X, int ldx, const bf16_t* W, int ldw, bf16_t* out, int ldo, const bf16_t* R, int ldr,
                        int B, int N, int K, int epi, int tiled, float* ws, size_t ws_floats, unsigned int* tickets, int ntickets,
                        hipStream_t s) {
-    if (B < 1 || B > SKINNY_ROWS || K % 64 || (ldx % 8) || (ldw % 8) || (ldo % 4)) return TRACE_ERR_ARG;
-    if (epi != EPI_NONE && epi != EPI_RESIDUAL && epi != EPI_SWIGLU && epi != EPI_PARTIAL) return TRACE_ERR_ARG;
-    if (N % (epi == EPI_SWIGLU ? 32 : 16) || (epi == EPI_RESIDUAL && (!R || ldr % 4))) return TRACE_ERR_ARG;
-    const SkinnyPlan p = skinny_plan(N, K, epi, B);
-    const size_t need = skinny_plan_ws(p, N, epi, B);
+    if (!skinny_shape_ok(SK_BF16, N, K, epi, B) || (ldx % 8) || (ldw % 8) || (ldo % 4) || (epi == EPI_RESIDUAL && (!R || ldr % 4))) return TRACE_ERR_ARG;
+    const SkinnyPlan p = skinny_plan(SK_BF16, N, K, epi, B);
+    const size_t need = skinny_plan_ws(p, N, epi);
     if (need && (!ws || ws_floats < need)) return TRACE_ERR_ARG;
     if (epi != EPI_PARTIAL && p.KS > 1 && (!tickets || ntickets < p.ntiles)) return TRACE_ERR_ARG;
     if (epi == EPI_PARTIAL) ldo = N;
-#define SL(EPI_, NT_) (B <= 16 ? skinny_lds_launch<EPI_, 1, NT_>(p, X, ldx, W, ldw, out, ldo, R, ldr, B, K, ws, tickets, tiled, s) \
-                     : B <= 32 ? skinny_lds_launch<EPI_, 2, NT_>(p, X, ldx, W, ldw, out, ldo, R, ldr, B, K, ws, tickets, tiled, s) \
-                               : skinny_lds_launch<EPI_, 4, NT_>(p, X, ldx, W, ldw, out, ldo, R, ldr, B, K, ws, tickets, tiled, s))
+    auto run = [&](auto epi_, auto nt_) {
+        return skinny_by_nb(p.NB, [&](auto nb_) {
+            return skinny_lds_launch<decltype(epi_)::value, decltype(nb_)::value, decltype(nt_)::value>(p, X, ldx, W, ldw, out, ldo, R, ldr, B, K, ws, tickets, tiled, s);
+        });
+    };
     switch (epi) {
-        case EPI_NONE: return SL(EPI_NONE, 1);
-        case EPI_RESIDUAL: return SL(EPI_RESIDUAL, 1);
-        case EPI_PARTIAL: return skinny_nt(N, epi) == 2 ? SL(EPI_PARTIAL, 2) : SL(EPI_PARTIAL, 1);
-        default: return SL(EPI_SWIGLU, 2);
+        case EPI_NONE: return run(IntC<EPI_NONE>{}, IntC<1>{});
+        case EPI_RESIDUAL: return run(IntC<EPI_RESIDUAL>{}, IntC<1>{});
+        case EPI_PARTIAL: return p.NT == 2 ? run(IntC<EPI_PARTIAL>{}, IntC<2>{}) : run(IntC<EPI_PARTIAL>{}, IntC<1>{});
+        default: return run(IntC<EPI_SWIGLU>{}, IntC<2>{});
     }
-#undef SL
 }
 
 int launch_swiglu_combine(const float* part, int KS, int N2, bf16_t* out, int ldo, int B, hipStream_t s) {

@@ -189,7 +189,7 @@ static const TuneRow TUNE_ROWS[] = {
     {"attn.decode.waves", &Tuning::attn_decode_waves, -1, 4, -1, "waves per decode-attention workgroup: -1 / 0 / 2 = 4 (ships), 1 = 3, 3 = 6, 4 = 8"},
     {"attn.decode.nt", &Tuning::attn_decode_nt, 0, 1, 0, "non-temporal cache loads in the decode attention"},
     {"attn.decode.lds_pad_kb", &Tuning::attn_decode_lds_pad_kb, 0, 152, 0, "KB of unused dynamic LDS per decode-attention workgroup (caps the workgroups per CU)"},
-    {"attn.decode.nsplit", &Tuning::attn_decode_nsplit, 0, 16, 0, "context splits of the decode attention forced to this number (0 = decode_nsplit's rule)"},
+    {"attn.decode.nsplit", &Tuning::attn_decode_nsplit, 0, 16, 0, "context splits of the decode attention forced to this number (0 = decode_route's rule)"},
     {"attn.prefill.debug", &Tuning::attn_prefill_debug, 0, 9, 0, "microbenchmark-only knock-outs of the prefill-shaped kernels: 1 = no K/V loads after tile 0, 2 = no tile math, 5 = no LDS-DMA ViT kernel, 6 = its transposed-V path"},
     {"attn.vit.big", &Tuning::attn_vit_big, 0, 2, 2, "ViT attention: 0 = the 4 x 32-row kernel, 1 = the 192-row kernel with a 4-stage ring, 2 = with a 3-stage ring"},
     {"skinny.debug", &Tuning::skinny_debug, 0, 9, 0, "microbenchmark-only, decode GEMV: 3 = stop before the epilogue, 4 = stop after the partial stores (ticket path)"},
@@ -396,27 +396,15 @@ extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ct
     A(c->xlast, (size_t)std::max(c->max_B, 64) * H);
     A(c->attn_ws, (size_t)SK_ROWS * c->NQ * c->nsplit * (c->HD + 2)); A(c->tickets, SK_ROWS * c->NKV);
     {
-        size_t f = skinny_ws_floats(c->QKV, H, EPI_NONE);
-        f = std::max(f, skinny_ws_floats(c->QKV, H, EPI_PARTIAL));
-        f = std::max(f, skinny_ws_floats(H, H, EPI_PARTIAL));
-        f = std::max(f, skinny_ws_floats(2 * I, H, EPI_SWIGLU));
-        f = std::max(f, skinny_ws_floats(2 * I, H, EPI_PARTIAL));
-        f = std::max(f, skinny_ws_floats(H, I, EPI_PARTIAL));
-        if (c->fp8)      // the fp8 GEMV picks its own K-chunk count (128-k units): size the partial rows for it as well
-            for (int B : {1, 16, 17, 32, 33, 64}) {
-                f = std::max(f, (size_t)skinny_w8_ks(c->QKV, (int)H, B) * SK_ROWS * c->QKV);
-                f = std::max(f, (size_t)skinny_w8_ks((int)H, (int)H, B) * SK_ROWS * H);
-                f = std::max(f, (size_t)skinny_w8_ks(2 * (int)I, (int)H, B) * SK_ROWS * 2 * I);
-                f = std::max(f, (size_t)skinny_w8_ks((int)H, (int)I, B) * SK_ROWS * H);
-                f = std::max(f, (size_t)skinny_fp8_ks(c->QKV, (int)H, B) * SK_ROWS * c->QKV);
-                f = std::max(f, (size_t)skinny_fp8_ks((int)H, (int)H, B) * SK_ROWS * H);
-                f = std::max(f, (size_t)skinny_fp8_ks(2 * (int)I, (int)H, B) * SK_ROWS * 2 * I);
-                f = std::max(f, (size_t)skinny_fp8_ks((int)H, (int)I, B) * SK_ROWS * H);
-            }
-        // batches above SKINNY_ROWS: the split-K partial-row GEMM's chunks (qkv, o, down)
-        f = std::max(f, (size_t)gemm_partial_ks(c->QKV, (int)H) * SK_ROWS * c->QKV);
-        f = std::max(f, (size_t)gemm_partial_ks((int)H, (int)H) * SK_ROWS * H);
-        f = std::max(f, (size_t)gemm_partial_ks((int)H, (int)I) * SK_ROWS * H);
+        // the partial rows of the four projections, for every kind of GEMV this context can run and (qkv, o, down) for the split-K GEMM of batches above
+        // SKINNY_ROWS; beside them what the ticket merge of the bf16 qkv (EPI_NONE) and gate|up (EPI_SWIGLU) GEMVs parks
+        const struct { int N, K; bool wide_partial; } proj[4] = {{c->QKV, (int)H, true}, {(int)H, (int)H, true}, {2 * (int)I, (int)H, false}, {(int)H, (int)I, true}};
+        size_t f = std::max(skinny_ws_floats(c->QKV, (int)H, EPI_NONE), skinny_ws_floats(2 * (int)I, (int)H, EPI_SWIGLU));
+        for (const auto& p : proj) {
+            for (SkinnyKind kind : {SK_BF16, SK_W8A8, SK_W8A16})
+                if (kind == SK_BF16 || c->fp8) f = std::max(f, skinny_partial_floats(kind, p.N, p.K));
+            if (p.wide_partial) f = std::max(f, (size_t)gemm_partial_ks(p.N, p.K) * SK_ROWS * p.N);
+        }
         c->sk_ws_floats = std::max<size_t>(f, 64);
         c->sk_ntickets = (int)std::max<size_t>(std::max<size_t>((size_t)c->QKV, (size_t)H), (size_t)(2 * I)) / 16;
         A(c->sk_ws, c->sk_ws_floats); A(c->sk_tickets, c->sk_ntickets);
@@ -1284,10 +1272,28 @@ static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* l
     return TRACE_OK;
 }
 
-// decode attention context split: ~256-320 workgroups (8 kv heads x B x nsplit) fill the CUs; more splits only add
-// partial-result traffic and ticket latency (measured, ctx 2100: B=1 16 splits 10.4 us, B=4 8 -> 13 us, B=16 2 -> 26 us,
-// B=32 1 -> 45 us; B=32 with 16 splits: 79 us).  attn.decode.nsplit > 0 forces the number (A/B).
-static int decode_nsplit(int B) { if (g_tune.attn_decode_nsplit > 0) return g_tune.attn_decode_nsplit; const int n = (40 + B / 2) / B; return n < 1 ? 1 : n > 16 ? 16 : n; }
+// Everything one decode step decides before it launches.  Pure: the tuning values come as an argument, nothing is kept between steps, and the only HIP
+// call behind it is the GEMV plan's CU count, asked once per process.  trace_op_decode_route shows it to host tests.  fp8_scheme: trace_config::llm_weights_fp8.
+//   step (= prof[8]): 3 wide above SKINNY_ROWS and, on bf16 weights, from decode.wide_min_rows; 2 fused up to decode.fuse_norm_rows on bf16 weights where
+//     both fused-norm GEMVs take the shape; 1 skinny otherwise.
+//   qkv_finish: RoPE + cache append as a launch of its own instead of the attention's prologue (decode.unfused_qkv, wide: decode.wide_fuse_qkv).
+//   ks_*: K-chunks of the qkv / o / gate|up / down partial rows (the wide step's gate|up GEMM has none: 0).
+//   nsplit, the attention's context split: ~256-320 workgroups (8 kv heads x B x nsplit) fill the CUs; more splits only add partial-result traffic and
+//     ticket latency (measured, ctx 2100: B=1 16 splits 10.4 us, B=4 8 -> 13 us, B=16 2 -> 26 us, B=32 1 -> 45 us; B=32 with 16 splits: 79 us).
+//     attn.decode.nsplit > 0 forces the number (A/B).
+struct DecodeRoute { int step; SkinnyKind kind; bool qkv_finish; int ks_q, ks_o, ks_g, ks_d, nsplit; };
+static DecodeRoute decode_route(int B, int fp8_scheme, int H, int I, int QKV, const Tuning& t) {
+    DecodeRoute r{};
+    const bool fp8 = fp8_scheme != 0;
+    r.kind = !fp8 ? SK_BF16 : fp8_scheme == 2 ? SK_W8A16 : SK_W8A8;
+    if (B > SKINNY_ROWS || (B >= t.decode_wide_min_rows && !fp8)) r.step = 3;
+    else r.step = B <= t.decode_fuse_norm_rows && !fp8 && skinny_fused_norm_ok(QKV, H, B) && skinny_fused_norm_ok(2 * I, H, B) ? 2 : 1;
+    r.qkv_finish = r.step == 3 ? !t.decode_wide_fuse_qkv : r.step == 1 && (t.decode_unfused_qkv == 1 || (t.decode_unfused_qkv == 0 && B >= 32));
+    auto ks = [&](int N, int K) { return r.step == 3 ? gemm_partial_ks(N, K, t) : skinny_ks(r.kind, N, K, EPI_PARTIAL, B); };
+    r.ks_q = ks(QKV, H); r.ks_o = ks(H, H); r.ks_g = r.step == 3 ? 0 : ks(2 * I, H); r.ks_d = ks(H, I);
+    r.nsplit = t.attn_decode_nsplit > 0 ? t.attn_decode_nsplit : std::max(1, std::min(16, (40 + B / 2) / B));
+    return r;
+}
 
 // Roofline probe (profile == 2): HIP events around ONE launch per step, layer 0's dominant kernel, for the scope this object lives in; `kind` says
 // which launch took the bracket (prof[8]).  Eager launches only: event-record nodes captured into a hipGraph do not yield usable timestamps on ROCm 7.2.
@@ -1301,13 +1307,14 @@ struct StepBracket {
     ~StepBracket() { if (e1) hipEventRecord(e1, s); }
 };
 
-// The decode attention of layer l.  fused: its prologue sums the qkv partial rows part [ks][SK_ROWS][QKV], applies RoPE and appends k / v to the cache;
-// otherwise dQKV holds ready q rows and the cache the new row (qkv_finish_layer ran).
-static int attn_decode_layer(trace_ctx* c, int l, bool fused, const float* part, int ks, hipStream_t s) {
+// The decode attention of layer l.  Without r.qkv_finish its prologue sums the qkv partial rows part [r.ks_q][SK_ROWS][QKV], applies RoPE and appends
+// k / v to the cache; otherwise dQKV holds ready q rows and the cache the new row (qkv_finish_layer ran).
+static int attn_decode_layer(trace_ctx* c, int l, const DecodeRoute& r, const float* part, hipStream_t s) {
+    const bool fused = !r.qkv_finish;
     return launch_attn_decode(c->dQKV, c->QKV, c->kcache + (size_t)l * c->layer_stride, c->vcache + (size_t)l * c->layer_stride, (long)c->slot_stride,
                               (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->dO, c->H, c->attn_ws, c->tickets, c->B, c->NQ, c->NKV, c->HD,
-                              decode_nsplit(c->B), 1.0f / sqrtf((float)c->HD), fused ? 1 : 0, fused ? c->rope_cos : nullptr, fused ? c->rope_sin : nullptr,
-                              fused ? part : nullptr, fused ? ks : 0, s);
+                              r.nsplit, 1.0f / sqrtf((float)c->HD), fused ? 1 : 0, fused ? c->rope_cos : nullptr, fused ? c->rope_sin : nullptr,
+                              fused ? part : nullptr, fused ? r.ks_q : 0, s);
 }
 // that prologue as a launch of its own: the qkv partial rows in sk_ws -> roped q rows in dQKV, k / v of layer l appended
 static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s) {
@@ -1321,12 +1328,10 @@ static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s) {
 // no combine kernel — and qkv / o / down cut along K into gemm_partial_ks() chunks whose fp32 partial rows the same consumers as below sum on
 // load.  The weights (14 GB per step) are then streamed once per 128 tokens instead of once per 64: bytes per token 0.50 -> 0.39 GB at
 // ctx ~2100, where the KV stream (0.27 GB per token) is the larger part.
-static int decode_step_wide(trace_ctx* c, float* logits_out, hipStream_t s) {
+static int decode_step_wide(trace_ctx* c, const DecodeRoute& r, float* logits_out, hipStream_t s) {
     const int H = c->H, I = c->I, HD = c->HD, QKV = c->QKV, B = c->B;
     if (c->fp8) return fail(TRACE_ERR_STATE, "the fp8 weight path decodes at most 64 sequences together");
-    const int ks_q = gemm_partial_ks(QKV, H), ks_o = gemm_partial_ks(H, H), ks_d = gemm_partial_ks(H, I);
     const int wt = g_tune.decode_gemm_tiled;
-    const bool fq = g_tune.decode_wide_fuse_qkv != 0;
     auto pgemm = [&](const bf16_t* A, int lda, const bf16_t* Wrow, const bf16_t* Wtile, int ldw, int N, int K, int ks) -> int {
         GemmArgs g{A, lda, (wt & 1) ? Wtile : Wrow, ldw, nullptr, 0, nullptr, nullptr, 0, B, N, K, nullptr, 0, nullptr, nullptr, 0, c->sk_ws, ks, (wt & 1) ? wt : 0};
         if ((size_t)ks * SK_ROWS * N > c->sk_ws_floats) return fail(TRACE_ERR_STATE, "partial-row workspace too small");
@@ -1335,20 +1340,20 @@ static int decode_step_wide(trace_ctx* c, float* logits_out, hipStream_t s) {
     LCHK(launch_rmsnorm(c->dX, H, c->dH, H, c->llm[0].rms1, B, H, c->c.rms_eps, s));
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
-        TRY(pgemm(c->dH, H, W.wqkv, W.wqkv_d, H, QKV, H, ks_q));
-        if (!fq) LCHK(qkv_finish_layer(c, l, ks_q, s));
+        TRY(pgemm(c->dH, H, W.wqkv, W.wqkv_d, H, QKV, H, r.ks_q));
+        if (r.qkv_finish) LCHK(qkv_finish_layer(c, l, r.ks_q, s));
         {   // bracketed: the layer-0 decode attention, which streams the batch's whole KV cache of that layer
             StepBracket br(c, l, 3, s);
             if (br.e1) c->kbytes_sum += (double)(c->pos_sum + (long)B * (c->step_in_call + 1)) * c->NKV * HD * 2 * 2;   // K + V^T rows of every sequence, bf16
-            LCHK(attn_decode_layer(c, l, fq, c->sk_ws, ks_q, s));
+            LCHK(attn_decode_layer(c, l, r, c->sk_ws, s));
         }
-        TRY(pgemm(c->dO, H, W.wo, W.wo_d, H, H, H, ks_o));
-        LCHK(launch_add_rmsnorm(c->sk_ws, ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s));
+        TRY(pgemm(c->dO, H, W.wo, W.wo_d, H, H, H, r.ks_o));
+        LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s));
         GemmArgs gu{c->dH, H, (wt & 1) ? W.wgu_d : W.wgu, H, c->dACT, I, nullptr, nullptr, 0, B, 2 * I, H, (wt & 1) ? nullptr : g_gemm_trace, 0, nullptr, nullptr, 0, nullptr, 0, (wt & 1) ? wt : 0};
         TRY(gemm_checked(gu, EPI_SWIGLU, s, "gate|up GEMM"));
-        TRY(pgemm(c->dACT, I, W.wd, W.wd_d, I, H, I, ks_d));
+        TRY(pgemm(c->dACT, I, W.wd, W.wd_d, I, H, I, r.ks_d));
         const bf16_t* nw = l + 1 < c->NL ? c->llm[l + 1].rms1 : c->final_norm;
-        LCHK(launch_add_rmsnorm(c->sk_ws, ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s));
+        LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s));
     }
     return head_and_select(c, c->dH, 1, logits_out, s);
 }
@@ -1360,47 +1365,41 @@ static int decode_step_wide(trace_ctx* c, float* logits_out, hipStream_t s) {
 //   -> gate|up GEMV [sums the o partials + residual, post-attention norm] -> down GEMV [sums the gate|up partials, SwiGLU]
 // Partial rows alternate between sk_ws (written by o / down, read by the fused GEMVs) and sk_ws2 (written by the fused GEMVs, read by the attention /
 // the combine); the residual rows alternate between dX and dX2 (a fused GEMV reads one and writes the other: its workgroups all read the whole row).
-static int decode_step_fused(trace_ctx* c, float* logits_out, hipStream_t s) {
+static int decode_step_fused(trace_ctx* c, const DecodeRoute& r, float* logits_out, hipStream_t s) {
     const int H = c->H, I = c->I, QKV = c->QKV, B = c->B;
-    const int ks_q = skinny_ks(QKV, H, EPI_PARTIAL, B), ks_o = skinny_ks(H, H, EPI_PARTIAL, B);
-    const int ks_g = skinny_ks(2 * I, H, EPI_PARTIAL, B), ks_d = skinny_ks(H, I, EPI_PARTIAL, B);
     bf16_t *xa = c->dX, *xb = c->dX2;             // current / next residual rows
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
-        LCHK(launch_skinny_gemm_fused_norm(l ? c->sk_ws : nullptr, l ? ks_d : 0, xa, H, xb, H, W.rms1, c->c.rms_eps, W.wqkv_d, B, QKV, H, c->sk_ws2,
+        LCHK(launch_skinny_gemm_fused_norm(l ? c->sk_ws : nullptr, l ? r.ks_d : 0, xa, H, xb, H, W.rms1, c->c.rms_eps, W.wqkv_d, B, QKV, H, c->sk_ws2,
                                            c->sk_ws_floats, s));
         std::swap(xa, xb);
-        LCHK(attn_decode_layer(c, l, true, c->sk_ws2, ks_q, s));
+        LCHK(attn_decode_layer(c, l, r, c->sk_ws2, s));
         LCHK(launch_skinny_gemm(c->dO, H, W.wo_d, H, nullptr, H, nullptr, 0, B, H, H, EPI_PARTIAL, 1, SKWS(c), s));
         {
             StepBracket br(c, l, 2, s);
-            LCHK(launch_skinny_gemm_fused_norm(c->sk_ws, ks_o, xa, H, xb, H, W.rms2, c->c.rms_eps, W.wgu_d, B, 2 * I, H, c->sk_ws2, c->sk_ws_floats, s));
+            LCHK(launch_skinny_gemm_fused_norm(c->sk_ws, r.ks_o, xa, H, xb, H, W.rms2, c->c.rms_eps, W.wgu_d, B, 2 * I, H, c->sk_ws2, c->sk_ws_floats, s));
         }
         std::swap(xa, xb);
         if (g_tune.decode_fuse_swiglu) {        // SwiGLU folded into the down GEMV's parking step (round 4, bit-identical to swiglu_combine + GEMV): 4 launches per layer
-            LCHK(launch_skinny_gemm_fused_swiglu(c->sk_ws2, ks_g, W.wd_d, B, H, I, c->sk_ws, c->sk_ws_floats, s));
+            LCHK(launch_skinny_gemm_fused_swiglu(c->sk_ws2, r.ks_g, W.wd_d, B, H, I, c->sk_ws, c->sk_ws_floats, s));
         } else {
-            LCHK(launch_swiglu_combine(c->sk_ws2, ks_g, 2 * I, c->dACT, I, B, s));
+            LCHK(launch_swiglu_combine(c->sk_ws2, r.ks_g, 2 * I, c->dACT, I, B, s));
             LCHK(launch_skinny_gemm(c->dACT, I, W.wd_d, I, nullptr, H, nullptr, 0, B, H, I, EPI_PARTIAL, 1, SKWS(c), s));
         }
     }
     // an even number of fused GEMVs: the residual rows are back in dX; the last layer's down partials + residual -> final norm -> heads
-    LCHK(launch_add_rmsnorm(c->sk_ws, ks_d, xa, H, xa, H, c->final_norm, c->dH, H, B, H, c->c.rms_eps, s));
+    LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_d, xa, H, xa, H, c->final_norm, c->dH, H, B, H, c->c.rms_eps, s));
     return head_and_select(c, c->dH, 1, logits_out, s);
 }
 
-// one decode step for the current batch: consumes dX (embedding of the last token), leaves the next one in dX
-static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
+// One decode step for up to SKINNY_ROWS sequences, on any kind of weights.
+static int decode_step_skinny(trace_ctx* c, const DecodeRoute& r, float* logits_out, hipStream_t s) {
     const int H = c->H, I = c->I, QKV = c->QKV, B = c->B;
-    if (B > SKINNY_ROWS || (B >= g_tune.decode_wide_min_rows && !c->fp8)) return decode_step_wide(c, logits_out, s);      // (fp8 contexts: at most 64 rows, checked at begin)
-    if (B <= g_tune.decode_fuse_norm_rows && !c->fp8 && skinny_fused_norm_ok(QKV, H, B) && skinny_fused_norm_ok(2 * I, H, B)) return decode_step_fused(c, logits_out, s);
     // Every GEMV leaves fp32 k-chunk partial rows in sk_ws and its consumer sums them on load (an in-kernel merge costs
     // 5-8 us of dependent round trips per GEMV): qkv -> attention (RoPE + cache append + attention) -> o -> [sum + residual
     // -> new residual, RMSNorm] -> gate|up -> [sum, SwiGLU] -> down -> [sum + residual, next layer's / the final RMSNorm].
-    const bool wo = c->fp8 && c->fp8_wonly;          // weight-only decode GEMVs: bf16 activations straight from dH / dO / dACT, no quantiser launches
-    const bool f8 = c->fp8 && !wo;
-    auto ksf = [&](int N, int K) { return wo ? skinny_w8_ks(N, K, B) : f8 ? skinny_fp8_ks(N, K, B) : skinny_ks(N, K, EPI_PARTIAL, B); };
-    const int ks_q = ksf(QKV, H), ks_o = ksf(H, H), ks_g = ksf(2 * I, H), ks_d = ksf(H, I);
+    const bool wo = r.kind == SK_W8A16;              // weight-only decode GEMVs: bf16 activations straight from dH / dO / dACT, no quantiser launches
+    const bool f8 = r.kind == SK_W8A8;
     // One projection of the step, X [B, K] -> partial rows in sk_ws, on the step's kind of weights: bf16 tile copies (Wd), or the e4m3 tile copy (W8d, scales
     // sw) with bf16 activations (weight-only) or with activations quantised row-wise first (quant_rows_fp8: [B, K] bf16 -> e4m3 + per-row scale).  The
     // normed hidden rows dH arrive already quantised (dH8 / dsh) from add_rmsnorm; only the step's first norm needs the quantiser.  Partial rows, their
@@ -1412,7 +1411,6 @@ static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
         const int rc = launch_quant_rows_fp8(X, K, c->dA8, K, c->dsa, B, K, s);
         return rc != TRACE_OK ? rc : launch_skinny_fp8(c->dA8, K, c->dsa, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
     };
-    const bool unfused = g_tune.decode_unfused_qkv == 1 || (g_tune.decode_unfused_qkv == 0 && B >= 32);
     LCHK(launch_rmsnorm(c->dX, H, c->dH, H, c->llm[0].rms1, B, H, c->c.rms_eps, s));
     if (f8) LCHK(launch_quant_rows_fp8(c->dH, H, c->dH8, H, c->dsh, B, H, s));
     for (int l = 0; l < c->NL; ++l) {
@@ -1420,22 +1418,28 @@ static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
         // (fusing the RMSNorm into the GEMV itself was tried: re-scaling the same activations in every workgroup cost
         //  more than a row kernel — 65 us vs 52 + 6 us for the gate|up GEMV)
         LCHK(gemv(c->dH, W.wqkv_d, W.wqkv8_d, W.sqkv, QKV, H));
-        if (unfused) LCHK(qkv_finish_layer(c, l, ks_q, s));
-        LCHK(attn_decode_layer(c, l, !unfused, c->sk_ws, ks_q, s));
+        if (r.qkv_finish) LCHK(qkv_finish_layer(c, l, r.ks_q, s));
+        LCHK(attn_decode_layer(c, l, r, c->sk_ws, s));
         LCHK(gemv(c->dO, W.wo_d, W.wo8_d, W.so, H, H));
-        LCHK(launch_add_rmsnorm(c->sk_ws, ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
+        LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
         {   // bracketed: the layer-0 gate|up GEMV (fp8: the bracket spans what the projection launches)
             StepBracket br(c, l, 1, s);
             LCHK(gemv(c->dH, W.wgu_d, W.wgu8_d, W.sgu, 2 * I, H));
         }
         // (SwiGLU inside the gate|up GEMV at batch <= 16 — one K chunk, no combine kernel — measured 3.73 vs 3.5 ms per batch-1 step: its 224
         //  workgroups leave 32 CUs without a weight stream)
-        LCHK(launch_swiglu_combine(c->sk_ws, ks_g, 2 * I, c->dACT, I, B, s));
+        LCHK(launch_swiglu_combine(c->sk_ws, r.ks_g, 2 * I, c->dACT, I, B, s));
         LCHK(gemv(c->dACT, W.wd_d, W.wd8_d, W.sd, H, I));
         const bf16_t* nw = l + 1 < c->NL ? c->llm[l + 1].rms1 : c->final_norm;
-        LCHK(launch_add_rmsnorm(c->sk_ws, ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
+        LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
     }
     return head_and_select(c, c->dH, 1, logits_out, s);
+}
+
+// one decode step for the current batch: consumes dX (embedding of the last token), leaves the next one in dX
+static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
+    const DecodeRoute r = decode_route(c->B, c->fp8 ? 1 + c->fp8_wonly : 0, c->H, c->I, c->QKV, g_tune);    // (fp8 contexts: at most 64 rows, checked at begin)
+    return r.step == 3 ? decode_step_wide(c, r, logits_out, s) : r.step == 2 ? decode_step_fused(c, r, logits_out, s) : decode_step_skinny(c, r, logits_out, s);
 }
 
 extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, const int32_t* heads, int max_new, int eos,
@@ -1759,10 +1763,25 @@ extern "C" int trace_op_skinny_gemm(const void* X, const void* W, void* out, con
     LCHK(launch_skinny_gemm((const bf16_t*)X, K, (const bf16_t*)W, K, (bf16_t*)out, No, (const bf16_t*)R, No, B, N, K, epilogue,
                             w_tiled, g_sk_ws, g_sk_ws_floats, g_sk_tk, g_sk_ntk, (hipStream_t)stream));
     if (epilogue == EPI_PARTIAL && out)
-        HIPCHK(hipMemcpyAsync(out, g_sk_ws, (size_t)skinny_ks(N, K, epilogue, B) * SK_ROWS * N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIPCHK(hipMemcpyAsync(out, g_sk_ws, (size_t)skinny_ks(SK_BF16, N, K, epilogue, B) * SK_ROWS * N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return TRACE_OK;
 }
-extern "C" int trace_op_skinny_ks(int N, int K, int epilogue, int B) { return skinny_ks(N, K, epilogue, B); }
+extern "C" int trace_op_skinny_ks(int N, int K, int epilogue, int B) { return skinny_ks(SK_BF16, N, K, epilogue, B); }
+extern "C" int trace_op_skinny_plan(int kind, int N, int K, int epilogue, int B, int64_t* out) {
+    if (!out || kind < SK_BF16 || kind > SK_W8A16 || !skinny_shape_ok((SkinnyKind)kind, N, K, epilogue, B)) return fail(TRACE_ERR_ARG, "the decode GEMV of this kind does not take this shape");
+    const SkinnyPlan p = skinny_plan((SkinnyKind)kind, N, K, epilogue, B);
+    const int64_t v[11] = {p.KS, p.chunk_units, p.T, p.WPT, p.ntiles, p.grid, p.threads, p.NT, p.NB, (int64_t)p.lds_bytes, (int64_t)skinny_partial_floats((SkinnyKind)kind, N, K)};
+    std::copy(v, v + 11, out);
+    return TRACE_OK;
+}
+extern "C" int trace_op_decode_route(int B, int fp8_scheme, int H, int I, int QKV, int32_t* out) {
+    if (!out || B < 1 || B > SK_ROWS || fp8_scheme < 0 || fp8_scheme > 2 || (fp8_scheme && B > SKINNY_ROWS)) return fail(TRACE_ERR_ARG, "bad batch or fp8 scheme");
+    if (H < 128 || I < 128 || QKV < 16) return fail(TRACE_ERR_ARG, "bad geometry");
+    const DecodeRoute r = decode_route(B, fp8_scheme, H, I, QKV, g_tune);
+    const int32_t v[8] = {r.step, (int32_t)r.kind, r.qkv_finish, r.ks_q, r.ks_o, r.ks_g, r.ks_d, r.nsplit};
+    std::copy(v, v + 8, out);
+    return TRACE_OK;
+}
 extern "C" int trace_op_sk_rows(void) { return SK_ROWS; }
 // gate|up of a wide decode step: X [M <= 128, K] . Wt (the 16-row interleaved gate|up matrix in the decode tile layout) -> SwiGLU -> out [M, N/2] bf16
 extern "C" int trace_op_gemm_swiglu_tiled(const void* X, const void* Wt, void* out, int M, int N, int K, int ring, void* stream) {
@@ -1791,7 +1810,7 @@ extern "C" int trace_op_gemm_fp8(const void* A8, const float* sa, const void* W8
 static int op_skinny_e4m3(const void* X, const float* sx, const void* W8, const float* sw, float* out, int B, int N, int K, hipStream_t s) {
     static uint8_t* wt = nullptr; static size_t wt_bytes = 0;
     static float* ws = nullptr; static size_t ws_floats = 0;
-    const int KS = sx ? skinny_fp8_ks(N, K, B) : skinny_w8_ks(N, K, B);
+    const int KS = skinny_ks(sx ? SK_W8A8 : SK_W8A16, N, K, EPI_PARTIAL, B);
     const size_t need_w = (size_t)N * K, need_ws = (size_t)KS * SK_ROWS * N;
     if (need_w > wt_bytes) { HIPCHK(hipDeviceSynchronize()); if (wt) hipFree(wt); HIPCHK(hipMalloc((void**)&wt, need_w)); wt_bytes = need_w; }
     if (need_ws > ws_floats) { HIPCHK(hipDeviceSynchronize()); if (ws) hipFree(ws); HIPCHK(hipMalloc((void**)&ws, need_ws * 4)); ws_floats = need_ws; }
@@ -1826,7 +1845,7 @@ extern "C" int trace_op_skinny_fused_norm(const float* part_in, int ks_in, const
     HIPCHK(hipMalloc((void**)&wt, (size_t)N * K * 2)); HIPCHK(hipMalloc((void**)&ws, wsf * 4));
     int rc = launch_tile_pack((const bf16_t*)W, K, wt, N, K, s);
     if (rc == TRACE_OK) rc = launch_skinny_gemm_fused_norm(part_in, ks_in, (const bf16_t*)R, K, (bf16_t*)xout, K, (const bf16_t*)w, eps, wt, B, N, K, ws, wsf, s);
-    if (rc == TRACE_OK && hipMemcpyAsync(out, ws, (size_t)skinny_ks(N, K, EPI_PARTIAL, B) * SK_ROWS * N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = TRACE_ERR_HIP;
+    if (rc == TRACE_OK && hipMemcpyAsync(out, ws, (size_t)skinny_ks(SK_BF16, N, K, EPI_PARTIAL, B) * SK_ROWS * N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = TRACE_ERR_HIP;
     hipStreamSynchronize(s);
     hipFree(wt); hipFree(ws);
     if (rc != TRACE_OK) return fail(rc, "fused-norm GEMV failed");

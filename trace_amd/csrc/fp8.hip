@@ -257,50 +257,12 @@ __global__ __launch_bounds__(512) void skinny_fp8_kernel(const uint8_t* __restri
     }   // task loop
 }
 
-struct Fp8Plan { int KS, chunk_units, T, WPT, ntiles, grid, threads, NT, NB; };
-int fp8_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-// same partition rule as decode.hip's skinny_plan, in 128-k units (a unit is the same 2 KB of weights per 16 rows)
-Fp8Plan fp8_plan(int N, int K, int B, bool wonly = false) {
-    Fp8Plan p{};
-    p.NT = (N >= 16384 && N % 32 == 0) ? 2 : 1;
-    p.NB = B > 32 ? 4 : B > 16 ? 2 : 1;
-    const int U = K / 128;
-    const int cap = (wonly ? 32 : 64) / p.NB;            // 128-k units of activations that fit 128 KB of LDS (bf16 rows: half as many)
-    const int ks_min = (U + cap - 1) / cap, ks_max = std::min(U, ks_min + 4);
-    p.ntiles = N / (16 * p.NT);
-    const int ncu = fp8_num_cus();
-    long best = -1;
-    for (int ks = ks_min; ks <= ks_max; ++ks) {
-        const int chunk = (U + ks - 1) / ks;
-        for (int T = 1; T <= 16; ++T) {
-            const int grid = ks * ((p.ntiles + T - 1) / T);
-            const long rounds = (grid + ncu - 1) / ncu;
-            const long cost = rounds * T * chunk * 64 + rounds * 8 + ks;
-            if (best < 0 || cost < best) { best = cost; p.KS = ks; p.chunk_units = chunk; p.T = T; p.grid = grid; }
-        }
-    }
-    p.WPT = 1;
-    while (p.WPT * 2 * p.T <= 8 && p.WPT * 2 * p.T * p.NT * p.NB <= 28 && p.WPT * 2 <= p.chunk_units) p.WPT *= 2;
-    p.threads = std::min(p.T, 8) * p.WPT * 64;
-    return p;
-}
-
 template <int NB, int NT, bool WONLY = false>
-int fp8_launch(const Fp8Plan& p, const uint8_t* X8, long ldx, const float* sx, const uint8_t* W, const float* sw, int B, int N, int K, float* ws,
+int fp8_launch(const SkinnyPlan& p, const uint8_t* X8, long ldx, const float* sx, const uint8_t* W, const float* sw, int B, int N, int K, float* ws,
                hipStream_t s) {
-    const size_t lds = (size_t)p.chunk_units * (WONLY ? 4 : 2) * NB * 1024 + (p.WPT > 1 ? (size_t)p.T * p.WPT * NT * NB * 1024 : 0);
     static LdsGrantSized grant;
-    if (!grant_dynamic_lds(grant, reinterpret_cast<const void*>(skinny_fp8_kernel<NB, NT, WONLY>), lds)) return TRACE_ERR_HIP;
-    hipLaunchKernelGGL((skinny_fp8_kernel<NB, NT, WONLY>), dim3(p.grid), dim3(p.threads), lds, s, X8, ldx, sx, W, sw, B, K, p.chunk_units, p.KS, p.T,
+    if (!grant_dynamic_lds(grant, reinterpret_cast<const void*>(skinny_fp8_kernel<NB, NT, WONLY>), p.lds_bytes)) return TRACE_ERR_HIP;
+    hipLaunchKernelGGL((skinny_fp8_kernel<NB, NT, WONLY>), dim3(p.grid), dim3(p.threads), p.lds_bytes, s, X8, ldx, sx, W, sw, B, K, p.chunk_units, p.KS, p.T,
                        p.WPT, p.ntiles, ws, N);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
@@ -319,32 +281,25 @@ int launch_tile_pack_fp8(const uint8_t* src, long ldw, uint8_t* dst, int N, int 
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
 
-int skinny_fp8_ks(int N, int K, int B) { return fp8_plan(N, K, B).KS; }
-int skinny_w8_ks(int N, int K, int B) { return fp8_plan(N, K, B, true).KS; }
-
-// the weight-only form: X bf16 [B][K] (ldx elements), e4m3 tile-layout weights + row scales; partial rows [skinny_w8_ks()][SK_ROWS][N]
+// The decode GEMV on e4m3 weights in the tile layout: partial rows [skinny_ks(kind, N, K, EPI_PARTIAL, B)][SK_ROWS][N] fp32 in ws, which the consumers of
+// decode.hip sum.  W8A8: X8 e4m3 rows (ldx bytes) with row scales sx.  Weight-only: X8 points at bf16 rows (ldx elements), sx is null.
+template <bool WONLY>
+static int fp8_gemv(const uint8_t* X8, long ldx, const float* sx, const uint8_t* Wtiled, const float* sw, int B, int N, int K, float* ws, size_t ws_floats,
+                    hipStream_t s) {
+    const SkinnyKind kind = WONLY ? SK_W8A16 : SK_W8A8;
+    if (!skinny_shape_ok(kind, N, K, EPI_PARTIAL, B) || (ldx % (WONLY ? 8 : 16))) return TRACE_ERR_ARG;
+    const SkinnyPlan p = skinny_plan(kind, N, K, EPI_PARTIAL, B);
+    if (!ws || ws_floats < (size_t)p.KS * SK_ROWS * N) return TRACE_ERR_ARG;
+    return skinny_by_nb(p.NB, [&](auto nb) {
+        return p.NT == 2 ? fp8_launch<decltype(nb)::value, 2, WONLY>(p, X8, ldx, sx, Wtiled, sw, B, N, K, ws, s)
+                         : fp8_launch<decltype(nb)::value, 1, WONLY>(p, X8, ldx, sx, Wtiled, sw, B, N, K, ws, s);
+    });
+}
 int launch_skinny_w8(const bf16_t* X, long ldx, const uint8_t* Wtiled, const float* sw, int B, int N, int K, float* ws, size_t ws_floats,
                      hipStream_t s) {
-    if (B < 1 || B > SKINNY_ROWS || K % 128 || N % 16 || (ldx % 8)) return TRACE_ERR_ARG;
-    const Fp8Plan p = fp8_plan(N, K, B, true);
-    if (!ws || ws_floats < (size_t)p.KS * SK_ROWS * N) return TRACE_ERR_ARG;
-    const uint8_t* X8 = reinterpret_cast<const uint8_t*>(X);
-#define WL(NT_) (B <= 16 ? fp8_launch<1, NT_, true>(p, X8, ldx, nullptr, Wtiled, sw, B, N, K, ws, s) \
-               : B <= 32 ? fp8_launch<2, NT_, true>(p, X8, ldx, nullptr, Wtiled, sw, B, N, K, ws, s) \
-                         : fp8_launch<4, NT_, true>(p, X8, ldx, nullptr, Wtiled, sw, B, N, K, ws, s))
-    return p.NT == 2 ? WL(2) : WL(1);
-#undef WL
+    return fp8_gemv<true>(reinterpret_cast<const uint8_t*>(X), ldx, nullptr, Wtiled, sw, B, N, K, ws, ws_floats, s);
 }
-
-// partial rows [skinny_fp8_ks()][SK_ROWS][N] fp32 in ws (>= KS * SK_ROWS * N floats): the consumers of decode.hip sum them
 int launch_skinny_fp8(const uint8_t* X8, long ldx, const float* sx, const uint8_t* Wtiled, const float* sw, int B, int N, int K, float* ws,
                       size_t ws_floats, hipStream_t s) {
-    if (B < 1 || B > SKINNY_ROWS || K % 128 || N % 16 || (ldx % 16)) return TRACE_ERR_ARG;
-    const Fp8Plan p = fp8_plan(N, K, B);
-    if (!ws || ws_floats < (size_t)p.KS * SK_ROWS * N) return TRACE_ERR_ARG;
-#define FL(NT_) (B <= 16 ? fp8_launch<1, NT_>(p, X8, ldx, sx, Wtiled, sw, B, N, K, ws, s) \
-               : B <= 32 ? fp8_launch<2, NT_>(p, X8, ldx, sx, Wtiled, sw, B, N, K, ws, s) \
-                         : fp8_launch<4, NT_>(p, X8, ldx, sx, Wtiled, sw, B, N, K, ws, s))
-    return p.NT == 2 ? FL(2) : FL(1);
-#undef FL
+    return fp8_gemv<false>(X8, ldx, sx, Wtiled, sw, B, N, K, ws, ws_floats, s);
 }

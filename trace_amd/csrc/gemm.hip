@@ -396,7 +396,7 @@ static int launch_dec(const GemmArgs& p, int nblk, hipStream_t s) {
 // Tile shape of the partial-row GEMM (decode.partial_cfg): 0 = 128 x 128 on 2 x 2 waves, 4-stage ring (round 3); 1 / 2 / 3 = 128 x 64 on
 // 4 x 1 waves with a 5- / 3- / 4-stage ring (24 KB stages: half the partial-row bytes per product at the same number of workgroups, K loops twice as long;
 // the 3-stage form fits two workgroups per CU)
-static int partial_bn() { return g_tune.decode_partial_cfg ? 64 : 128; }
+static int partial_bn(const Tuning& t = g_tune) { return t.decode_partial_cfg ? 64 : 128; }
 static int launch_partial(const GemmArgs& p, hipStream_t s) {
     const int bn = (p.w_tiled & 1) ? partial_bn() : 128;
     if (p.M < 1 || p.M > SK_ROWS || p.N % bn || p.K % BK || p.fp8 || !p.part || p.ks < 1 || (p.K / BK) % p.ks) return TRACE_ERR_ARG;
@@ -418,9 +418,9 @@ static int launch_swiglu_tiled(const GemmArgs& p, hipStream_t s) {
 // in one round instead of 8 = 384 in one and a half, with half the partial-row bytes; o / down (32 tiles) keep 8 chunks = 256.  Wide step, ms per 128-sequence step at
 // ctx 1968 (profiles/r06_decode_splitk_ab.txt): target 256 11.01, 192 10.59, 160 10.41 (= 192), 128 (o / down at 4 chunks) 10.72, 96 10.96, 64 12.27.
 // decode.partial_wgs is the workgroup target (TRACE_PARTIAL_WGS sets its initial value: tuning runs); 0 = that initial value.
-int gemm_partial_ks(int N, int K) {
-    const int target = g_tune.decode_partial_wgs > 0 ? g_tune.decode_partial_wgs : tuning_initial().decode_partial_wgs;
-    const int tiles = N / partial_bn(), nk = K / BK;
+int gemm_partial_ks(int N, int K, const Tuning& t) {
+    const int target = t.decode_partial_wgs > 0 ? t.decode_partial_wgs : tuning_initial().decode_partial_wgs;
+    const int tiles = N / partial_bn(t), nk = K / BK;
     int ks = 1;
     while (tiles * ks < target && nk % (ks * 2) == 0 && nk / (ks * 2) >= 4) ks *= 2;
     return ks;

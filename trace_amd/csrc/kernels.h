@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <type_traits>
 #include "common.h"
 #include "tuning.h"
 
@@ -63,7 +64,7 @@ enum GemmKernel { GK_GLDS128, GK_GLDS256, GK_LDR, GK_PERS, GK_W4 };
 struct GemmRoute { GemmKernel k; int walk; };                     // 0 = ticketed, 1 = static deal, 2 = one workgroup per tile (gemm_pers only)
 bool gemm_shape_ok(const GemmArgs& p, int epi);                   // false: launch_gemm_bf16 answers TRACE_ERR_ARG
 GemmRoute gemm_route(const GemmArgs& p, int epi, const Tuning& t);
-int gemm_partial_ks(int N, int K);                                // K-chunks launch_gemm_bf16(EPI_PARTIAL) should be given for an [<= 128, K] x [N, K]^T product
+int gemm_partial_ks(int N, int K, const Tuning& t = g_tune);                             // K-chunks launch_gemm_bf16(EPI_PARTIAL) should be given for an [<= 128, K] x [N, K]^T product
 int launch_gemm_ldr(const GemmArgs& p, int epi, hipStream_t s);    // gemm_ldr.hip: 256x256 tiles, 8 MFMA + 4 loader waves (N % 256 == 0)
 int launch_gemm_pers(const GemmArgs& p, int epi, int walk, hipStream_t s);   // gemm_pers.hip: the same tile, persistent workgroups, register epilogue (bf16, K >= 128)
 int launch_gemm_w4(const GemmArgs& p, int epi, int walk, hipStream_t s);     // gemm_w4.hip: the persistent 256x256 tile on 4 waves of 128x128 (bf16, K >= 192)
@@ -157,10 +158,24 @@ int launch_kv_copy(bf16_t* kcache, bf16_t* vtcache, long layer_stride, long slot
                    int kv_heads, int src, const KvCopyDst& dst, int rows, hipStream_t s);
 
 // ---- decode (decode.hip) ----
+// The decode GEMVs by operand kind: bf16 weights and activations (launch_skinny_gemm*), e4m3 weights with e4m3 or with bf16 activations (fp8.hip).
+enum SkinnyKind { SK_BF16 = 0, SK_W8A8 = 1, SK_W8A16 = 2 };
+// How one GEMV is cut into workgroups (decode.hip skinny_plan_nb): KS k-chunks of chunk_units units, `grid` workgroups of `threads` threads that take T
+// tiles of 16 NT output rows with WPT waves a tile, NB 16-row activation groups, lds_bytes of dynamic LDS (2 activation images per unit and row group
+// for SK_BF16 / SK_W8A8, 4 for SK_W8A16, + the reduction scratch of WPT > 1).  The fp8 kinds take EPI_PARTIAL only.
+struct SkinnyPlan { int KS, chunk_units, T, WPT, ntiles, grid, threads, NT, NB; size_t lds_bytes; };
+bool skinny_shape_ok(SkinnyKind kind, int N, int K, int epi, int B);     // false: the kind's launcher answers TRACE_ERR_ARG
+SkinnyPlan skinny_plan(SkinnyKind kind, int N, int K, int epi, int B);
+int skinny_ks(SkinnyKind kind, int N, int K, int epi, int B);            // the plan's KS
+size_t skinny_partial_floats(SkinnyKind kind, int N, int K);             // KS * SK_ROWS * N of the EPI_PARTIAL plan, largest over the batch classes B <= 16, <= 32, <= 64
+int skinny_num_cus();                                                    // CUs of the current device, 256 (the MI355X's) when none answers
+// f(std::integral_constant<int, NB>): the launchers' row-group template argument from a plan's NB
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F> int skinny_by_nb(int NB, F f) { return NB == 1 ? f(IntC<1>{}) : NB == 2 ? f(IntC<2>{}) : f(IntC<4>{}); }
 // out[b, n] = sum_k X[b,k] W[n,k]  (B <= 64) (+ residual / SwiGLU on interleaved W)
 // tiled: W is the decode copy made by launch_tile_pack ([N/16][K/64][64][16]); else row-major [N][ldw].
 // ws / tickets: workspace of skinny_ws_floats(N, K, epi) floats and >= N/16 zero-initialised tickets.
-// EPI_PARTIAL: no bf16 output; fp32 partial rows [skinny_ks(N, K, epi, B)][SK_ROWS][N] in ws, summed by launch_add_rmsnorm.
+// EPI_PARTIAL: no bf16 output; fp32 partial rows [skinny_ks(SK_BF16, N, K, epi, B)][SK_ROWS][N] in ws, summed by launch_add_rmsnorm.
 int launch_skinny_gemm(const bf16_t* X, int ldx, const bf16_t* W, int ldw, bf16_t* out, int ldo, const bf16_t* R,
                        int ldr, int B, int N, int K, int epi, int tiled, float* ws, size_t ws_floats, unsigned int* tickets,
                        int ntickets, hipStream_t s);
@@ -171,8 +186,7 @@ int launch_skinny_gemm_fused_norm(const float* part_in, int ks_in, const bf16_t*
 // the down GEMV fed by the gate|up GEMV's partial rows [ks_gu][SK_ROWS][2 K]: SwiGLU (swiglu_combine's arithmetic) folded into its parking step (B <= 4)
 int launch_skinny_gemm_fused_swiglu(const float* part_gu, int ks_gu, const bf16_t* Wtiled, int B, int N, int K, float* ws, size_t ws_floats, hipStream_t s);
 bool skinny_fused_norm_ok(int N, int K, int B);      // false: this shape keeps the GEMV + add_rmsnorm pair
-size_t skinny_ws_floats(int N, int K, int epi);
-int skinny_ks(int N, int K, int epi, int B);
+size_t skinny_ws_floats(int N, int K, int epi);      // SK_BF16, any B: the partial rows of EPI_PARTIAL, else what the ticket merge parks
 int launch_tile_pack(const bf16_t* src, int ldw, bf16_t* dst, int N, int K, hipStream_t s);
 // out[b][j] = bf16(silu(sum_ks gate) * sum_ks up) over EPI_PARTIAL rows [KS][SK_ROWS][N2] of the 16-row interleaved gate|up product
 int launch_swiglu_combine(const float* part, int KS, int N2, bf16_t* out, int ldo, int B, hipStream_t s);
@@ -227,15 +241,13 @@ int launch_step_logprob(const float* logits, const StepState& st, int B, int V, 
 int launch_quant_rows_fp8(const bf16_t* X, long ldx, uint8_t* X8, long ld8, float* sx, int rows, int K, hipStream_t s);
 // W8 [N][K] bytes -> decode copy [N/16][K/128][64 lanes][32 B]
 int launch_tile_pack_fp8(const uint8_t* src, long ldw, uint8_t* dst, int N, int K, hipStream_t s);
-// decode GEMV on fp8 operands: fp32 partial rows [skinny_fp8_ks(N,K,B)][SK_ROWS][N] = (X8 . W8^T) * sx[m] * sw[n] in ws
+// decode GEMV on fp8 operands: fp32 partial rows [skinny_ks(SK_W8A8,N,K,EPI_PARTIAL,B)][SK_ROWS][N] = (X8 . W8^T) * sx[m] * sw[n] in ws
 int launch_skinny_fp8(const uint8_t* X8, long ldx, const float* sx, const uint8_t* Wtiled, const float* sw, int B, int N, int K, float* ws,
                       size_t ws_floats, hipStream_t s);
-int skinny_fp8_ks(int N, int K, int B);
 // weight-only (W8A16) form of the same GEMV: bf16 activations, e4m3 weights widened to bf16 in registers, bf16 MFMA; partial rows
-// [skinny_w8_ks(N,K,B)][SK_ROWS][N] = (X . W8^T) * sw[n]
+// [skinny_ks(SK_W8A16,N,K,EPI_PARTIAL,B)][SK_ROWS][N] = (X . W8^T) * sw[n]
 int launch_skinny_w8(const bf16_t* X, long ldx, const uint8_t* Wtiled, const float* sw, int B, int N, int K, float* ws, size_t ws_floats,
                      hipStream_t s);
-int skinny_w8_ks(int N, int K, int B);
 
 // ---- STC connector support (stc.hip): channels-last [n][h][w][C] row kernels ----
 int launch_dwconv3x3(const bf16_t* x, const bf16_t* w /*[C][9]*/, bf16_t* y, int N, int H, int W, int C, hipStream_t s);

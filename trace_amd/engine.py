@@ -954,6 +954,20 @@ class ops:
         return _lib.load(ops.element).trace_op_skinny_ks(N, K, epilogue, B)
 
     @staticmethod
+    def skinny_plan(kind, N, K, epilogue, B) -> dict:
+        """trace_op_skinny_plan: the workgroup partition of one decode GEMV (kind 0 bf16, 1 W8A8, 2 W8A16) and its partial-row floats"""
+        out = (C.c_int64 * 11)()
+        _lib.check(_lib.load(ops.element).trace_op_skinny_plan(kind, N, K, epilogue, B, out))
+        return dict(zip(("KS", "chunk_units", "T", "WPT", "ntiles", "grid", "threads", "NT", "NB", "lds_bytes", "partial_floats"), out))
+
+    @staticmethod
+    def decode_route(B, fp8_scheme, H, I, QKV) -> dict:
+        """trace_op_decode_route: what a decode step of B sequences does under the current tuning values ('step' = get_profile()[8])"""
+        out = (C.c_int32 * 8)()
+        _lib.check(_lib.load(ops.element).trace_op_decode_route(B, fp8_scheme, H, I, QKV, out))
+        return dict(zip(("step", "kind", "qkv_finish", "ks_q", "ks_o", "ks_g", "ks_d", "nsplit"), out))
+
+    @staticmethod
     def swiglu_combine(part, Bn):
         lib = _lib.load(ops.element)
         N2 = part.shape[2]
