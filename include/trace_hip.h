@@ -197,6 +197,29 @@ int trace_decode_set_sampling(trace_ctx* ctx, float temperature, int top_k, floa
 int trace_decode_set_logprobs(trace_ctx* ctx, int on);
 int trace_decode_read_logprobs(trace_ctx* ctx, float* out, void* stream);
 
+/* Logits processors (generate(repetition_penalty=, no_repeat_ngram_size=, min_new_tokens=): HF RepetitionPenaltyLogitsProcessor ->
+ * NoRepeatNGramLogitsProcessor -> MinNewTokensLengthLogitsProcessor, transformers 4.40.1), on the device inside the decode step.  Set before
+ * trace_decode_begin; it holds for every later batch until changed (like trace_decode_set_sampling); (1.0, 0, 0) disarms it.  The first arming call
+ * allocates the processed-logits rows, and the masked-logits rows if nothing has allocated them yet.  For row b at device step s (0 = the token of
+ * trace_decode_begin), with [lo, hi) the id range of the row's active head and x its masked fp32 logits as the head stage writes them:
+ *   history h = the ids the row has recorded so far, out_ids[b][0 .. out_len[b]).  The prompt is NOT part of it (the reference hands HF
+ *     inputs_embeds, so HF's processors see the generated ids only).  Ids are global vocabulary ids [text | <sync> | time | score]: a time digit
+ *     emitted in one time span is penalised / banned in a later one as well, as HF does on the reference.  Ids of h outside [lo, hi) touch nothing.
+ *   1. repetition_penalty p (> 0, finite; 1.0 = off; p < 1 rewards): for every DISTINCT id t of h: x[t] = x[t] < 0 ? x[t] * p : x[t] / p — one fp32
+ *      multiply or one true fp32 division of the raw value, once per id however often it occurs; -inf stays -inf, 0 stays 0;
+ *   2. no_repeat_ngram_size n (0 = off, 1..64): if len(h) + 1 >= n, for every i in [0, len(h) - n] with h[i .. i+n-2] == h[len(h)-n+1 .. len(h)-1]:
+ *      x[h[i+n-1]] = -inf (n = 1 bans every id of h);
+ *   3. min_new_tokens m (0 = off): while s < m and eos >= 0: x[eos] = -inf, eos the one given to trace_decode_begin.
+ * The three rules are independent and commute.  The token is then selected from the processed row: the arg-max with the lowest id among equal
+ * maxima, or the sampler above.  If every id of the head ends up banned, greedy emits the head's lowest id; under sampling that case is unspecified.
+ * Log-probabilities (trace_decode_set_logprobs) stay what they were: they describe the RAW row, the model's own distribution — the processed row
+ * lives in a buffer of its own.  Rows that are done keep stepping; nothing is recorded for them.  With the setting off a decode batch issues the
+ * launches and replays the graphs it did before (steps with the extra launch are cached apart); the params live in device memory, so a captured
+ * step stays valid when they change between batches.  Host-select mode (trace_decode_host_mode) ignores the setting: the host holds the logits and
+ * calls trace_op_logits_process on them.  TRACE_ERR_ARG: p <= 0 or not finite, n outside 0..64, m < 0; and, at trace_decode_begin, an armed
+ * setting together with forced != NULL (the history is the recorded ids, which under forced ids are not the fed ones). */
+int trace_decode_set_logits_params(trace_ctx* ctx, float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens);
+
 /* Two-stage pipeline support (trace/eval/evaluate.py:298-417 loops over independent videos: while one batch decodes — HBM-bound —
  * the next batch's ViT + prefill — MFMA-bound — can run on another stream into other KV slots; the stages share no buffers).
  * trace_stream_create: a HIP stream confined to cu_count CUs starting at logical CU cu_first (hipExtStreamCreateWithCUMask; mask bit i
@@ -304,6 +327,14 @@ int trace_op_sample(const float* logits, int ld, int B, const int32_t* heads, in
  * int32 [B] device (active head, global vocabulary id), out fp32 [B] device; an id outside the head's range gives -inf. */
 int trace_op_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out,
                            void* stream);
+/* The logits processors above over loose rows, the same device code (tests; the host-driven decode loop): logits [B][ld] fp32 device (ld >= V+1+Tv+Sv;
+ * only the head's range is read), heads / hist_len / steps int32 [B] device (active head, history length, device step), hist int32 [B][ld_hist]
+ * device (row b's history = hist[b][0 .. hist_len[b]), lengths clamped to [0, ld_hist]), eos as trace_decode_begin takes it.  out fp32 [B][ld]
+ * device, may not alias logits: the processed values on the head's range, -inf everywhere else of [0, V+1+Tv+Sv).  trace_amd/sampling.py
+ * process_row_ref restates a row in float32 bit for bit. */
+int trace_op_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
+                            const int32_t* hist_len, const int32_t* steps, int eos, float repetition_penalty, int no_repeat_ngram_size,
+                            int min_new_tokens, float* out, void* stream);
 /* Single-query decode attention over loose caches (head_dim 128, nq == 4 nkv, nkv <= 64, max_ctx % 32 == 0): kcache [B][nkv][max_ctx][128],
  * vtcache [B][nkv][128][max_ctx] (V transposed), row b in slot b; pos[b] (device) = index of the newest token, already in the caches (ctx = pos + 1);
  * q [B][nq * 128] ready (rotated) -> O [B][nq * 128]; ws: B * nq * nsplit * 130 floats.  Cache positions past pos[b] inside a 32-position block are

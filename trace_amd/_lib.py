@@ -61,6 +61,7 @@ SIGNATURES = {
     "trace_decode_set_sampling": (I, [P, F, I, F, C.c_uint64]),
     "trace_decode_set_logprobs": (I, [P, I]),
     "trace_decode_read_logprobs": (I, [P, P, P]),
+    "trace_decode_set_logits_params": (I, [P, F, I, I]),
     "trace_stream_create": (I, [P, I, I, C.POINTER(P)]),
     "trace_stream_destroy": (I, [P, P]),
     "trace_set_gemm_cus": (I, [P, I]),
@@ -97,6 +98,7 @@ SIGNATURES = {
     "trace_op_add_rmsnorm": (I, [P, I, P, P, P, P, I, I, F, P]),
     "trace_op_sample": (I, [P, I, I, P, I, I, I, F, I, F, C.c_uint64, P, P, P]),
     "trace_op_token_logprob": (I, [P, I, I, P, I, I, I, P, P, P]),
+    "trace_op_logits_process": (I, [P, I, I, P, I, I, I, P, I, P, P, I, F, I, I, P, P]),
     "trace_op_attn_decode": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
     "trace_op_qkv_finish": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "trace_op_attn_decode_fused": (I, [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P]),

@@ -18,6 +18,7 @@
 #include "../../include/trace_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "logits.h"
 #include "sample.h"
 
 static thread_local std::string g_err;
@@ -125,6 +126,14 @@ struct trace_ctx {
     // (rows of the current batch at stride max_new), written by the launch after the selection from the same d_slog rows
     int lp_set = 0, lp_on = 0;
     float* d_logprobs = nullptr;
+    // logits processors (trace_decode_set_logits_params): armed at trace_decode_begin like the sampling; the device copy d_lgparams is what
+    // logits_process_kernel reads, d_plog the [SK_ROWS][NV] processed rows the selection then reads (d_slog stays raw: the log-probabilities' rows).
+    // graphs_logits[sampling + 2 * logprobs]: steps with the extra launch are cached apart, so a disarmed batch replays the graphs it always did
+    LogitsParams lgp{1.f, 0, 0};
+    int lgp_set = 0, lgp_on = 0;
+    LogitsParams* d_lgparams = nullptr;
+    float* d_plog = nullptr;
+    hipGraphExec_t graphs_logits[4][SK_ROWS + 1] = {{nullptr}};
     hipStream_t cap_stream = nullptr;
     std::vector<hipStream_t> streams;   // trace_stream_create
     // profiling
@@ -415,7 +424,7 @@ extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ct
     // trace_llm_head_logits: its own arg-max partials and three constant head-id rows (all 0 / all 1 / all 2), so that it shares nothing with a
     // decode batch in flight on another stream and needs no host copy or synchronisation per call
     A(c->hl_val, (size_t)SK_ROWS * c->ntiles); A(c->hl_idx, (size_t)SK_ROWS * c->ntiles);
-    A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4); A(c->d_sparams, 1);
+    A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4); A(c->d_sparams, 1); A(c->d_lgparams, 1);
     A(c->d_out_ids, (size_t)SK_ROWS * cfg->max_new_tokens); A(c->d_forced, (size_t)SK_ROWS * cfg->max_new_tokens);
 #undef A
     if (rc == TRACE_OK && hipHostMalloc((void**)&c->h_ring, Lm * 8 * trace_ctx::NSTAGE_H) != hipSuccess) rc = fail(TRACE_ERR_HIP, "hipHostMalloc");
@@ -444,6 +453,7 @@ extern "C" int trace_ctx_destroy(trace_ctx* c) {
     for (auto& g : c->graphs_sample) if (g) hipGraphExecDestroy(g);
     for (auto& g : c->graphs_lp) if (g) hipGraphExecDestroy(g);
     for (auto& g : c->graphs_sample_lp) if (g) hipGraphExecDestroy(g);
+    for (auto& row : c->graphs_logits) for (auto& g : row) if (g) hipGraphExecDestroy(g);
     for (auto& e : c->kev) if (e) hipEventDestroy(e);
     for (auto& e : c->vev) if (e) hipEventDestroy(e);
     if (c->mev0) hipEventDestroy(c->mev0);
@@ -1263,9 +1273,16 @@ static int select_only(trace_ctx* c, int advance, hipStream_t s, const float* sa
 }
 static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* logits_out, hipStream_t s) {
     // sampling / log-probabilities: both read the masked logits rows the head kernel writes (the caller's logits_out, else d_slog)
-    float* lg = (c->samp_on || c->lp_on) && !c->host_mode && !logits_out ? c->d_slog : logits_out;
+    float* lg = (c->samp_on || c->lp_on || c->lgp_on) && !c->host_mode && !logits_out ? c->d_slog : logits_out;
     TRY(head_only(c, xn, lg, s));
     if (c->host_mode) return TRACE_OK;      // the host picks the token and calls trace_decode_feed
+    if (c->lgp_on) {
+        // logits processors: the raw rows -> d_plog, and the selection (sampled, or the arg-max over the row) reads d_plog; lg stays raw for the launch below
+        LCHK(launch_step_logits_process(lg, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_lgparams, c->d_plog, s));
+        if (c->samp_on) TRY(select_only(c, advance, s, c->d_plog));
+        else LCHK(launch_select_row(c->d_plog, step_state(c), c->embed, c->time_tab, c->score_tab, c->sync_row, c->dX, c->H, c->B, c->H, c->V, c->Tv, c->Sv,
+                                    advance, s));
+    } else
     TRY(select_only(c, advance, s, c->samp_on ? lg : nullptr));
     // the log-probability of the token just recorded: after the selection (it reads out_ids / out_len / the advanced step counter), from the same rows
     if (c->lp_on) LCHK(launch_step_logprob(lg, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_logprobs, s));
@@ -1456,6 +1473,8 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
         if (pos[b] + max_new > c->max_ctx) return fail(TRACE_ERR_ARG, "prefill + max_new_tokens exceeds max_ctx");
         for (int b2 = 0; b2 < b; ++b2) if (slots[b2] == slots[b]) return fail(TRACE_ERR_ARG, "duplicate slot");
     }
+    if (forced && c->lgp_set && !c->host_mode)
+        return fail(TRACE_ERR_ARG, "logits processors (trace_decode_set_logits_params) with forced ids: the history is the recorded ids, not the fed ones");
     c->B = B; c->max_new = max_new; c->eos = eos; c->has_forced = forced != nullptr;
     c->pos_sum = 0;
     for (int b = 0; b < B; ++b) c->pos_sum += pos[b];
@@ -1472,6 +1491,8 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     if (c->samp_on) HIPCHK(hipMemcpyAsync(c->d_sparams, &c->samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     c->lp_on = c->lp_set && !c->host_mode;         // host-select mode: the host has the logits and calls trace_op_token_logprob on them
     if (c->lp_on) HIPCHK(hipMemsetAsync(c->d_logprobs, 0, (size_t)B * max_new * 4, s));    // entries past a row's length stay 0.0
+    c->lgp_on = c->lgp_set && !c->host_mode;       // host-select mode: the host holds the logits and calls trace_op_logits_process on them
+    if (c->lgp_on) HIPCHK(hipMemcpyAsync(c->d_lgparams, &c->lgp, sizeof(LogitsParams), hipMemcpyHostToDevice, s));
     c->fed = 0; c->steps_done = 0;
     if (forced) HIPCHK(hipMemcpyAsync(c->d_forced, forced, (size_t)B * max_new * 4, hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemsetAsync(c->d_forced, 0xff, (size_t)B * max_new * 4, s));      // -1 = not forced
@@ -1499,7 +1520,8 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
         for (int i = 0; i < n; ++i) { c->step_in_call = steps_before + i; TRY(decode_step(c, logits_out, s)); }
     } else {
         const int key = c->B;
-        hipGraphExec_t* slot_g = c->lp_on ? (c->samp_on ? &c->graphs_sample_lp[key] : &c->graphs_lp[key])
+        hipGraphExec_t* slot_g = c->lgp_on ? &c->graphs_logits[(c->samp_on ? 1 : 0) + (c->lp_on ? 2 : 0)][key]
+                               : c->lp_on ? (c->samp_on ? &c->graphs_sample_lp[key] : &c->graphs_lp[key])
                                           : (c->samp_on ? &c->graphs_sample[key] : &c->graphs[key]);
         if (!*slot_g) {
             hipGraph_t g = nullptr;
@@ -1584,6 +1606,37 @@ extern "C" int trace_decode_set_logprobs(trace_ctx* c, int on) {
         if (!c->d_logprobs) TRY(dalloc(c, &c->d_logprobs, (size_t)SK_ROWS * c->c.max_new_tokens));
     }
     c->lp_set = on ? 1 : 0;
+    return TRACE_OK;
+}
+
+static const char* logits_params_bad(float p, int n, int m) {
+    if (!(p > 0.f) || !std::isfinite(p)) return "repetition_penalty must be a finite number > 0";
+    if (n < 0 || n > LOGITS_MAX_NGRAM) return "no_repeat_ngram_size must lie in [0, 64]";
+    if (m < 0) return "min_new_tokens must not be negative";
+    return nullptr;
+}
+
+extern "C" int trace_decode_set_logits_params(trace_ctx* c, float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (const char* m = logits_params_bad(repetition_penalty, no_repeat_ngram_size, min_new_tokens)) return fail(TRACE_ERR_ARG, m);
+    c->lgp = LogitsParams{repetition_penalty, no_repeat_ngram_size, min_new_tokens};
+    c->lgp_set = repetition_penalty != 1.f || no_repeat_ngram_size != 0 || min_new_tokens != 0;
+    if (c->lgp_set) {
+        if (!c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
+        if (!c->d_plog) TRY(dalloc(c, &c->d_plog, (size_t)SK_ROWS * c->NV));
+    }
+    return TRACE_OK;
+}
+
+extern "C" int trace_op_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
+                                       const int32_t* hist_len, const int32_t* steps, int eos, float repetition_penalty, int no_repeat_ngram_size,
+                                       int min_new_tokens, float* out, void* stream) {
+    if (!logits || !heads || !hist || !hist_len || !steps || !out) return fail(TRACE_ERR_ARG, "null pointer");
+    if (out == logits) return fail(TRACE_ERR_ARG, "out may not alias logits");
+    if (const char* m = logits_params_bad(repetition_penalty, no_repeat_ngram_size, min_new_tokens)) return fail(TRACE_ERR_ARG, m);
+    const int rc = launch_logits_process(logits, ld, B, heads, V, Tv, Sv, hist, ld_hist, hist_len, steps, eos,
+                                         LogitsParams{repetition_penalty, no_repeat_ngram_size, min_new_tokens}, out, ld, (hipStream_t)stream);
+    if (rc != TRACE_OK) return fail(rc, "logits_process launch failed (B, ld, ld_hist or head widths out of range)");
     return TRACE_OK;
 }
 

@@ -235,6 +235,16 @@ int launch_sample_rows(const float* logits, int ld, int B, const int32_t* heads,
 // kernel wrote for this step [B][NV]; writes out_logprobs[b][step] ([B][max_new]) where select_next recorded a token in this step.
 int launch_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out, hipStream_t s);
 int launch_step_logprob(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, float* out_logprobs, hipStream_t s);
+// logits processors (logits.h: repetition penalty, no-repeat n-grams, min_new_tokens) from a row of masked logits into a row of their own.
+// Loose rows: hist int32 [B][ld_hist] / hist_len / heads / steps int32 [B] (device), out [B][ldo] written whole, -inf outside the head
+// (trace_op_logits_process).  Decode step: between launch_head_logits and the selection of the same step, history = st.out_ids / st.out_len,
+// params *dlp (device), rows [B][NV] -> [B][NV] (the head's range only).  launch_select_row: launch_select_next's greedy form over such rows.
+struct LogitsParams;   // logits.h
+int launch_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
+                          const int32_t* hist_len, const int32_t* steps, int eos, const LogitsParams& lp, float* out, int ldo, hipStream_t s);
+int launch_step_logits_process(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, const LogitsParams* dlp, float* out, hipStream_t s);
+int launch_select_row(const float* logits, const StepState& st, const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab,
+                      const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H, int V, int Tv, int Sv, int advance, hipStream_t s);
 
 // ---- fp8 (e4m3) weight path of the decoder (fp8.hip; the fp8 GEMM is launch_gemm_bf16 with GemmArgs::fp8 set) ----
 // X bf16 [rows][K] -> X8 e4m3 [rows][K] + sx[row] = amax/448 (per-row dynamic scale).  Also used row-wise on weight matrices at load.

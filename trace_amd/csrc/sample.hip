@@ -1,5 +1,5 @@
 // trace_op_sample: the device sampler (sample.h) over loose rows of masked head logits — the kernel-level entry of the tests and the sampler of
-// the host-driven (stopping-criteria) decode loop.  The decode step itself samples inside select_next_kernel<true> (decode.hip): the same
+// the host-driven (stopping-criteria) decode loop.  The decode step itself samples inside select_next_kernel<SELECT_SAMPLE> (decode.hip): the same
 // sample_row, so both paths pick the same id from the same row, params, step and row index.
 #include "common.h"
 #include "kernels.h"

@@ -13,7 +13,7 @@ from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
 from .prefix import APPEND_GROUP_MAX, group_by_length, split_questions
-from .sampling import SamplingParams, sample_rows_host
+from .sampling import LogitsParams, SamplingParams, sample_rows_host
 
 __all__ = ["TraceEngine", "SamplingParams", "ops"]
 
@@ -461,6 +461,22 @@ class TraceEngine:
             _lib.check(self.lib.trace_decode_set_sampling(self.h, float(sampling.temperature), int(sampling.top_k), float(sampling.top_p),
                                                           int(sampling.seed)))
 
+    def set_logits_params(self, logits: Optional[LogitsParams]):
+        """Logits processors for the decode batches begun from now on (trace_decode_set_logits_params): repetition penalty, no-repeat n-grams and
+        min_new_tokens over the ids a row has generated so far, applied on the device between the head logits and the token selection.  None or
+        LogitsParams() disarms them."""
+        lp = logits if logits is not None else LogitsParams()
+        _lib.check(self.lib.trace_decode_set_logits_params(self.h, float(lp.repetition_penalty), int(lp.no_repeat_ngram_size), int(lp.min_new_tokens)))
+
+    def logits_process(self, logits: torch.Tensor, heads: Sequence[int], hist: Sequence[Sequence[int]], params: LogitsParams, steps: Sequence[int],
+                       eos: int = -1) -> torch.Tensor:
+        """Masked logits [B, NV] fp32 (device) -> a new tensor of the same shape: row b processed as a decode step processes it at device step
+        steps[b] with history hist[b] (trace_op_logits_process: the device code of the decode step; sampling.process_row_ref bit for bit) - the
+        host-driven paths call it on the logits they bring back."""
+        cfg = self.cfg
+        return ops.logits_process(logits, heads, hist, params, steps, eos, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size,
+                                  element=_lib.element_of(self.dtype))
+
     def sample(self, logits: torch.Tensor, heads: Sequence[int], sampling: SamplingParams, steps: Sequence[int]) -> List[int]:
         """One id per row of masked logits [B, NV] fp32 (device), drawn as a decode step draws them (row b: Philox step steps[b], row index b):
         the device sampler (trace_op_sample) inside its domain, the host statement of the same rules outside it."""
@@ -571,36 +587,49 @@ class TraceEngine:
         flush()
 
     def decode(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
-               forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False):
+               forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
+               logits: Optional[LogitsParams] = None):
         """Stage 2 of generate(): the decode loop over prefilled KV slots, on the current stream -> (ids per sequence, final heads).
+        logits: repetition penalty / no-repeat n-grams / min_new_tokens (LogitsParams; None or all off = today's launches and graphs), applied
+        inside the decode step to the ids each row has generated so far (set_logits_params); not together with forced ids.
         sampling: None / temperature <= 0 = greedy; otherwise every id is drawn on the device (trace_decode_set_sampling: same graphs, same
         stepping), or — parameters outside the device sampler's domain — one eager step at a time with the host statement of the same rules.
         logprobs: the result gains a third element, one float32 array per row as long as that row's ids: the log-probability of every emitted
         token under the model's own (unwarped) distribution, computed inside the decode step (trace_decode_set_logprobs)."""
+        armed = logits is not None and not logits.off
+        if armed and forced is not None:
+            raise ValueError("logits processors act on the ids a row has recorded; under forced ids those are not the fed ones (forced= with logits=)")
         if sampling is not None and not sampling.greedy and not sampling.on_device:
-            return self._decode_host_sampled(slots, heads, max_new_tokens, eos, forced, sampling, logprobs)
+            return self._decode_host_sampled(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits if armed else None)
         on_dev = sampling is not None and not sampling.greedy
         if on_dev:
             self.set_sampling(sampling)
         if logprobs:
             self.set_logprobs(True)
+        if armed:
+            self.set_logits_params(logits)
         try:
             return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs)
         finally:
+            if armed:
+                self.set_logits_params(None)
             if logprobs:
                 self.set_logprobs(False)
             if on_dev:
                 self.set_sampling(None)
 
-    def _decode_host_sampled(self, slots, heads, max_new_tokens, eos, forced, sampling: SamplingParams, logprobs: bool = False):
+    def _decode_host_sampled(self, slots, heads, max_new_tokens, eos, forced, sampling: SamplingParams, logprobs: bool = False,
+                             logits: Optional[LogitsParams] = None):
         B = len(slots)
         self.host_mode(True)
         try:
             lg = self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, want_logits=True)
             cur = list(heads)
+            ids = [[] for _ in range(B)]
             lp = np.zeros((B, max_new_tokens), np.float32)
             for step in range(max_new_tokens):
-                tok = self.sample(lg, cur, sampling, [step] * B)
+                # (logits processors: the loose op on the rows brought back, the history = the ids recorded so far; the log-probability stays the raw row's)
+                tok = self.sample(self.logits_process(lg, cur, ids, logits, [step] * B, eos) if logits is not None else lg, cur, sampling, [step] * B)
                 if forced is not None:
                     tok = [f[step] if step < len(f) and f[step] >= 0 else t for t, f in zip(tok, forced)]
                 val = self.token_logprob(lg, cur, tok) if logprobs else None       # host-select mode: the fed token, under the head it was drawn from
@@ -637,15 +666,16 @@ class TraceEngine:
 
     def generate(self, videos: Sequence[torch.Tensor], timestamps: Sequence, input_ids: Sequence[Sequence[int]],
                  heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
-                 forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False):
+                 forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
+                 logits: Optional[LogitsParams] = None):
         B = len(videos)
         if B > self.decode_batch_max:
             raise ValueError(f"batch {B} exceeds the engine's decode batch {self.decode_batch_max}")
         self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
-        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs)
+        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits)
 
     def generate_samples(self, video: torch.Tensor, timestamps, prompt_ids: Sequence[int], head: int, n: int, max_new_tokens: int, eos: int = -1,
-                         sampling: Optional[SamplingParams] = None, use_graph: bool = True):
+                         sampling: Optional[SamplingParams] = None, use_graph: bool = True, logits: Optional[LogitsParams] = None):
         """n sampled continuations of ONE prompt from one tower pass and one prefill: the prompt is encoded and prefilled into KV slot 0, its rows
         are copied to slots 1 .. n - 1 (kv_copy), and slots 0 .. n - 1 decode as one batch with log-probabilities on.  Row r draws with Philox
         row index r, as any decode batch does, so the result equals generate() of the prompt repeated n times with the same SamplingParams:
@@ -659,11 +689,12 @@ class TraceEngine:
         self.prefill(0, L)
         if n > 1:
             self.kv_copy(0, list(range(1, n)), L)
-        return self.decode(range(n), [int(head)] * n, max_new_tokens, eos, use_graph, None, sampling, logprobs=True)
+        return self.decode(range(n), [int(head)] * n, max_new_tokens, eos, use_graph, None, sampling, logprobs=True, logits=logits)
 
     def generate_questions(self, video: torch.Tensor, timestamps, prompts: Sequence[Sequence[int]], heads: Sequence[int], max_new_tokens: int,
                            eos: int = -1, sampling: Optional[SamplingParams] = None, use_graph: bool = True,
-                           forced: Optional[Sequence[Sequence[int]]] = None, prefix_key=None, logprobs: bool = False):
+                           forced: Optional[Sequence[Sequence[int]]] = None, prefix_key=None, logprobs: bool = False,
+                           logits: Optional[LogitsParams] = None):
         """generate() for Q prompts about ONE video whose ids agree up to and including the <video> placeholder (the reference's per-question
         loops, trace/eval/videomme/evaluate.py:349-386): the tower, the slot pool and the prefill of the common prefix run once (slot 0), the
         prefix's KV rows are copied to the other Q - 1 slots, each prompt's rows after <video> are appended (one pass per group of equal
@@ -694,7 +725,7 @@ class TraceEngine:
                     slot += 1
         if prefix_key is not None:
             self.set_prefix_entry(prefix_key, P)
-        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs)
+        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits)
 
     # ---- two-stage pipeline over a stream of batches ---------------------------------------------------
     def make_streams(self, decode_cus: int = 0):
@@ -715,11 +746,11 @@ class TraceEngine:
         return enc, dec
 
     def generate_stream(self, batches: Iterable, max_new_tokens: int, eos: int = -1, use_graph: bool = True, streams=None,
-                        sampling: Optional[SamplingParams] = None, logprobs: bool = False):
+                        sampling: Optional[SamplingParams] = None, logprobs: bool = False, logits: Optional[LogitsParams] = None):
         """generate() over a stream of batches as a two-stage pipeline: while batch k decodes (HBM-bound) on one stream, batch k+1
         runs its ViT + slot pool + prefill (MFMA-bound) on another, into the other half of the KV slots.  `batches` yields
         (videos, timestamps, input_ids, heads, forced-or-None); yields generate()'s result per batch, in order.  Every batch holds at
-        most max_batch // 2 videos.  sampling: as decode(), the same params (and seed) for every batch.  Results are identical to generate() batch by batch: the stages share no buffers (KV banks,
+        most max_batch // 2 videos.  sampling / logits: as decode(), the same params (and seed) for every batch.  Results are identical to generate() batch by batch: the stages share no buffers (KV banks,
         prefill / ViT scratch vs decode scratch) and every kernel's reductions have a fixed order.
 
         The decode stage is issued from a worker thread: one decode batch is ~75 k kernel dispatches, far more than a HIP stream's
@@ -738,7 +769,8 @@ class TraceEngine:
             with torch.cuda.stream(dec_s):
                 dec_s.wait_event(ready)
                 # (logprobs: read inside this job, right after the ids — decode() returns them, nothing goes through engine state afterwards)
-                return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs)
+                return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs,
+                                   logits=logits)
 
         pending = None                                  # (bank, heads, forced, B, ready event): prefilled, waiting for its decode
         bank = 0
@@ -802,6 +834,28 @@ class ops:
         out = torch.empty(B, dtype=torch.int32, device=dev)
         _lib.check(lib.trace_op_sample(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, float(sampling.temperature), int(sampling.top_k),
                                        float(sampling.top_p), int(sampling.seed), _ptr(st), _ptr(out), _stream()))
+        return out
+
+    @staticmethod
+    def logits_process(logits, heads, hist, params: LogitsParams, steps, eos: int, V: int, Tv: int, Sv: int, element=None):
+        """trace_op_logits_process: logits [B, ld >= V+1+Tv+Sv] fp32 (device) -> a new fp32 [B, ld] (device): row b under head heads[b] with the
+        repetition penalty, the n-gram bans and the min_new_tokens rule of `params` for history hist[b] (a sequence of id sequences, any lengths)
+        at device step steps[b]; -inf outside the head.  sampling.process_row_ref bit for bit.  heads / steps: sequences of ints or int32 device tensors."""
+        lib = _lib.load(element or ops.element)
+        lg = logits.contiguous()
+        B, ld = lg.shape
+        dev = lg.device
+        hd = heads if isinstance(heads, torch.Tensor) else torch.tensor([int(h) for h in heads], dtype=torch.int32, device=dev)
+        st = steps if isinstance(steps, torch.Tensor) else torch.tensor([int(x) for x in steps], dtype=torch.int32, device=dev)
+        if len(hist) != B:
+            raise ValueError("one history per row")
+        ldh = max(1, max(len(h) for h in hist))
+        hh = torch.tensor([[int(t) for t in h] + [0] * (ldh - len(h)) for h in hist], dtype=torch.int32, device=dev)
+        hl = torch.tensor([len(h) for h in hist], dtype=torch.int32, device=dev)
+        out = torch.empty_like(lg) if ld == V + 1 + Tv + Sv else torch.full_like(lg, float("-inf"))      # (the op writes columns [0, V+1+Tv+Sv))
+        _lib.check(lib.trace_op_logits_process(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, _ptr(hh), ldh, _ptr(hl), _ptr(st), int(eos),
+                                               float(params.repetition_penalty), int(params.no_repeat_ngram_size), int(params.min_new_tokens),
+                                               _ptr(out), _stream()))
         return out
 
     @staticmethod

@@ -92,11 +92,12 @@ def parse_output_ids(ids: Sequence[int], tokenizer, model, stop_str: Optional[st
 @torch.no_grad()
 def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: str, *, num_frames: Optional[int] = None,
                     max_new_tokens: int = 512, batch_size: Optional[int] = None, conv_mode: str = "llama_2",
-                    device_preprocess: bool = True, pipeline: bool = True, sampling=None, logprobs: bool = False) -> List[dict]:
+                    device_preprocess: bool = True, pipeline: bool = True, sampling=None, logprobs: bool = False, logits=None) -> List[dict]:
     """items: dicts with "video" (decoded frames array / list / a reader with get_batch), optional "fps", "id", "query"
     (formatted into `prompt` as the tvg / vhd tasks do, evaluate.py:303-306).  Returns one result dict per item, in order, on
     every rank: {"video", "id", "timestamps", "scores", "captions", "output_ids"}.  sampling: a trace_amd.engine.SamplingParams (None = greedy),
-    the same params and seed for every chunk.  logprobs: every result gains "output_logprobs", one float per entry of "output_ids" (the
+    the same params and seed for every chunk.  logits: a trace_amd.sampling.LogitsParams (repetition penalty, no-repeat n-grams, min_new_tokens over the
+    ids each row has generated; None = off).  logprobs: every result gains "output_logprobs", one float per entry of "output_ids" (the
     device's per-token log-probabilities; their float bits cross the ranks in the same all-gather as the ids)."""
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
     world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
@@ -127,12 +128,12 @@ def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: 
             yield vids, tss, idl, [1] * len(chunk), None
 
     if pipelined and len(mine) > bs:
-        for out, _, *lp in eng.generate_stream(chunks(), max_new_tokens, eos=eos, sampling=sampling, logprobs=logprobs):
+        for out, _, *lp in eng.generate_stream(chunks(), max_new_tokens, eos=eos, sampling=sampling, logprobs=logprobs, logits=logits):
             local.extend(out)
             local_lp.extend(lp[0] if logprobs else [])
     else:
         for vids, tss, idl, heads, _ in chunks():
-            out, _, *lp = eng.generate(vids, tss, idl, heads, max_new_tokens, eos=eos, sampling=sampling, logprobs=logprobs)
+            out, _, *lp = eng.generate(vids, tss, idl, heads, max_new_tokens, eos=eos, sampling=sampling, logprobs=logprobs, logits=logits)
             local.extend(out)
             local_lp.extend(lp[0] if logprobs else [])
     per_rank = (len(items) + world - 1) // world

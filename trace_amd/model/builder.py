@@ -136,13 +136,13 @@ def load_tokenizer(model_path: str, cfg: TraceConfig, **kwargs):
 
 def apply_generation_config(model, model_path: str) -> None:
     """from_pretrained reads the checkpoint's generation_config.json (when present) into the model's generate() defaults; the sampling keys
-    this build acts on are do_sample / temperature / top_k / top_p."""
+    this build acts on are do_sample / temperature / top_k / top_p and repetition_penalty / no_repeat_ngram_size / min_new_tokens."""
     fn = os.path.join(model_path, "generation_config.json")
     if not os.path.exists(fn):
         return
     with open(fn) as f:
         gc = json.load(f)
-    for k in ("do_sample", "temperature", "top_k", "top_p"):
+    for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"):
         if gc.get(k) is not None:
             setattr(model.generation_config, k, gc[k])
 

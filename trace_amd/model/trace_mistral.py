@@ -14,7 +14,7 @@ import torch
 from ..config import TraceConfig
 from ..constants import MMODAL_TOKEN_INDEX, NUM_FRAMES
 from ..prefix import split_questions
-from ..sampling import SamplingParams, check_sampling
+from ..sampling import LogitsParams, SamplingParams, check_sampling, head_bounds
 from .encoders import NumberTokenizer, ScoreTower, TimeTower
 
 
@@ -70,7 +70,8 @@ class TraceMistralForCausalLM:
         self.device = engine.device
         self.dtype = engine.dtype
         # HF GenerationConfig defaults; builder.load_pretrained_model overrides them from the checkpoint's generation_config.json
-        self.generation_config = SimpleNamespace(do_sample=False, temperature=1.0, top_k=50, top_p=1.0)
+        self.generation_config = SimpleNamespace(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                                                 min_new_tokens=0)
         self._prefix_cache = False
 
     # ---- prompt-prefix reuse across generate() calls ----
@@ -90,7 +91,7 @@ class TraceMistralForCausalLM:
     def prefix_cache_enabled(self) -> bool:
         return self._prefix_cache
 
-    def _generate_prefix_cached(self, raw, vids, modals, timestamps, id_lists, heads, max_new_tokens, eos, sampling, logprobs=False):
+    def _generate_prefix_cached(self, raw, vids, modals, timestamps, id_lists, heads, max_new_tokens, eos, sampling, logprobs=False, **lg):
         """generate()'s main path with the cache on; None = this call is not of the cacheable shape (today's path runs)."""
         eng, B = self.engine, len(vids)
         try:
@@ -109,7 +110,7 @@ class TraceMistralForCausalLM:
         key = (raw[0], raw[0]._version, ts_key, modals[0], tuple(prefix))
         if B > 1:
             return eng.generate_questions(vids[0], timestamps[0], id_lists, heads, max_new_tokens, eos=eos, sampling=sampling, prefix_key=key,
-                                          logprobs=logprobs)
+                                          logprobs=logprobs, **lg)
         ent = eng.prefix_entry()
         hit = ent is not None and ent[0][0] is key[0] and ent[0][1:] == key[1:]
         if hit:
@@ -121,7 +122,7 @@ class TraceMistralForCausalLM:
             eng.set_prefix_entry(key, P)
         eng.embed_rows(suffixes[0])
         eng.prefill_append(0, P, None, L=len(suffixes[0]))
-        return eng.decode([0], heads, max_new_tokens, eos, sampling=sampling, logprobs=logprobs)
+        return eng.decode([0], heads, max_new_tokens, eos, sampling=sampling, logprobs=logprobs, **lg)
 
     # ---- nn.Module-like conveniences the drivers call ----
     def get_model(self):
@@ -154,7 +155,10 @@ class TraceMistralForCausalLM:
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, stopping_criteria=None,
                  use_cache: bool = True, attention_mask=None, position_ids=None, output_logprobs: bool = False, **kwargs):
         """do_sample / temperature / top_k / top_p: explicit values, else `generation_config`'s, else this model's defaults (HF's: greedy,
-        1.0, 50, 1.0, or the checkpoint's generation_config.json).  Sampling follows HF's warpers (temperature -> top_k -> top_p ->
+        1.0, 50, 1.0, or the checkpoint's generation_config.json).  repetition_penalty / no_repeat_ngram_size / min_new_tokens: the same
+        precedence; HF's processors in HF's order on the device, inside the decode step (trace_amd/csrc/logits.h).  Their history is the ids a row
+        has generated so far, never the prompt (the reference hands HF inputs_embeds), as global vocabulary ids: a time or score digit emitted
+        earlier counts in a later span too.  Log-probabilities keep describing the raw, unprocessed distribution.  Sampling follows HF's warpers (temperature -> top_k -> top_p ->
         multinomial) on the device (trace_amd/csrc/sample.h); the 64-bit seed is drawn from torch's default generator, so torch.manual_seed
         makes a call reproducible.  temperature == 0 or do_sample=False: greedy.
         output_logprobs=True: instead of the id tensor, an object with `.sequences` (exactly that tensor), `.logprobs` (float32 [B, n], zero
@@ -162,7 +166,10 @@ class TraceMistralForCausalLM:
         on the device inside the decode step; a row's sum is its score) and `.heads` (the final heads)."""
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")          # trace_mistral.py:282-283
-        sampling = self._sampling_params(do_sample, temperature, top_k, top_p, generation_config, kwargs)
+        lgp = self._logits_params(kwargs.pop("repetition_penalty", None), kwargs.pop("no_repeat_ngram_size", None), kwargs.pop("min_new_tokens", None),
+                                  generation_config)
+        sampling = self._sampling_params(do_sample, temperature, top_k, top_p, _ProcessorsOff(generation_config, self.generation_config), kwargs)
+        lg = {} if lgp is None else {"logits": lgp}              # handed on only when armed
         if images_or_videos is None:
             raise NotImplementedError("text-only generation is outside the accelerated path")
         cfg, eng = self.config, self.engine
@@ -199,8 +206,8 @@ class TraceMistralForCausalLM:
                 eng.vit_forward(vids[b])
                 eng.stc_connector(None, vids[b].shape[0])
                 eng.prefill(b, eng.splice(id_lists[b]))
-            if sampling is not None or output_logprobs:
-                out, new_heads, *lps = eng.decode(list(range(B)), [0] * B, max_new_tokens, eos, sampling=sampling, logprobs=output_logprobs)
+            if sampling is not None or output_logprobs or lgp is not None:
+                out, new_heads, *lps = eng.decode(list(range(B)), [0] * B, max_new_tokens, eos, sampling=sampling, logprobs=output_logprobs, **lg)
             else:
                 eng.decode_begin(list(range(B)), [0] * B, max_new_tokens, eos)
                 if max_new_tokens > 1:
@@ -210,12 +217,12 @@ class TraceMistralForCausalLM:
             res = None
             if self._prefix_cache and all(isinstance(x, torch.Tensor) for x in images_or_videos):
                 res = self._generate_prefix_cached(list(images_or_videos), vids, modals, video_timestamps, id_lists, list(heads), max_new_tokens, eos, sampling,
-                                                   output_logprobs)
+                                                   output_logprobs, **lg)
             out, new_heads, *lps = res if res is not None else eng.generate(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos=eos,
-                                                                            sampling=sampling, logprobs=output_logprobs)
+                                                                            sampling=sampling, logprobs=output_logprobs, **lg)
         else:
             out, new_heads, *lps = self._generate_stepwise(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos,
-                                                           sampling, stopping_criteria, ids, output_logprobs)
+                                                           sampling, stopping_criteria, ids, output_logprobs, lgp)
         for b in range(B):                       # the reference mutates `heads` in place (trace_mistral.py:342)
             heads[b] = int(new_heads[b])
         pad = eos if pad_token_id is None else pad_token_id
@@ -249,7 +256,9 @@ class TraceMistralForCausalLM:
             raise ValueError("generate_samples takes one prompt (B = 1); use generate() for a batch")
         if not isinstance(n, int) or isinstance(n, bool) or n < 1:
             raise ValueError(f"n must be a positive integer, got {n!r}")
-        sampling = self._sampling_params(True, temperature, top_k, top_p, generation_config, kwargs)
+        lgp = self._logits_params(kwargs.pop("repetition_penalty", None), kwargs.pop("no_repeat_ngram_size", None), kwargs.pop("min_new_tokens", None),
+                                  generation_config)
+        sampling = self._sampling_params(True, temperature, top_k, top_p, _ProcessorsOff(generation_config, self.generation_config), kwargs)
         if sampling is None:
             raise ValueError("generate_samples needs temperature > 0: greedy rows would all be identical")
         cfg, eng = self.config, self.engine
@@ -263,7 +272,8 @@ class TraceMistralForCausalLM:
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
         if eos is None:
             eos = -1
-        out, new_heads, lps = eng.generate_samples(x, video_timestamps[0], ids[0].tolist(), head, n, max_new_tokens, eos=eos, sampling=sampling)
+        out, new_heads, lps = eng.generate_samples(x, video_timestamps[0], ids[0].tolist(), head, n, max_new_tokens, eos=eos, sampling=sampling,
+                                                   **({} if lgp is None else {"logits": lgp}))
         scores = np.array([np.sum(np.asarray(r, np.float32), dtype=np.float64) for r in lps], np.float64)
         order = rank_samples(scores) if best_first else list(range(n))
         pad = eos if pad_token_id is None else pad_token_id
@@ -304,9 +314,28 @@ class TraceMistralForCausalLM:
         g = torch.randint(0, 1 << 32, (2,), dtype=torch.int64)        # torch's default generator: torch.manual_seed(s) reproduces a call
         return SamplingParams(temperature, int(top_k), top_p, (int(g[0]) << 32) | int(g[1]))
 
-    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, prompt_ids, logprobs=False):
+    def _logits_params(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, generation_config) -> Optional[LogitsParams]:
+        """repetition_penalty / no_repeat_ngram_size / min_new_tokens with HF's precedence: explicit argument > generation_config > the model's
+        defaults.  None = all three off (the decode step then is what it is without them).  ValueError outside HF's domains, and for an n-gram
+        size above 64 (the device's bound)."""
+        srcs = [s for s in (generation_config, self.generation_config) if s is not None]
+
+        def pick(name, val, off):
+            if val is not None:
+                return val
+            for src in srcs:
+                v = src.get(name) if isinstance(src, dict) else getattr(src, name, None)
+                if v is not None:
+                    return v
+            return off
+        lgp = LogitsParams(pick("repetition_penalty", repetition_penalty, 1.0), pick("no_repeat_ngram_size", no_repeat_ngram_size, 0),
+                           pick("min_new_tokens", min_new_tokens, 0))
+        return None if lgp.off else lgp
+
+    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, prompt_ids, logprobs=False, lgp=None):
         """Stopping-criteria path: one device step at a time with the masked logits brought back; ids from the device sampler
-        (trace_op_sample: the same draw a device decode step makes at that step and row) or the arg-max."""
+        (trace_op_sample: the same draw a device decode step makes at that step and row) or the arg-max.  lgp (LogitsParams): the logits
+        processors through the loose-row op (trace_op_logits_process: the decode step's device code) on those rows, history = the recorded ids."""
         eng = self.engine
         B = len(vids)
         for b in range(B):
@@ -318,14 +347,21 @@ class TraceMistralForCausalLM:
         eng.host_mode(True)
         try:
             lg = eng.decode_begin(list(range(B)), heads, max_new, eos=eos, want_logits=True)
+            rec = [[] for _ in range(B)]
+            cfg = self.config
             for step in range(max_new):
+                sel = lg if lgp is None else eng.logits_process(lg, cur_heads, rec, lgp, [step] * B, eos)     # (lg stays raw: the log-probabilities' row)
                 if sampling is not None:
-                    tok = eng.sample(lg, cur_heads, sampling, [step] * B)
-                else:
+                    tok = eng.sample(sel, cur_heads, sampling, [step] * B)
+                elif lgp is None:
                     tok = torch.argmax(lg, dim=-1).tolist()
+                else:                           # the device's rule: the lowest id among equal maxima of the head's range (all banned: its first id)
+                    rows = sel.cpu().numpy()
+                    tok = [lo + int(np.argmax(rows[b, lo:hi])) for b, (lo, hi) in
+                           enumerate(head_bounds(h, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size) for h in cur_heads)]
                 val = eng.token_logprob(lg, cur_heads, tok) if logprobs else None      # the loose-row op on the logits this path brings back anyway
                 eng.feed(tok)
-                if sampling is not None or logprobs:
+                if sampling is not None or logprobs or lgp is not None:
                     rec, cur_heads = eng.decode_read()
                 if logprobs:
                     for b in range(B):
@@ -433,6 +469,23 @@ class TraceMistralForCausalLM:
         return SimpleNamespace(logits=logits, past_key_values=self._live_kv, loss=None, hidden_states=None, attentions=None)
 
     __call__ = forward
+
+
+class _ProcessorsOff:
+    """A generation-config view for _sampling_params in which the logits processors this build implements read as off: generate() resolves them
+    itself (_logits_params), and _sampling_params keeps refusing the name when it is called on its own."""
+
+    def __init__(self, *srcs):
+        self._srcs = [s for s in srcs if s is not None]
+
+    def __getattr__(self, name):
+        if name == "repetition_penalty":
+            return 1.0
+        for src in self._srcs:
+            v = src.get(name) if isinstance(src, dict) else getattr(src, name, None)
+            if v is not None:
+                return v
+        return None
 
 
 def rank_samples(scores) -> List[int]:

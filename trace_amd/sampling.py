@@ -4,7 +4,9 @@
 sampler in float32 numpy, operation by operation (the same exp polynomial, the same run sums and Hillis-Steele scan, the same rank
 arithmetic), so it returns the device's id bit for bit; it also serves as the host path for the parameter combinations the device does not
 take (top_k > 1024, or top_k = 0 with top_p < 1), where it applies the same rules.  `philox_uniform` is the RNG contract in numpy.
-`token_logprob_ref` restates the per-token log-probability (sample.h token_logprob_row) the same way: the device's float bits."""
+`token_logprob_ref` restates the per-token log-probability (sample.h token_logprob_row) the same way: the device's float bits.
+`LogitsParams` / `process_row_ref`: the logits processors of the decode step (repetition penalty, no-repeat n-grams, min_new_tokens:
+trace_amd/csrc/logits.h) and their float32 restatement, again bit for bit."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -222,6 +224,68 @@ def token_logprob_ref(row, i):
         if not 0 <= int(i) < n:
             return _F(-np.inf)
         return _F((x[int(i)] - M) - _slog(np.array([S], np.float32))[0])
+
+
+# ---- logits processors (csrc/logits.h) ----
+MAX_NGRAM = 64                # logits.h LOGITS_MAX_NGRAM
+
+
+def check_logits_params(repetition_penalty, no_repeat_ngram_size, min_new_tokens) -> None:
+    """HF's own argument checks (RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor / MinNewTokensLengthLogitsProcessor, with 0
+    = off for the two integers as in GenerationConfig) and the device's bound on the n-gram size"""
+    p = float(repetition_penalty)
+    if not p > 0 or p != p or p == float("inf"):
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive finite float, but is {repetition_penalty}")
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0:
+            raise ValueError(f"`{name}` has to be a non-negative integer, but is {v}")
+    if no_repeat_ngram_size > MAX_NGRAM:
+        raise ValueError(f"`no_repeat_ngram_size` is at most {MAX_NGRAM} on the device, but is {no_repeat_ngram_size}")
+
+
+@dataclass(frozen=True)
+class LogitsParams:
+    """HF's logits processors in HF's order: repetition_penalty (1.0 = off), no_repeat_ngram_size (0 = off, at most 64), min_new_tokens
+    (0 = off).  The history they look at is the ids a row has generated so far — never the prompt — as global vocabulary ids."""
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
+
+    def __post_init__(self):
+        check_logits_params(self.repetition_penalty, self.no_repeat_ngram_size, self.min_new_tokens)
+
+    @property
+    def off(self) -> bool:
+        return float(self.repetition_penalty) == 1.0 and self.no_repeat_ngram_size == 0 and self.min_new_tokens == 0
+
+
+def process_row_ref(row, hist, lo, hi, params: LogitsParams, step, eos):
+    """The device's processed row (logits.h logits_process_row), bit for bit: row = one whole row of masked logits (float32 [NV]), hist = the ids
+    the row has generated so far (global ids; ids outside [lo, hi) touch nothing), [lo, hi) the active head's range, step the device step, eos
+    the decode batch's (< 0: none).  Returns a new float32 [NV]: the processed values on [lo, hi), -inf elsewhere.
+      1. every DISTINCT id t of hist: y[t] = x[t] * p if x[t] < 0 else x[t] / p (float32, from the raw value);
+      2. n-gram n, if len(hist) + 1 >= n: y[hist[i + n - 1]] = -inf for every i in [0, len(hist) - n] whose n - 1 ids equal the last n - 1;
+      3. step < min_new_tokens and eos in the head: y[eos] = -inf."""
+    x = np.asarray(row, np.float32)
+    h = [int(t) for t in hist]
+    out = np.full(len(x), -np.inf, np.float32)
+    out[lo:hi] = x[lo:hi]
+    p = _F(params.repetition_penalty)
+    if p != _F(1.0):
+        ids = np.array(sorted({t for t in h if lo <= t < hi}), np.int64)
+        if len(ids):
+            v = x[ids]
+            with np.errstate(invalid="ignore"):
+                out[ids] = np.where(v < 0, v * p, v / p).astype(np.float32)
+    n, L = int(params.no_repeat_ngram_size), len(h)
+    if n >= 1 and L + 1 >= n:
+        suffix = h[L - (n - 1):] if n > 1 else []
+        for i in range(0, L - n + 1):
+            if h[i:i + n - 1] == suffix and lo <= h[i + n - 1] < hi:
+                out[h[i + n - 1]] = -np.inf
+    if int(step) < int(params.min_new_tokens) and lo <= int(eos) < hi:
+        out[int(eos)] = -np.inf
+    return out
 
 
 def head_bounds(head: int, V: int, Tv: int, Sv: int):
