@@ -58,6 +58,21 @@ int trace_element_type(void);
 /* from_pretrained (trace/model/builder.py:113-114): create, stream tensors in by their reference state-dict
  * names (bf16; `on_device` says whether `data` is a device or host pointer), then finalize. */
 int trace_ctx_create(const trace_config* cfg, int device_id, trace_ctx** out);
+/* trace_ctx_create with options (trace_config is frozen at ABI version 4).  size = sizeof(trace_ctx_opts) of the caller.  kv_cache_fp8 = 1: the context
+ * keeps its KV cache as e4m3 bytes with one fp32 scale per position and kv head (the "kv8" format, stated at the end of this header) — 264 bytes per
+ * position and kv head instead of 512, i.e. about twice the sequences or context per card — plus one layer's 16-bit K / V^T of 8 slots that every prefill
+ * stages through.  opts == NULL or a zero flag is trace_ctx_create.  Under kv_cache_fp8:
+ *   - a prefill of whole prompts computes the bits the 16-bit-cache context computes (hidden rows, last-position row, step-0 logits): its attention runs
+ *     on the 16-bit staging rows, which are quantised into the cache afterwards;
+ *   - trace_llm_prefill_append first dequantises the cached rows it continues, so the new rows attend the QUANTISED past — what the decode steps see.
+ *     Deterministic, but not the bits of an uncut prefill: "a row's bits do not depend on where the prompt was cut" is the 16-bit cache's promise;
+ *   - every decode step appends with a launch of its own (the route trace_op_decode_route out[2] = 1 describes) and attends the e4m3 cache;
+ *   - trace_kv_copy moves the e4m3 arrays (whole 32-position blocks), trace_debug_buffers answers TRACE_ERR_STATE (trace_debug_kv8_buffers).
+ * TRACE_ERR_ARG, checked before any device call: kv_cache_fp8 outside {0, 1}; kv_cache_fp8 with llm_weights_fp8 != 0 (fp8 weights over an fp8 cache
+ * is out of scope). */
+typedef struct trace_ctx_opts { int32_t size; int32_t kv_cache_fp8; } trace_ctx_opts;
+int trace_ctx_create_opts(const trace_config* cfg, int device_id, const trace_ctx_opts* opts, trace_ctx** out);
+int trace_ctx_kv_cache_type(trace_ctx* ctx);            /* 0 = element type, 1 = e4m3 + scales */
 int trace_ctx_destroy(trace_ctx* ctx);
 int trace_ctx_load_tensor(trace_ctx* ctx, const char* name, const void* data, int on_device, const int64_t* shape,
                           int ndim);
@@ -237,13 +252,19 @@ int trace_set_profile(trace_ctx* ctx, int on);
 /* Debugging aid: device addresses of the K cache, the V^T cache and the prefill's last-position hidden rows, with strides[8] = layer, slot, kv-head
  * strides (elements), ctx_pad, layers, kv heads, head_dim, hidden (tools/pipeline_stress.py checksums them between the pipeline's stages). */
 int trace_debug_buffers(trace_ctx* ctx, void** kcache, void** vcache, void** xlast, int64_t* strides);
+/* The same for a kv_cache_fp8 context: device addresses of K8, V8 (bytes), ks, vs (fp32), strides[8] = layer, slot, kv-head strides of the payload in
+ * BYTES (those of the scales are these / 128), ctx_pad, layers, kv heads, head_dim, hidden.  TRACE_ERR_STATE on a 16-bit-cache context. */
+int trace_debug_kv8_buffers(trace_ctx* ctx, void** k8, void** v8, void** ks, void** vs, int64_t* strides);
 /* out[0..n) (n <= 20): [0] ms per decode step of the last trace_decode_steps call, [1] its steps, [2] average ms of the bracketed decode launch,
  * [3] its samples, [4] its algorithmic bytes, [5] average ms of the bracketed ViT fc1 GEMM launch, [6] its samples, [7] its GFLOP,
- * [8] which decode launch took the bracket: 1 = gate|up GEMV, 2 = batch-1 fused-norm gate|up GEMV, 3 = the wide step's layer-0 decode attention,
+ * [8] which decode launch took the bracket: 1 = gate|up GEMV, 2 = batch-1 fused-norm gate|up GEMV, 3 = the layer-0 decode attention (the wide step's
+ * own choice, or bracket bit 2), 4 = the layer-0 append launch (bracket bit 3),
  * [9] always 0 (rounds 3-4: whether the bracketed ViT GEMMs ran with the LayerNorm fold; the fold left the product in round 5),
  * [12..14] average ms of the bracketed ViT qkv / out-proj / fc2 GEMM launches (layer 0, the same calls as [5]), [15..17] their GFLOP. */
 int trace_get_profile(trace_ctx* ctx, float* out, int n);
-/* Which per-launch brackets profiling mode 2 takes: bit 0 = the ViT fc1 GEMM, bit 1 = the decode step's dominant kernel.  A pipelined caller
+/* Which per-launch brackets profiling mode 2 takes: bit 0 = the ViT fc1 GEMM, bit 1 = the decode step's dominant kernel; instead of bit 1 (set one
+ * of the three), bit 2 = the layer-0 decode attention in whichever step body runs (with its fused append where it has one; [4] = the K + V bytes it streams),
+ * bit 3 = the layer-0 append launch (qkv_finish / qkv_finish_kv8; none is taken where the step fuses the append into the attention).  A pipelined caller
  * (two stages on two streams) leaves a stage's bracket on only while that stage has the GPU to itself (pipeline fill / drain). */
 int trace_set_profile_brackets(trace_ctx* ctx, int mask);
 
@@ -356,6 +377,46 @@ int trace_op_qkv_finish(const float* part, int ks, void* q_out, void* kcache, vo
 int trace_op_attn_decode_fused(const float* part, int ks, void* kcache, void* vtcache, const int32_t* slots, const int32_t* pos, const float* cos_t,
                                const float* sin_t, void* O, float* ws, int B, int nq, int nkv, int num_slots, int max_ctx, int nsplit, float scale,
                                void* stream);
+
+/* ---- The e4m3 KV cache format ("kv8"), and its kernels over loose arrays -------------------------------------------------------------------------
+ * For one position j of one kv head, x = the 128 values of the row in the library's element type (K after RoPE, V as is), read as fp32:
+ *     amax   = max |x_d|
+ *     s      = amax > 0 ? amax / 448 : 1        (fp32 division)  -> scale[j]
+ *     inv    = amax > 0 ? 448 / amax : 1        (fp32 division)
+ *     byte_d = e4m3fn(clamp(x_d * inv, -448, 448))               round to nearest even; OCP e4m3fn, not fnuz
+ * (the rule of trace_op_quant_rows_fp8 on a 128-wide row).  Dequantised value = s * e4m3(byte): 264 bytes per position and kv head instead of 512.
+ * Arrays, per layer:
+ *     K8     [slot][kvh][ctx][128]          bytes
+ *     V8     [slot][kvh][ctx / 32][128][32] bytes: position-blocked V^T, value d of position p is byte (d, p % 32) of the 4 KB block p / 32
+ *     ks, vs [slot][kvh][ctx]               fp32
+ * The attention widens the bytes to the element type in registers (exact for every finite e4m3 value, bf16 and fp16) and keeps the 16-bit matrix
+ * instructions; q and the probabilities are never narrowed.  The scales fold into the per-position scalars:
+ *     score_j = (acc_j * scale) * ks[j]         acc = fp32 sum of q . widen(K8[j])
+ *     p_j     = exp(score_j - m);  l += p_j     (l sums the unscaled p)
+ *     P_j     = round16(p_j * vs[j])            operand of the PV product against widen(V8)
+ *     o       = round16((sum_j P_j . widen(V8[j])) / l)
+ * Positions past pos[b] inside a 32-position block are read, masked and weigh exactly 0: they must hold finite bytes (not 0x7F / 0xFF) and finite
+ * scales (zero-filled arrays do).  trace_amd/kv8.py restates the format in torch.
+ * A context keeps its cache in this format under trace_ctx_create_opts(kv_cache_fp8 = 1); the entry points below run the kernels over loose arrays. */
+/* trace_op_attn_decode over kv8 arrays (row b in slot b; max_ctx % 32 == 0, nq == 4 nkv, nkv <= 64): q [B][nq * 128] rotated, pos[b] = the newest
+ * position, already in the arrays -> O [B][nq * 128]; ws: B * nq * nsplit * 130 floats.  TRACE_ERR_ARG before any launch: B above trace_op_sk_rows(), a
+ * shape outside the above, a position outside [0, max_ctx). */
+int trace_op_attn_decode_kv8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs, const int32_t* pos, void* O, float* ws,
+                             int B, int nq, int nkv, int max_ctx, int nsplit, float scale, void* stream);
+/* trace_op_qkv_finish for kv8 arrays: the same sums (chunk order), rounding to the element type and RoPE; the roped q heads go to q_out as there; the
+ * new k row and v column of row b are quantised by the rule above and stored at position pos[b] of slot slots[b] — 128 + 128 bytes and the two scales
+ * per kv head, nothing else.  Errors as trace_op_qkv_finish. */
+int trace_op_qkv_finish_kv8(const float* part, int ks_chunks, void* q_out, void* k8, void* v8, float* ks, float* vs, const int32_t* slots,
+                            const int32_t* pos, const float* cos_t, const float* sin_t, int B, int nq, int nkv, int num_slots, int max_ctx, void* stream);
+/* 16-bit rows -> kv8: k_rows (roped) / v_rows [B][nkv][R][128], both row-major, become positions pos0 .. pos0 + R - 1 of slot slots[b] (int32 [B]
+ * device); nothing outside those positions is written.  TRACE_ERR_ARG before any launch: B above trace_op_sk_rows(), a slot outside [0, num_slots) or
+ * given twice, rows outside [0, max_ctx), max_ctx % 32. */
+int trace_op_kv8_pack(const void* k_rows, const void* v_rows, void* k8, void* v8, float* ks, float* vs, const int32_t* slots, int pos0, int R, int B,
+                      int nkv, int num_slots, int max_ctx, void* stream);
+/* kv8 -> 16-bit: positions 0 .. R - 1 of slot slots[b] as round16(s * e4m3) into row b of k_out [B][nkv][max_ctx][128] / vt_out [B][nkv][128][max_ctx]
+ * (the 16-bit cache's layout); positions from R on are not written.  Errors as above. */
+int trace_op_kv8_unpack(const void* k8, const void* v8, const float* ks, const float* vs, const int32_t* slots, void* k_out, void* vt_out, int R, int B,
+                        int nkv, int num_slots, int max_ctx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,10 @@ class TraceConfigC(C.Structure):
     ]
 
 
+class TraceCtxOptsC(C.Structure):
+    _fields_ = [("size", C.c_int32), ("kv_cache_fp8", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/trace_hip.h declares
 P, I, F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
@@ -35,6 +39,8 @@ SIGNATURES = {
     "trace_abi_version": (I, []),
     "trace_element_type": (I, []),
     "trace_ctx_create": (I, [C.POINTER(TraceConfigC), I, C.POINTER(P)]),
+    "trace_ctx_create_opts": (I, [C.POINTER(TraceConfigC), I, C.POINTER(TraceCtxOptsC), C.POINTER(P)]),
+    "trace_ctx_kv_cache_type": (I, [P]),
     "trace_ctx_destroy": (I, [P]),
     "trace_ctx_load_tensor": (I, [P, C.c_char_p, P, I, C.POINTER(C.c_int64), I]),
     "trace_ctx_finalize": (I, [P]),
@@ -67,6 +73,7 @@ SIGNATURES = {
     "trace_set_gemm_cus": (I, [P, I]),
     "trace_set_profile": (I, [P, I]),
     "trace_debug_buffers": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64)]),
+    "trace_debug_kv8_buffers": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64)]),
     "trace_get_profile": (I, [P, P, I]),
     "trace_set_profile_brackets": (I, [P, I]),
     "trace_op_gemm": (I, [P, I, P, I, P, I, P, P, I, I, I, I, I, P]),
@@ -102,9 +109,13 @@ SIGNATURES = {
     "trace_op_attn_decode": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
     "trace_op_qkv_finish": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "trace_op_attn_decode_fused": (I, [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P]),
+    "trace_op_attn_decode_kv8": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, P]),
+    "trace_op_qkv_finish_kv8": (I, [P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "trace_op_kv8_pack": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "trace_op_kv8_unpack": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
 }
 
-NOT_A_STATUS = {"trace_abi_version", "trace_element_type", "trace_op_skinny_ks", "trace_op_sk_rows", "trace_op_gemm_partial_ks"}   # ints that are values
+NOT_A_STATUS = {"trace_abi_version", "trace_element_type", "trace_ctx_kv_cache_type", "trace_op_skinny_ks", "trace_op_sk_rows", "trace_op_gemm_partial_ks"}   # ints that are values
 _libs = {}
 
 

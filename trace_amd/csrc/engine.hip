@@ -76,6 +76,14 @@ struct trace_ctx {
     // KV cache: K [layer][slot][kvh][ctx_pad][hd] row-major; V TRANSPOSED [layer][slot][kvh][hd][ctx_pad] (decode.hip)
     bf16_t *kcache, *vcache;
     size_t kv_head_stride, slot_stride, layer_stride;
+    // e4m3 KV cache (trace_ctx_create_opts, kv8.hip): K8 / V8 bytes [layer][slot][kvh][...] with the strides above in BYTES, ks / vs fp32 with those / HD,
+    // instead of kcache / vcache; kv_stage_k / kv_stage_v = ONE layer's 16-bit K / V^T of PF_MAX_N slots (the strides above in elements) that every layer's
+    // prefill attention runs on before its rows are packed; d_ident = 0 .. MAX_SLOTS - 1 (slot lists of the pack / unpack launches)
+    int kv8 = 0;
+    uint8_t *k8cache = nullptr, *v8cache = nullptr;
+    float *kscache = nullptr, *vscache = nullptr;
+    bf16_t *kv_stage_k = nullptr, *kv_stage_v = nullptr;
+    int32_t* d_ident = nullptr;
     // ViT workspaces
     bf16_t *vX, *vH, *vQKV, *vVT, *vMLP;
     bf16_t *sl_res, *sl_out, *video;     // [T*S, vh], [T*S, H], [T*TPF, H]
@@ -138,7 +146,8 @@ struct trace_ctx {
     std::vector<hipStream_t> streams;   // trace_stream_create
     // profiling
     int profile = 0;                  // 1: time decode_steps calls; 2: also bracket the layer-0 gate|up GEMV launch
-    int bracket_mask = 3;             // which per-launch brackets profile == 2 takes: bit 0 = the ViT fc1 GEMM, bit 1 = the decode step's kernel
+    int bracket_mask = 3;             // which per-launch brackets profile == 2 takes: bit 0 = the ViT fc1 GEMM, bit 1 = the decode step's kernel; instead of
+                                      // bit 1, bit 2 = the layer-0 decode attention of every step body, bit 3 = the layer-0 append launch (qkv_finish)
                                       // (trace_set_profile_brackets: a pipelined caller switches a stage's bracket off while the other stage's
                                       // kernels share the GPU with it — an event pair then times the queueing, not the kernel)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -154,7 +163,7 @@ struct trace_ctx {
     double vsum_ms[3] = {0.0, 0.0, 0.0}; double vflops[3] = {0.0, 0.0, 0.0};
     float prof[20] = {0};
     int bracket_kind = 0;             // which launch the decode bracket of profile == 2 was put around: 0 none yet, 1 = gate|up GEMV (skinny path), 2 = the fused-norm
-                                      // gate|up GEMV of a batch-1 step, 3 = the wide step's layer-0 decode attention
+                                      // gate|up GEMV of a batch-1 step, 3 = the layer-0 decode attention, 4 = the layer-0 append launch
 };
 
 template <typename T>
@@ -291,13 +300,25 @@ extern "C" int trace_op_gemm_route(int M, int N, int K, int lda, int ldw, int ld
 extern "C" int trace_abi_version(void) { return TRACE_ABI_VERSION; }
 extern "C" int trace_element_type(void) { return TRACE_ELEMENT_TYPE; }
 
-extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ctx** out) {
+static int ctx_create(const trace_config* cfg, int device_id, int kv8, trace_ctx** out);
+extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ctx** out) { return ctx_create(cfg, device_id, 0, out); }
+extern "C" int trace_ctx_create_opts(const trace_config* cfg, int device_id, const trace_ctx_opts* opts, trace_ctx** out) {
+    if (!cfg || !out) return fail(TRACE_ERR_ARG, "null argument");
+    if (opts && opts->size < (int32_t)sizeof(trace_ctx_opts)) return fail(TRACE_ERR_ARG, "trace_ctx_opts::size is smaller than this library's struct");
+    const int kv8 = opts ? opts->kv_cache_fp8 : 0;
+    if (kv8 != 0 && kv8 != 1) return fail(TRACE_ERR_ARG, "kv_cache_fp8 must be 0 or 1");
+    if (kv8 && cfg->llm_weights_fp8) return fail(TRACE_ERR_ARG, "kv_cache_fp8 with llm_weights_fp8: the e4m3 KV cache runs on 16-bit weights only");
+    return ctx_create(cfg, device_id, kv8, out);
+}
+extern "C" int trace_ctx_kv_cache_type(trace_ctx* c) { return c ? c->kv8 : fail(TRACE_ERR_ARG, "null context"); }
+static int ctx_create(const trace_config* cfg, int device_id, int kv8, trace_ctx** out) {
     if (!cfg || !out) return fail(TRACE_ERR_ARG, "null argument");
     g_err.clear();
     HIPCHK(hipSetDevice(device_id));
     trace_ctx* c = new trace_ctx();
     c->c = *cfg;
     c->dev = device_id;
+    c->kv8 = kv8;
     c->H = cfg->hidden_size; c->I = cfg->intermediate_size; c->NL = cfg->num_layers;
     c->NQ = cfg->num_heads; c->NKV = cfg->num_kv_heads; c->HD = c->H / c->NQ;
     c->V = cfg->vocab_size; c->Tv = cfg->time_vocab; c->Sv = cfg->score_vocab;
@@ -377,7 +398,13 @@ extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ct
     c->kv_head_stride = (size_t)c->ctx_pad * c->HD;
     c->slot_stride = c->kv_head_stride * c->NKV;
     c->layer_stride = c->slot_stride * c->max_B;
-    A(c->kcache, c->layer_stride * c->NL); A(c->vcache, c->layer_stride * c->NL);
+    if (c->kv8) {
+        A(c->k8cache, c->layer_stride * c->NL); A(c->v8cache, c->layer_stride * c->NL);
+        A(c->kscache, c->layer_stride / c->HD * c->NL); A(c->vscache, c->layer_stride / c->HD * c->NL);
+        A(c->kv_stage_k, c->slot_stride * PF_MAX_N); A(c->kv_stage_v, c->slot_stride * PF_MAX_N);
+        A(c->d_ident, MAX_SLOTS);
+        c->kcache = c->vcache = nullptr;
+    } else { A(c->kcache, c->layer_stride * c->NL); A(c->vcache, c->layer_stride * c->NL); }
     // --- ViT workspaces ---
     const size_t Tm = cfg->max_frames, Tv_ = c->vit_frames, Mv = Tv_ * c->NT;      // tower workspaces: vit_batch_frames at a time
     A(c->vX, Mv * vh); A(c->vH, Mv * vh); A(c->vQKV, Mv * 3 * vh); A(c->vVT, Tv_ * vh * c->tokpad);
@@ -429,6 +456,11 @@ extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ct
 #undef A
     if (rc == TRACE_OK && hipHostMalloc((void**)&c->h_ring, Lm * 8 * trace_ctx::NSTAGE_H) != hipSuccess) rc = fail(TRACE_ERR_HIP, "hipHostMalloc");
     if (rc != TRACE_OK) { trace_ctx_destroy(c); return rc; }
+    if (c->kv8) {
+        std::vector<int32_t> ident(MAX_SLOTS);
+        for (int i = 0; i < MAX_SLOTS; ++i) ident[i] = i;
+        if (hipMemcpy(c->d_ident, ident.data(), MAX_SLOTS * 4, hipMemcpyHostToDevice) != hipSuccess) { trace_ctx_destroy(c); return fail(TRACE_ERR_HIP, "hipMemcpy"); }
+    }
     c->h_len = Lm;
     c->h_kind = c->h_ring; c->h_row = c->h_kind + Lm;
     for (int i = 0; i < trace_ctx::NSTAGE_H; ++i) hipEventCreateWithFlags(&c->h_ev[i], hipEventDisableTiming);
@@ -1086,8 +1118,21 @@ extern "C" int trace_preprocess_frames(trace_ctx* c, const void* frames_u8, int 
 // past > 0 (trace_llm_prefill_append): every target slot already holds `past` rows; the nb x L new rows take positions past .. past + L - 1
 // (RoPE, cache rows) and attend the cached rows 0 .. past - 1 as well: query row i of a prompt sees keys <= i + past.  Every kernel is the one
 // the past == 0 call runs, every per-row sum in the same order: a row's bits do not depend on where the prompt was cut (tests/test_gpu_prefix_reuse.py).
+// Under the e4m3 KV cache (c->kv8) the K / V^T the prefill kernels write and attend are ONE layer's 16-bit staging rows, prompt b in staging slot b:
+// the same launches on other pointers, so a past == 0 prefill computes the bits of the 16-bit-cache context.  After a layer's attention kv8_pack moves rows
+// past .. past + L - 1 into the cache; with past > 0 kv8_unpack first fills staging rows 0 .. past - 1 from it, so the new rows attend the QUANTISED past
+// (what the decode steps will see) — deterministic, but not the bits of an uncut prefill.
+static Kv8Cache kv8_layer(const trace_ctx* c, int l) {
+    return Kv8Cache{c->k8cache + (size_t)l * c->layer_stride, c->v8cache + (size_t)l * c->layer_stride, c->kscache + (size_t)l * (c->layer_stride / c->HD),
+                    c->vscache + (size_t)l * (c->layer_stride / c->HD), (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad};
+}
+static int prefill_kv8_pack(trace_ctx* c, int l, int slot0, int nb, int L, int past, hipStream_t s) {
+    return launch_kv8_pack(c->kv_stage_k + (size_t)past * c->HD, (long)c->slot_stride, (long)c->kv_head_stride, c->HD,
+                           c->pQKV + (size_t)(c->NQ + c->NKV) * c->HD, (long)L * c->QKV, c->HD, c->QKV, kv8_layer(c, l), c->d_ident + slot0, past, L, nb, c->NKV, s);
+}
 static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out, hipStream_t s, int past = 0) {
     const int H = c->H, I = c->I, HD = c->HD, QKV = c->QKV, M = nb * L;
+    const int kslot0 = c->kv8 ? 0 : slot0;            // first K / V^T slot the layer's kernels use
     AttnArgs a{};
     a.Q = c->pQKV; a.O = c->pO;
     a.q_bs = (long)L * QKV; a.q_hs = HD; a.q_rs = QKV;
@@ -1098,8 +1143,10 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
     a.scale = 1.0f / sqrtf((float)HD); a.causal = 1;
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
-        bf16_t* kc = c->kcache + (size_t)l * c->layer_stride;
-        bf16_t* vc = c->vcache + (size_t)l * c->layer_stride;
+        bf16_t* kc = c->kv8 ? c->kv_stage_k : c->kcache + (size_t)l * c->layer_stride;
+        bf16_t* vc = c->kv8 ? c->kv_stage_v : c->vcache + (size_t)l * c->layer_stride;
+        if (c->kv8 && past > 0)
+            LCHK(launch_kv8_unpack(kv8_layer(c, l), c->d_ident + slot0, kc, vc, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, past, nb, c->NKV, s));
         LCHK(launch_rmsnorm(c->pX, H, c->pH, H, W.rms1, M, H, c->c.rms_eps, s));
         // Round 6: the LAST decoder layer of a prefill whose caller does not ask for the hidden rows.  What is consumed afterwards is the layer's K / V
         // rows of every position (the cache) and the final hidden state of each prompt's LAST row only (the reference computes all L rows of
@@ -1111,16 +1158,17 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
             const size_t last = (size_t)(L - 1);
             TRY(gemm(c->pH, H, W.wqkv + (size_t)QW * H, H, c->pQKV + QW, QKV, nullptr, nullptr, 0, M, KV, H, EPI_NONE, s));
             TRY(gemm(c->pH + last * H, L * H, W.wqkv, H, c->pQKV + last * QKV, L * QKV, nullptr, nullptr, 0, nb, QW, H, EPI_NONE, s));
-            LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, slot0, past, M,
+            LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, kslot0, past, M,
                                 c->NQ, c->NKV, HD, c->rope_cos, c->rope_sin, L, s));      // (also rotates the stale q of the other rows: 10 us, nobody reads them)
-            LCHK(launch_transpose_v(c->pQKV + (size_t)(c->NQ + c->NKV) * HD, (long)L * QKV, HD, QKV, vc + (size_t)slot0 * c->slot_stride,
+            LCHK(launch_transpose_v(c->pQKV + (size_t)(c->NQ + c->NKV) * HD, (long)L * QKV, HD, QKV, vc + (size_t)kslot0 * c->slot_stride,
                                     (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, L, HD, c->NKV, nb, s, 0, past));
             AttnArgs a1 = a;
             a1.Q = c->pQKV + last * QKV; a1.O = c->pO + last * H;
             a1.nq_rows = 1;                                  // one query row per prompt: row L - 1 attends all past + L keys (causal offset nkv - nq)
-            a1.K = kc + (size_t)slot0 * c->slot_stride;
-            a1.V = vc + (size_t)slot0 * c->slot_stride;
+            a1.K = kc + (size_t)kslot0 * c->slot_stride;
+            a1.V = vc + (size_t)kslot0 * c->slot_stride;
             LCHK(launch_attn_prefill(a1, s));
+            if (c->kv8) LCHK(prefill_kv8_pack(c, l, slot0, nb, L, past, s));
             bf16_t* xl = c->pX + last * H;
             bf16_t* hl = c->pH + last * H;
             TRY(gemm(c->pO + last * H, L * H, W.wo, H, xl, L * H, nullptr, xl, L * H, nb, H, H, EPI_RESIDUAL, s));
@@ -1131,14 +1179,15 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
         }
         if (c->fp8) { TRY(gemm_fp8(c, c->pH, H, W.wqkv8, W.sqkv, c->pQKV, QKV, nullptr, 0, M, QKV, H, EPI_NONE, s)); }
         else TRY(gemm(c->pH, H, W.wqkv, H, c->pQKV, QKV, nullptr, nullptr, 0, M, QKV, H, EPI_NONE, s));
-        LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, slot0, past, M,
+        LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, kslot0, past, M,
                             c->NQ, c->NKV, HD, c->rope_cos, c->rope_sin, L, s));
         // V goes into the cache transposed ([kvh][hd][ctx_pad]; positions past+L..Lpad-1 are zero-filled, later overwritten)
-        LCHK(launch_transpose_v(c->pQKV + (size_t)(c->NQ + c->NKV) * HD, (long)L * QKV, HD, QKV, vc + (size_t)slot0 * c->slot_stride,
+        LCHK(launch_transpose_v(c->pQKV + (size_t)(c->NQ + c->NKV) * HD, (long)L * QKV, HD, QKV, vc + (size_t)kslot0 * c->slot_stride,
                                 (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, L, HD, c->NKV, nb, s, 0, past));
-        a.K = kc + (size_t)slot0 * c->slot_stride;
-        a.V = vc + (size_t)slot0 * c->slot_stride;
+        a.K = kc + (size_t)kslot0 * c->slot_stride;
+        a.V = vc + (size_t)kslot0 * c->slot_stride;
         LCHK(launch_attn_prefill(a, s));
+        if (c->kv8) LCHK(prefill_kv8_pack(c, l, slot0, nb, L, past, s));
         if (c->fp8) {
             TRY(gemm_fp8(c, c->pO, H, W.wo8, W.so, c->pX, H, c->pX, H, M, H, H, EPI_RESIDUAL, s));
             LCHK(launch_rmsnorm(c->pX, H, c->pH, H, W.rms2, M, H, c->c.rms_eps, s));
@@ -1228,6 +1277,7 @@ extern "C" int trace_kv_copy(trace_ctx* c, int src_slot, const int32_t* dst_slot
         KvCopyDst d{};
         d.n = std::min(KV_COPY_MAX, n - i0);
         for (int i = 0; i < d.n; ++i) d.slot[i] = dst_slots[i0 + i];
+        if (c->kv8) { LCHK(launch_kv8_copy(kv8_layer(c, 0), (long)c->layer_stride, c->NL, c->NKV, src_slot, d, rows, s)); continue; }
         LCHK(launch_kv_copy(c->kcache, c->vcache, (long)c->layer_stride, (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->HD, c->NL,
                             c->NKV, src_slot, d, rows, s));
     }
@@ -1316,26 +1366,39 @@ static DecodeRoute decode_route(int B, int fp8_scheme, int H, int I, int QKV, co
 // which launch took the bracket (prof[8]).  Eager launches only: event-record nodes captured into a hipGraph do not yield usable timestamps on ROCm 7.2.
 struct StepBracket {
     hipEvent_t e1 = nullptr; hipStream_t s;
-    StepBracket(trace_ctx* c, int l, int kind, hipStream_t s_) : s(s_) {
-        if (l != 0 || c->profile != 2 || !(c->bracket_mask & 2) || s == c->cap_stream || c->kev_used + 2 > (int)c->kev.size()) return;
+    StepBracket(trace_ctx* c, int l, int kind, hipStream_t s_, int bit = 2) : s(s_) {
+        if (l != 0 || c->profile != 2 || !(c->bracket_mask & bit) || s == c->cap_stream || c->kev_used + 2 > (int)c->kev.size()) return;
         hipEventRecord(c->kev[c->kev_used], s);
         e1 = c->kev[c->kev_used + 1]; c->kev_used += 2; c->bracket_kind = kind;
     }
     ~StepBracket() { if (e1) hipEventRecord(e1, s); }
 };
+// algorithmic bytes of one layer's decode attention in the current step: the K + V rows of every sequence, 16-bit, or e4m3 + two scales
+static double attn_kv_bytes(const trace_ctx* c) {
+    return (double)(c->pos_sum + (long)c->B * (c->step_in_call + 1)) * c->NKV * (c->kv8 ? 2 * c->HD + 8 : c->HD * 2 * 2);
+}
 
 // The decode attention of layer l.  Without r.qkv_finish its prologue sums the qkv partial rows part [r.ks_q][SK_ROWS][QKV], applies RoPE and appends
 // k / v to the cache; otherwise dQKV holds ready q rows and the cache the new row (qkv_finish_layer ran).
 static int attn_decode_layer(trace_ctx* c, int l, const DecodeRoute& r, const float* part, hipStream_t s) {
     const bool fused = !r.qkv_finish;
+    StepBracket br(c, l, 3, s, 4);                  // bracket bit 2: this launch in whichever step body runs (with its fused prologue, where it has one)
+    if (br.e1) c->kbytes_sum += attn_kv_bytes(c);
+    if (c->kv8)       // no fused prologue over the e4m3 cache: decode_step sets r.qkv_finish
+        return fused ? TRACE_ERR_STATE
+                     : launch_attn_decode_kv8(c->dQKV, c->QKV, kv8_layer(c, l), c->d_slots, c->d_pos, c->dO, c->H, c->attn_ws, c->tickets, c->B, c->NQ, c->NKV,
+                                              c->HD, r.nsplit, 1.0f / sqrtf((float)c->HD), s);
     return launch_attn_decode(c->dQKV, c->QKV, c->kcache + (size_t)l * c->layer_stride, c->vcache + (size_t)l * c->layer_stride, (long)c->slot_stride,
                               (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->dO, c->H, c->attn_ws, c->tickets, c->B, c->NQ, c->NKV, c->HD,
                               r.nsplit, 1.0f / sqrtf((float)c->HD), fused ? 1 : 0, fused ? c->rope_cos : nullptr, fused ? c->rope_sin : nullptr,
                               fused ? part : nullptr, fused ? r.ks_q : 0, s);
 }
 // that prologue as a launch of its own: the qkv partial rows in sk_ws -> roped q rows in dQKV, k / v of layer l appended
-static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s) {
-    return launch_qkv_finish(c->sk_ws, ks, c->QKV, c->dQKV, c->kcache + (size_t)l * c->layer_stride, c->vcache + (size_t)l * c->layer_stride,
+static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s, const float* part = nullptr) {
+    if (!part) part = c->sk_ws;
+    StepBracket br(c, l, 4, s, 8);                  // bracket bit 3: the append launch
+    if (c->kv8) return launch_qkv_finish_kv8(part, ks, c->QKV, c->dQKV, kv8_layer(c, l), c->d_slots, c->d_pos, c->B, c->NQ, c->NKV, c->rope_cos, c->rope_sin, s);
+    return launch_qkv_finish(part, ks, c->QKV, c->dQKV, c->kcache + (size_t)l * c->layer_stride, c->vcache + (size_t)l * c->layer_stride,
                              (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->B, c->NQ, c->NKV, c->rope_cos, c->rope_sin, s);
 }
 
@@ -1346,7 +1409,7 @@ static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s) {
 // load.  The weights (14 GB per step) are then streamed once per 128 tokens instead of once per 64: bytes per token 0.50 -> 0.39 GB at
 // ctx ~2100, where the KV stream (0.27 GB per token) is the larger part.
 static int decode_step_wide(trace_ctx* c, const DecodeRoute& r, float* logits_out, hipStream_t s) {
-    const int H = c->H, I = c->I, HD = c->HD, QKV = c->QKV, B = c->B;
+    const int H = c->H, I = c->I, QKV = c->QKV, B = c->B;
     if (c->fp8) return fail(TRACE_ERR_STATE, "the fp8 weight path decodes at most 64 sequences together");
     const int wt = g_tune.decode_gemm_tiled;
     auto pgemm = [&](const bf16_t* A, int lda, const bf16_t* Wrow, const bf16_t* Wtile, int ldw, int N, int K, int ks) -> int {
@@ -1361,7 +1424,7 @@ static int decode_step_wide(trace_ctx* c, const DecodeRoute& r, float* logits_ou
         if (r.qkv_finish) LCHK(qkv_finish_layer(c, l, r.ks_q, s));
         {   // bracketed: the layer-0 decode attention, which streams the batch's whole KV cache of that layer
             StepBracket br(c, l, 3, s);
-            if (br.e1) c->kbytes_sum += (double)(c->pos_sum + (long)B * (c->step_in_call + 1)) * c->NKV * HD * 2 * 2;   // K + V^T rows of every sequence, bf16
+            if (br.e1) c->kbytes_sum += attn_kv_bytes(c);
             LCHK(attn_decode_layer(c, l, r, c->sk_ws, s));
         }
         TRY(pgemm(c->dO, H, W.wo, W.wo_d, H, H, H, r.ks_o));
@@ -1390,6 +1453,7 @@ static int decode_step_fused(trace_ctx* c, const DecodeRoute& r, float* logits_o
         LCHK(launch_skinny_gemm_fused_norm(l ? c->sk_ws : nullptr, l ? r.ks_d : 0, xa, H, xb, H, W.rms1, c->c.rms_eps, W.wqkv_d, B, QKV, H, c->sk_ws2,
                                            c->sk_ws_floats, s));
         std::swap(xa, xb);
+        if (r.qkv_finish) LCHK(qkv_finish_layer(c, l, r.ks_q, s, c->sk_ws2));      // (the e4m3 KV cache only: this step's 16-bit form always fuses the append)
         LCHK(attn_decode_layer(c, l, r, c->sk_ws2, s));
         LCHK(launch_skinny_gemm(c->dO, H, W.wo_d, H, nullptr, H, nullptr, 0, B, H, H, EPI_PARTIAL, 1, SKWS(c), s));
         {
@@ -1455,7 +1519,8 @@ static int decode_step_skinny(trace_ctx* c, const DecodeRoute& r, float* logits_
 
 // one decode step for the current batch: consumes dX (embedding of the last token), leaves the next one in dX
 static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
-    const DecodeRoute r = decode_route(c->B, c->fp8 ? 1 + c->fp8_wonly : 0, c->H, c->I, c->QKV, g_tune);    // (fp8 contexts: at most 64 rows, checked at begin)
+    DecodeRoute r = decode_route(c->B, c->fp8 ? 1 + c->fp8_wonly : 0, c->H, c->I, c->QKV, g_tune);    // (fp8 contexts: at most 64 rows, checked at begin)
+    if (c->kv8) r.qkv_finish = true;                 // the e4m3 KV cache always appends with a launch of its own (qkv_finish_kv8), in every step body
     return r.step == 3 ? decode_step_wide(c, r, logits_out, s) : r.step == 2 ? decode_step_fused(c, r, logits_out, s) : decode_step_skinny(c, r, logits_out, s);
 }
 
@@ -1735,7 +1800,16 @@ extern "C" int trace_set_gemm_cus(trace_ctx* c, int n) {
 // debugging aid (tools/pipeline_stress.py): device addresses and element strides of the KV caches and of the prefill's last-position hidden rows
 extern "C" int trace_debug_buffers(trace_ctx* c, void** kcache, void** vcache, void** xlast, int64_t* strides) {
     if (!c || !kcache || !vcache || !xlast || !strides) return fail(TRACE_ERR_ARG, "null argument");
+    if (c->kv8) return fail(TRACE_ERR_STATE, "this context keeps an e4m3 KV cache: trace_debug_kv8_buffers");
     *kcache = c->kcache; *vcache = c->vcache; *xlast = c->xlast;
+    strides[0] = (int64_t)c->layer_stride; strides[1] = (int64_t)c->slot_stride; strides[2] = (int64_t)c->kv_head_stride; strides[3] = c->ctx_pad;
+    strides[4] = c->NL; strides[5] = c->NKV; strides[6] = c->HD; strides[7] = c->H;
+    return TRACE_OK;
+}
+extern "C" int trace_debug_kv8_buffers(trace_ctx* c, void** k8, void** v8, void** ks, void** vs, int64_t* strides) {
+    if (!c || !k8 || !v8 || !ks || !vs || !strides) return fail(TRACE_ERR_ARG, "null argument");
+    if (!c->kv8) return fail(TRACE_ERR_STATE, "this context keeps a 16-bit KV cache: trace_debug_buffers");
+    *k8 = c->k8cache; *v8 = c->v8cache; *ks = c->kscache; *vs = c->vscache;
     strides[0] = (int64_t)c->layer_stride; strides[1] = (int64_t)c->slot_stride; strides[2] = (int64_t)c->kv_head_stride; strides[3] = c->ctx_pad;
     strides[4] = c->NL; strides[5] = c->NKV; strides[6] = c->HD; strides[7] = c->H;
     return TRACE_OK;
@@ -1748,7 +1822,7 @@ extern "C" int trace_set_profile(trace_ctx* c, int on) {
 }
 extern "C" int trace_set_profile_brackets(trace_ctx* c, int mask) {
     if (!c) return fail(TRACE_ERR_ARG, "null ctx");
-    c->bracket_mask = mask & 3;
+    c->bracket_mask = mask & 15;
     return TRACE_OK;
 }
 extern "C" int trace_get_profile(trace_ctx* c, float* out, int n) {
@@ -1982,5 +2056,78 @@ extern "C" int trace_op_attn_decode_fused(const float* part, int ks, void* kcach
     TRY(op_check_slots_pos(slots, pos, B, num_slots, max_ctx, s));
     LCHK(launch_attn_decode(nullptr, (nq + 2 * nkv) * 128, (bf16_t*)kcache, (bf16_t*)vtcache, (long)nkv * max_ctx * 128, (long)max_ctx * 128, max_ctx,
                             slots, pos, (bf16_t*)O, nq * 128, ws, g_op_tickets, B, nq, nkv, 128, nsplit, scale, 1, cos_t, sin_t, part, ks, s));
+    return TRACE_OK;
+}
+
+// ---- e4m3 KV cache hooks (kv8.hip; tests/test_gpu_kv8_probes.py) ----
+// loose arrays k8 [num_slots][nkv][max_ctx][128], v8 [num_slots][nkv][max_ctx/32][128][32], ks / vs [num_slots][nkv][max_ctx]
+static Kv8Cache op_kv8(void* k8, void* v8, float* ks, float* vs, int nkv, int max_ctx) {
+    return Kv8Cache{(uint8_t*)k8, (uint8_t*)v8, ks, vs, (long)nkv * max_ctx * 128, (long)max_ctx * 128, max_ctx};
+}
+static int op_check_pos(const int32_t* pos, int B, int max_ctx, hipStream_t s) {
+    if (!pos) return fail(TRACE_ERR_ARG, "null pos");
+    std::vector<int32_t> hp(B);
+    HIPCHK(hipMemcpyAsync(hp.data(), pos, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b)
+        if (hp[b] < 0 || hp[b] >= max_ctx) return fail(TRACE_ERR_ARG, "position out of range");
+    return TRACE_OK;
+}
+static int op_check_slots(const int32_t* slots, int B, int num_slots, hipStream_t s) {
+    if (!slots || num_slots < 1) return fail(TRACE_ERR_ARG, "null slots");
+    std::vector<int32_t> hs(B);
+    HIPCHK(hipMemcpyAsync(hs.data(), slots, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<char> seen(num_slots, 0);
+    for (int b = 0; b < B; ++b) {
+        if (hs[b] < 0 || hs[b] >= num_slots) return fail(TRACE_ERR_ARG, "slot out of range");
+        if (seen[hs[b]]) return fail(TRACE_ERR_ARG, "slot given twice");
+        seen[hs[b]] = 1;
+    }
+    return TRACE_OK;
+}
+extern "C" int trace_op_attn_decode_kv8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs, const int32_t* pos, void* O,
+                                        float* ws, int B, int nq, int nkv, int max_ctx, int nsplit, float scale, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!q || !k8 || !v8 || !ks || !vs || !O || !ws) return fail(TRACE_ERR_ARG, "null argument");
+    TRY(op_attn_decode_state(B, nq, nkv, max_ctx, nsplit));
+    TRY(op_check_pos(pos, B, max_ctx, s));
+    LCHK(launch_attn_decode_kv8((const bf16_t*)q, nq * 128, op_kv8((void*)k8, (void*)v8, (float*)ks, (float*)vs, nkv, max_ctx), g_op_slots, pos, (bf16_t*)O,
+                                nq * 128, ws, g_op_tickets, B, nq, nkv, 128, nsplit, scale, s));
+    return TRACE_OK;
+}
+extern "C" int trace_op_qkv_finish_kv8(const float* part, int ks_chunks, void* q_out, void* k8, void* v8, float* ks, float* vs, const int32_t* slots,
+                                       const int32_t* pos, const float* cos_t, const float* sin_t, int B, int nq, int nkv, int num_slots, int max_ctx,
+                                       void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!part || !q_out || !k8 || !v8 || !ks || !vs || !cos_t || !sin_t || ks_chunks < 1) return fail(TRACE_ERR_ARG, "null argument");
+    TRY(op_attn_decode_state(B, nq, nkv, max_ctx, 1));
+    TRY(op_check_slots_pos(slots, pos, B, num_slots, max_ctx, s));
+    LCHK(launch_qkv_finish_kv8(part, ks_chunks, (nq + 2 * nkv) * 128, (bf16_t*)q_out, op_kv8(k8, v8, ks, vs, nkv, max_ctx), slots, pos, B, nq, nkv, cos_t,
+                               sin_t, s));
+    return TRACE_OK;
+}
+extern "C" int trace_op_kv8_pack(const void* k_rows, const void* v_rows, void* k8, void* v8, float* ks, float* vs, const int32_t* slots, int pos0, int R,
+                                 int B, int nkv, int num_slots, int max_ctx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!k_rows || !v_rows || !k8 || !v8 || !ks || !vs) return fail(TRACE_ERR_ARG, "null argument");
+    if (B < 1 || B > SK_ROWS) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(SK_ROWS) + " rows)");
+    if (nkv < 1 || nkv > OP_ATTN_MAX_KV || max_ctx < 32 || max_ctx % 32) return fail(TRACE_ERR_ARG, "bad kv8 cache shape");
+    if (R < 1 || pos0 < 0 || (long)pos0 + R > max_ctx) return fail(TRACE_ERR_ARG, "rows outside the slot");
+    TRY(op_check_slots(slots, B, num_slots, s));
+    LCHK(launch_kv8_pack((const bf16_t*)k_rows, (long)nkv * R * 128, (long)R * 128, 128, (const bf16_t*)v_rows, (long)nkv * R * 128, (long)R * 128, 128,
+                         op_kv8(k8, v8, ks, vs, nkv, max_ctx), slots, pos0, R, B, nkv, s));
+    return TRACE_OK;
+}
+extern "C" int trace_op_kv8_unpack(const void* k8, const void* v8, const float* ks, const float* vs, const int32_t* slots, void* k_out, void* vt_out,
+                                   int R, int B, int nkv, int num_slots, int max_ctx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!k8 || !v8 || !ks || !vs || !k_out || !vt_out) return fail(TRACE_ERR_ARG, "null argument");
+    if (B < 1 || B > SK_ROWS) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(SK_ROWS) + " rows)");
+    if (nkv < 1 || nkv > OP_ATTN_MAX_KV || max_ctx < 32 || max_ctx % 32) return fail(TRACE_ERR_ARG, "bad kv8 cache shape");
+    if (R < 1 || R > max_ctx) return fail(TRACE_ERR_ARG, "rows outside the slot");
+    TRY(op_check_slots(slots, B, num_slots, s));
+    LCHK(launch_kv8_unpack(op_kv8((void*)k8, (void*)v8, (float*)ks, (float*)vs, nkv, max_ctx), slots, (bf16_t*)k_out, (bf16_t*)vt_out,
+                           (long)nkv * max_ctx * 128, (long)max_ctx * 128, max_ctx, R, B, nkv, s));
     return TRACE_OK;
 }

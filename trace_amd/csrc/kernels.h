@@ -259,6 +259,26 @@ int launch_skinny_fp8(const uint8_t* X8, long ldx, const float* sx, const uint8_
 int launch_skinny_w8(const bf16_t* X, long ldx, const uint8_t* Wtiled, const float* sw, int B, int N, int K, float* ws, size_t ws_floats,
                      hipStream_t s);
 
+// ---- e4m3 KV cache (kv8.hip; the format is stated in include/trace_hip.h) ----
+// The four arrays of one layer: K8 [slot][kvh][ctx_pad][128] bytes, V8 [slot][kvh][ctx_pad/32][128][32] bytes (position-blocked V^T), ks / vs
+// [slot][kvh][ctx_pad] fp32.  slot_stride / kv_head_stride in payload bytes (kv_head_stride = ctx_pad * 128); the scales' strides are those / 128.
+struct Kv8Cache { uint8_t* k8; uint8_t* v8; float* ks; float* vs; long slot_stride; long kv_head_stride; int ctx_pad; };
+// launch_attn_decode's unfused form over a kv8 cache (4 waves): q [B][ldq] rotated, the newest position already in the cache
+int launch_attn_decode_kv8(const bf16_t* q, int ldq, const Kv8Cache& c, const int32_t* slots, const int32_t* pos, bf16_t* O, int ldo, float* ws,
+                           unsigned int* tickets, int B, int nq, int nkv, int hd, int nsplit, float scale, hipStream_t s);
+// launch_qkv_finish for a kv8 cache: roped q rows to qout, the new k row / v column quantised and stored with their scales at pos[b] of slots[b]
+int launch_qkv_finish_kv8(const float* part, int ks, int ldq, bf16_t* qout, const Kv8Cache& c, const int32_t* slots, const int32_t* pos, int B, int nq,
+                          int nkv, const float* cos_t, const float* sin_t, hipStream_t s);
+// 16-bit row-major K (roped) / V rows r = 0 .. R-1 (element d of (b, kvh, r) at b * bs + kvh * hs + r * rs + d) -> positions pos0 + r of slot slots[b]
+int launch_kv8_pack(const bf16_t* K, long k_bs, long k_hs, long k_rs, const bf16_t* V, long v_bs, long v_hs, long v_rs, const Kv8Cache& c,
+                    const int32_t* slots, int pos0, int R, int B, int nkv, hipStream_t s);
+// positions [0, R) of slot slots[b] -> row b of K [.][kvh][pos][128] / V^T [.][kvh][128][ctx_stride] (strides dst_bs / dst_hs) as round16(scale * e4m3)
+int launch_kv8_unpack(const Kv8Cache& c, const int32_t* slots, bf16_t* K, bf16_t* Vt, long dst_bs, long dst_hs, int ctx_stride, int R, int B, int nkv,
+                      hipStream_t s);
+// launch_kv_copy for the four arrays of every layer (c = layer 0's; layer_stride in payload bytes): positions [0, round_up(rows, 32)) of slot src to
+// the dst slots — whole 32-position blocks, so the tail holds finite values that a later append overwrites
+int launch_kv8_copy(const Kv8Cache& c, long layer_stride, int layers, int kv_heads, int src, const KvCopyDst& dst, int rows, hipStream_t s);
+
 // ---- STC connector support (stc.hip): channels-last [n][h][w][C] row kernels ----
 int launch_dwconv3x3(const bf16_t* x, const bf16_t* w /*[C][9]*/, bf16_t* y, int N, int H, int W, int C, hipStream_t s);
 int launch_avgpool(const bf16_t* x, bf16_t* y /*[N][C]*/, int N, int HW, int C, hipStream_t s);

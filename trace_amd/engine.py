@@ -36,8 +36,12 @@ def _i32(seq) -> "C.Array":
 class TraceEngine:
     def __init__(self, cfg: TraceConfig, device: int = 0, max_batch: int = 1, max_ctx: Optional[int] = None,
                  max_frames: Optional[int] = None, max_new_tokens: int = 1024, vit_batch_frames: Optional[int] = None,
-                 llm_fp8=False, dtype: torch.dtype = torch.bfloat16):
-        """dtype: the 16-bit element type everything is stored and multiplied in — torch.bfloat16 (libtrace_hip.so; north_star's configs) or
+                 llm_fp8=False, dtype: torch.dtype = torch.bfloat16, kv_cache=None):
+        """kv_cache: None = the KV cache in the 16-bit element type; "fp8" = e4m3 bytes with one fp32 scale per position and kv head (trace_amd/kv8.py:
+        264 bytes per position and kv head instead of 512).  Under "fp8" a prefill of whole prompts computes the bits of the 16-bit-cache engine, the
+        decode steps attend the quantised rows, and prefill_append / enable_prefix_cache() continue from the QUANTISED prefix: their "bit-identical to
+        an uncut prefill" promise is the 16-bit cache's — under "fp8" the guarantee is determinism.  Not with llm_fp8.
+        dtype: the 16-bit element type everything is stored and multiplied in — torch.bfloat16 (libtrace_hip.so; north_star's configs) or
         torch.float16 (libtrace_hip_f16.so: the reference's own inference dtype, trace/model/builder.py:50,127,147); accumulation is fp32 in both."""
         # llm_fp8: False / None = bf16 weights; "w8a8" (True is accepted as its alias) = W8A8 prefill GEMMs and decode GEMVs; "weight_only" = W8A8
         # prefill GEMMs, weight-only decode GEMVs (bf16 activations).  Anything else is an error — a typo must not silently pick a numerics scheme.
@@ -51,6 +55,11 @@ class TraceEngine:
             raise ValueError(f"llm_fp8 must be False, True / 'w8a8' or 'weight_only', got {llm_fp8!r}")
         if self.fp8_scheme and dtype != torch.bfloat16:
             raise ValueError("the fp8 weight path exists in the bf16 library only")
+        if kv_cache not in (None, "fp8"):
+            raise ValueError(f"kv_cache must be None or 'fp8', got {kv_cache!r}")
+        if kv_cache and self.fp8_scheme:
+            raise ValueError("kv_cache='fp8' with llm_fp8: fp8 weights over an fp8 KV cache is not supported")
+        self.kv_cache = kv_cache
         if not torch.cuda.is_available():
             raise _lib.TraceHipError("no HIP device visible: the TRACE hot path only runs on an MI355X (no CPU fallback)")
         self.dtype = dtype
@@ -77,7 +86,11 @@ class TraceEngine:
             {None: 0, "w8a8": 1, "weight_only": 2}[self.fp8_scheme])
         self.llm_fp8 = self.fp8_scheme is not None
         h = C.c_void_p()
-        _lib.check(self.lib.trace_ctx_create(C.byref(c), device, C.byref(h)))
+        if kv_cache:
+            o = _lib.TraceCtxOptsC(C.sizeof(_lib.TraceCtxOptsC), 1)
+            _lib.check(self.lib.trace_ctx_create_opts(C.byref(c), device, C.byref(o), C.byref(h)))
+        else:
+            _lib.check(self.lib.trace_ctx_create(C.byref(c), device, C.byref(h)))
         self.h = h
         self.time_tower, self.score_tower = TimeTower(), ScoreTower()
         self._B = 0
@@ -1083,6 +1096,53 @@ class ops:
         _lib.check(lib.trace_op_attn_decode_fused(_ptr(part), part.shape[0], _ptr(kcache), _ptr(vtcache), _ptr(slots), _ptr(pos), _ptr(cos_t),
                                                   _ptr(sin_t), _ptr(o), _ptr(ws), Bn, nq, nkv, S, max_ctx, nsplit, scale, _stream()))
         return o
+
+    # ---- e4m3 KV cache (trace_amd/kv8.py states the format and the four arrays) ----
+    @staticmethod
+    def attn_decode_kv8(q, k8, v8, ks, vs, pos, nsplit, scale):
+        """q [B, nq*128] rotated; k8 uint8 [B, nkv, max_ctx, 128], v8 uint8 [B, nkv, max_ctx/32, 128, 32], ks / vs fp32 [B, nkv, max_ctx] (row b in
+        slot b); pos int32 [B] (device) -> [B, nq*128]"""
+        lib = _lib.load(ops.element)
+        Bn, nq = q.shape[0], q.shape[1] // 128
+        nkv, max_ctx = k8.shape[1], k8.shape[2]
+        ws = torch.zeros((Bn * nq * nsplit * 130,), dtype=torch.float32, device=q.device)
+        o = torch.empty_like(q)
+        _lib.check(lib.trace_op_attn_decode_kv8(_ptr(q), _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), _ptr(pos), _ptr(o), _ptr(ws), Bn, nq, nkv, max_ctx,
+                                                nsplit, scale, _stream()))
+        return o
+
+    @staticmethod
+    def qkv_finish_kv8(part, k8, v8, ks, vs, slots, pos, cos_t, sin_t, nq):
+        """ops.qkv_finish for kv8 arrays [S, ...]: roped q rows [B, nq * 128]; the new k row / v column quantised and stored IN PLACE with their scales"""
+        lib = _lib.load(ops.element)
+        S, nkv, max_ctx = k8.shape[0], k8.shape[1], k8.shape[2]
+        Bn = pos.shape[0]
+        qkv = torch.zeros((Bn, (nq + 2 * nkv) * 128), dtype=ops.dtype(), device=part.device)
+        _lib.check(lib.trace_op_qkv_finish_kv8(_ptr(part), part.shape[0], _ptr(qkv), _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), _ptr(slots), _ptr(pos),
+                                               _ptr(cos_t), _ptr(sin_t), Bn, nq, nkv, S, max_ctx, _stream()))
+        return qkv[:, :nq * 128].contiguous()
+
+    @staticmethod
+    def kv8_pack(k_rows, v_rows, k8, v8, ks, vs, slots, pos0):
+        """k_rows (roped) / v_rows [B, nkv, R, 128] in the element type -> positions pos0 .. pos0 + R - 1 of slot slots[b] of the kv8 arrays, IN PLACE"""
+        lib = _lib.load(ops.element)
+        Bn, nkv, R = k_rows.shape[0], k_rows.shape[1], k_rows.shape[2]
+        _lib.check(lib.trace_op_kv8_pack(_ptr(k_rows.contiguous()), _ptr(v_rows.contiguous()), _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), _ptr(slots),
+                                         pos0, R, Bn, nkv, k8.shape[0], k8.shape[2], _stream()))
+
+    @staticmethod
+    def kv8_unpack(k8, v8, ks, vs, slots, R, k_out=None, vt_out=None):
+        """positions 0 .. R - 1 of slot slots[b] -> row b of (k [B, nkv, max_ctx, 128], V^T [B, nkv, 128, max_ctx]) in the element type; positions from R
+        on keep what k_out / vt_out held (zeros when they are made here)"""
+        lib = _lib.load(ops.element)
+        Bn, nkv, max_ctx = slots.shape[0], k8.shape[1], k8.shape[2]
+        if k_out is None:
+            k_out = torch.zeros((Bn, nkv, max_ctx, 128), dtype=ops.dtype(), device=k8.device)
+        if vt_out is None:
+            vt_out = torch.zeros((Bn, nkv, 128, max_ctx), dtype=ops.dtype(), device=k8.device)
+        _lib.check(lib.trace_op_kv8_unpack(_ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), _ptr(slots), _ptr(k_out), _ptr(vt_out), R, Bn, nkv, k8.shape[0],
+                                           max_ctx, _stream()))
+        return k_out, vt_out
 
     # ---- fp8 (e4m3) path pieces ----
     @staticmethod

@@ -171,7 +171,7 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
     # torch_dtype=torch.float16 selects the fp16 library (libtrace_hip_f16.so)
     dtype = kwargs.get("torch_dtype") or torch.bfloat16
     eng = TraceEngine(cfg, device=dev_index, max_batch=max_batch, max_ctx=max_ctx, max_frames=max(T, 1),
-                      max_new_tokens=max_new_tokens, dtype=dtype)
+                      max_new_tokens=max_new_tokens, dtype=dtype, kv_cache=kwargs.get("kv_cache"))      # kv_cache="fp8": the e4m3 KV cache
     if raw.get("synthetic_weights"):
         from .. import synth
         small = cfg.hidden_size * cfg.num_hidden_layers < 4096 * 8
