@@ -160,6 +160,42 @@ int trace_embed_rows(trace_ctx* ctx, const int32_t* ids, int n_ids, const int32_
  * logits_out [R, V+1+Tv+Sv] fp32 device.  The decode loop needs the last row only and gets it from trace_decode_begin / _steps. */
 int trace_llm_head_logits(trace_ctx* ctx, const void* hidden, int R, int head, float* logits_out, void* stream);
 
+/* Scoring GIVEN tokens: how likely is this continuation?  (Multiple-choice scoring of the per-question drivers, trace/eval/videomme/evaluate.py; ranking
+ * candidate captions or moments; teacher-forced log-likelihood of a [time | score | caption] stream.)  trace_decode_begin(forced = ...) with
+ * log-probabilities records the model's OWN choice at every step; these entry points score the ids that are fed.
+ * A continuation is a list of global vocabulary ids c[0 .. n) over [text | <sync> | time | score] and the head h0 active for c[0] (callers pass 1, as
+ * generate does).  The head of position i follows the switch rule of the decode step applied to the FED ids:
+ *     head[0] = h0,   head[i + 1] = c[i] == V ? 1 : c[i] == V + 1 ? 2 : c[i] == V + Tv + 1 ? 0 : head[i]
+ * and its log-probability is
+ *     logprob[i] = (x[c[i]] - M) - log S,   M = max x,   S = sum exp(x - M)
+ * over the raw fp32 logits x of head[i]'s id range [lo, hi), taken from the final-norm hidden row that PRECEDES c[i]: the last prompt row for c[0], the
+ * row fed with the embedding of c[i - 1] otherwise (the decode branch's embedding rule = trace_embed_rows with the matching placeholders).  An id outside
+ * [lo, hi) gives -inf; id -1 means "ignore" (padding) and gives 0.0; a continuation's score is the plain sum of its entries.
+ * The sums, so that a float32 restatement (trace_amd/sampling.py score_logprob_ref) gives the device's bits from the same fp32 logits: the head's range is
+ * cut into column tiles [j CT, (j + 1) CT) on ABSOLUTE ids, CT = trace_op_score_tile() = 128, clipped to [lo, hi).  Per tile: m_j = max x,
+ * s_j = h0 + h1 where h0 / h1 sum exp(x - m_j) over the tile's lower / upper 64 columns, each sequentially in ascending id order from 0.  Then
+ * M = max_j m_j, S = sum_j s_j * exp(m_j - M) sequentially in ascending j from 0 (S >= 1), exp / log = csrc/sample.h sample_exp / sample_log, no FMA
+ * contraction.  The logits themselves are never stored: text rows run a 16-bit MFMA GEMM (K = hidden, fp32 accumulation) against the V + 1 rows of the
+ * lm | sync block whose epilogue leaves (m_j, s_j, x_target) per row and tile; time / score rows (Tv, Sv <= 128) are dot products in the merge kernel.
+ *
+ * trace_op_score_rows: loose rows.  hidden [R][ld], W [V + 1 + Tv + Sv][ldw] head rows in global vocabulary order, both the library's element type,
+ *     row length K (K % 64 == 0, ld / ldw >= K and % 8 == 0); heads / ids int32 [R] DEVICE; ws: trace_op_score_ws_bytes(R, V, Tv, Sv) bytes of device
+ *     scratch; out fp32 [R] device.  R <= 65536.  Heads outside 0..2 are read as 2, ids are not range-checked beyond "outside the head" (device arrays).
+ * trace_llm_score_rows: the same over the context's head matrix; hidden [R][hidden] = final-norm rows (the hidden_out of a prefill), R at most the
+ *     prefill workspace's rows; the scratch is allocated on first use.
+ * trace_llm_score_append: the body of trace_llm_prefill_append for n <= 8 slots followed by the score of all n x L final-norm rows: row (b, i) is
+ *     scored against ids[b * L + i] under heads[b * L + i].  heads / ids are HOST int32 [n * L], out is a HOST float [n * L]; the call synchronises the
+ *     stream.  Afterwards the slots hold past + L rows, as after trace_llm_prefill_append.  Every argument error of trace_llm_prefill_append applies
+ *     (there is no hidden_out here); in addition TRACE_ERR_ARG for a head outside 0..2 and an id < -1 or >= V + 1 + Tv + Sv — all before any launch.
+ *     Works on the fp8-weight paths and under kv_cache_fp8 (where, as for trace_llm_prefill_append, the new rows attend the QUANTISED past). */
+int trace_op_score_tile(void);
+int64_t trace_op_score_ws_bytes(int R, int V, int Tv, int Sv);
+int trace_op_score_rows(const void* hidden, int ld, const void* W, int ldw, int K, int R, const int32_t* heads, const int32_t* ids, int V, int Tv, int Sv,
+                        void* ws, float* out, void* stream);
+int trace_llm_score_rows(trace_ctx* ctx, const void* hidden, int R, const int32_t* heads, const int32_t* ids, float* out, void* stream);
+int trace_llm_score_append(trace_ctx* ctx, int slot0, int n, int past, const void* const* embeds, int L, const int32_t* heads, const int32_t* ids,
+                           float* out, void* stream);
+
 /* generate() = greedy loop with head switching (trace_mistral.py:268-347 + HF greedy search).
  * begin: sequences = the given KV slots (each prefilled); heads[b] in {0 text,1 time,2 score} (callers pass [1]);
  *        computes token 0 from the prefill hidden state.  forced: HOST [B, max_new] teacher-forcing ids or NULL.
@@ -199,7 +235,7 @@ int trace_decode_set_sampling(trace_ctx* ctx, float temperature, int top_k, floa
  * For row b at step s, with head = the row's active head at that step, [lo, hi) its id range, and x the RAW masked fp32 logits of that range as
  * the head stage writes them (no temperature, no top-k, no top-p: the model's distribution, not the warped one):
  *     logprob[b][s] = (x[id] - M) - log(S),   M = max x,   S = sum_i exp(x_i - M)
- * id = the token recorded in out_ids[b][s] (under forced ids: the model's own choice; an id outside [lo, hi) gives -inf).  S is formed exactly
+ * id = the token recorded in out_ids[b][s] (under forced ids: the model's own choice — trace_llm_score_append scores the fed ids; an id outside [lo, hi) gives -inf).  S is formed exactly
  * as the sampler forms its sums: weights from the sampler's exp, thread t of 256 sums the id-order run [t C, (t + 1) C), C = ceil((hi - lo) / 256),
  * then a Hillis-Steele scan over the 256 run totals; no FMA contraction anywhere.  log (arguments >= 1: the maximum contributes exp(0)) is
  * the odd atanh series of csrc/sample.h sample_log, every operation rounded on its own.  trace_amd/sampling.py token_logprob_ref restates it

@@ -59,6 +59,11 @@ SIGNATURES = {
     "trace_kv_copy": (I, [P, I, P, I, I, P]),
     "trace_embed_rows": (I, [P, P, I, P, I, P, I, P, P]),
     "trace_llm_head_logits": (I, [P, P, I, I, P, P]),
+    "trace_op_score_tile": (I, []),
+    "trace_op_score_ws_bytes": (C.c_int64, [I, I, I, I]),
+    "trace_op_score_rows": (I, [P, I, P, I, I, I, P, P, I, I, I, P, P, P]),
+    "trace_llm_score_rows": (I, [P, P, I, P, P, P, P]),
+    "trace_llm_score_append": (I, [P, I, I, I, C.POINTER(P), I, P, P, P, P]),
     "trace_decode_begin": (I, [P, P, I, P, I, I, P, P, P]),
     "trace_decode_steps": (I, [P, I, I, P, P]),
     "trace_decode_read": (I, [P, P, P, P, P]),
@@ -115,7 +120,7 @@ SIGNATURES = {
     "trace_op_kv8_unpack": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
 }
 
-NOT_A_STATUS = {"trace_abi_version", "trace_element_type", "trace_ctx_kv_cache_type", "trace_op_skinny_ks", "trace_op_sk_rows", "trace_op_gemm_partial_ks"}   # ints that are values
+NOT_A_STATUS = {"trace_abi_version", "trace_element_type", "trace_ctx_kv_cache_type", "trace_op_skinny_ks", "trace_op_sk_rows", "trace_op_gemm_partial_ks", "trace_op_score_tile"}   # ints that are values
 _libs = {}
 
 

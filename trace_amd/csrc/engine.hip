@@ -134,6 +134,9 @@ struct trace_ctx {
     // (rows of the current batch at stride max_new), written by the launch after the selection from the same d_slog rows
     int lp_set = 0, lp_on = 0;
     float* d_logprobs = nullptr;
+    // scoring given tokens (trace_llm_score_rows / _append, score.hip): allocated on first use for pf_rows() rows — the tile partials, the rows' heads
+    // and target ids, their log-probabilities
+    float* score_ws = nullptr; int32_t* d_score_heads = nullptr; int32_t* d_score_ids = nullptr; float* d_score_out = nullptr;
     // logits processors (trace_decode_set_logits_params): armed at trace_decode_begin like the sampling; the device copy d_lgparams is what
     // logits_process_kernel reads, d_plog the [SK_ROWS][NV] processed rows the selection then reads (d_slog stays raw: the log-probabilities' rows).
     // graphs_logits[sampling + 2 * logprobs]: steps with the extra launch are cached apart, so a disarmed batch replays the graphs it always did
@@ -1242,7 +1245,8 @@ extern "C" int trace_llm_prefill_multi(trace_ctx* c, int slot0, const void* cons
 
 // Continue n slots that hold at least `past` rows each (a prompt prefix prefilled or copied there earlier) with L new rows per slot: what
 // trace_llm_prefill_multi is for whole prompts.  Everything is checked before the first launch.
-extern "C" int trace_llm_prefill_append(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, void* hidden_out, void* stream) {
+// the argument rules of an append, for trace_llm_prefill_append and trace_llm_score_append alike (the latter has no hidden_out and passes NULL)
+static int append_check(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, const void* hidden_out) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
     if (n < 1 || n > PF_MAX_N || slot0 < 0 || slot0 + n > c->max_B) return fail(TRACE_ERR_ARG, "bad slot / n");
     if (L < 1 || past < 0) return fail(TRACE_ERR_ARG, "bad L / past");
@@ -1254,9 +1258,18 @@ extern "C" int trace_llm_prefill_append(trace_ctx* c, int slot0, int n, int past
         if (embeds && !embeds[i]) return fail(TRACE_ERR_ARG, "null embeds");
         if (past > c->slot_len[slot0 + i]) return fail(TRACE_ERR_STATE, "past exceeds the rows the slot holds");
     }
-    hipStream_t s = (hipStream_t)stream;
+    return TRACE_OK;
+}
+// the n prompts' new rows end to end into pX (embeds == NULL: the internal buffer already holds them)
+static int append_stage_embeds(trace_ctx* c, int n, const void* const* embeds, int L, hipStream_t s) {
     if (embeds)
         for (int i = 0; i < n; ++i) HIPCHK(hipMemcpyAsync(c->pX + (size_t)i * L * c->H, embeds[i], (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
+    return TRACE_OK;
+}
+extern "C" int trace_llm_prefill_append(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, void* hidden_out, void* stream) {
+    TRY(append_check(c, slot0, n, past, embeds, L, hidden_out));
+    hipStream_t s = (hipStream_t)stream;
+    TRY(append_stage_embeds(c, n, embeds, L, s));
     return prefill_impl(c, slot0, n, L, hidden_out, s, past);
 }
 
@@ -1720,6 +1733,60 @@ extern "C" int trace_op_token_logprob(const float* logits, int ld, int B, const 
     if (!logits || !heads || !ids || !out) return fail(TRACE_ERR_ARG, "null pointer");
     const int rc = launch_token_logprob(logits, ld, B, heads, V, Tv, Sv, ids, out, (hipStream_t)stream);
     if (rc != TRACE_OK) return fail(rc, "token_logprob launch failed (B, ld or head widths out of range)");
+    return TRACE_OK;
+}
+
+// ---- scoring given tokens (score.hip) ----
+extern "C" int trace_op_score_tile(void) { return SCORE_TILE; }
+extern "C" int64_t trace_op_score_ws_bytes(int R, int V, int Tv, int Sv) {
+    if (R < 1 || R > SCORE_MAX_ROWS || V < 1 || Tv < 1 || Sv < 1) return fail(TRACE_ERR_ARG, "bad R / head widths");
+    return (int64_t)score_ws_floats(R, V) * 4;
+}
+extern "C" int trace_op_score_rows(const void* hidden, int ld, const void* W, int ldw, int K, int R, const int32_t* heads, const int32_t* ids, int V, int Tv,
+                                   int Sv, void* ws, float* out, void* stream) {
+    if (!hidden || !W || !heads || !ids || !ws || !out) return fail(TRACE_ERR_ARG, "null pointer");
+    const int rc = launch_score_rows((const bf16_t*)hidden, ld, (const bf16_t*)W, ldw, K, R, heads, ids, V, Tv, Sv, (float*)ws, out, (hipStream_t)stream);
+    if (rc != TRACE_OK) return fail(rc, "score_rows launch failed (R, K % 64, ld / ldw % 8 or head widths out of range)");
+    return TRACE_OK;
+}
+static int score_buffers(trace_ctx* c) {
+    const size_t PR = pf_rows(c->max_ctx);
+    if (!c->score_ws) TRY(dalloc(c, &c->score_ws, score_ws_floats((int)PR, c->V)));
+    if (!c->d_score_heads) TRY(dalloc(c, &c->d_score_heads, PR));
+    if (!c->d_score_ids) TRY(dalloc(c, &c->d_score_ids, PR));
+    if (!c->d_score_out) TRY(dalloc(c, &c->d_score_out, PR));
+    return TRACE_OK;
+}
+extern "C" int trace_llm_score_rows(trace_ctx* c, const void* hidden, int R, const int32_t* heads, const int32_t* ids, float* out, void* stream) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (!hidden || !heads || !ids || !out) return fail(TRACE_ERR_ARG, "null pointer");
+    if (R < 1 || (size_t)R > pf_rows(c->max_ctx)) return fail(TRACE_ERR_ARG, "R outside 1 .. the prefill workspace's rows");
+    TRY(score_buffers(c));
+    const int rc = launch_score_rows((const bf16_t*)hidden, c->H, c->wheads, c->H, c->H, R, heads, ids, c->V, c->Tv, c->Sv, c->score_ws, out, (hipStream_t)stream);
+    if (rc != TRACE_OK) return fail(rc, "score_rows launch failed");
+    return TRACE_OK;
+}
+// trace_llm_prefill_append's checks (append_check: one function for both) and body with every row's final-norm hidden state kept (in pH, free once the last layer is done), then the score of
+// the n x L rows.  Everything is checked before the first launch.
+extern "C" int trace_llm_score_append(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, const int32_t* heads, const int32_t* ids,
+                                      float* out, void* stream) {
+    TRY(append_check(c, slot0, n, past, embeds, L, nullptr));
+    if (!heads || !ids || !out) return fail(TRACE_ERR_ARG, "null heads / ids / out");
+    const int M = n * L;
+    for (int i = 0; i < M; ++i) {
+        if (heads[i] < 0 || heads[i] > 2) return fail(TRACE_ERR_ARG, "head must be 0, 1 or 2");
+        if (ids[i] < -1 || ids[i] >= c->NV) return fail(TRACE_ERR_ARG, "id must be -1 (ignore) or a vocabulary id");
+    }
+    TRY(score_buffers(c));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(c->d_score_heads, heads, (size_t)M * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_score_ids, ids, (size_t)M * 4, hipMemcpyHostToDevice, s));
+    TRY(append_stage_embeds(c, n, embeds, L, s));
+    TRY(prefill_impl(c, slot0, n, L, c->pH, s, past));
+    const int rc = launch_score_rows(c->pH, c->H, c->wheads, c->H, c->H, M, c->d_score_heads, c->d_score_ids, c->V, c->Tv, c->Sv, c->score_ws, c->d_score_out, s);
+    if (rc != TRACE_OK) return fail(rc, "score_rows launch failed");
+    HIPCHK(hipMemcpyAsync(out, c->d_score_out, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return TRACE_OK;
 }
 

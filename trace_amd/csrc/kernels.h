@@ -235,6 +235,17 @@ int launch_sample_rows(const float* logits, int ld, int B, const int32_t* heads,
 // kernel wrote for this step [B][NV]; writes out_logprobs[b][step] ([B][max_new]) where select_next recorded a token in this step.
 int launch_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out, hipStream_t s);
 int launch_step_logprob(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, float* out_logprobs, hipStream_t s);
+// ---- scoring given tokens (score.hip) ----
+// log-probability of ids[r] under head heads[r] for R final-norm hidden rows X [R][ld] against the head rows W [V + 1 + Tv + Sv][ldw] (global vocabulary
+// order), without materialising logits: text rows through a 128 x 128-tile MFMA GEMM whose epilogue leaves (max, sum of exp, target logit) per row and
+// column tile of SCORE_TILE columns, time / score rows (Tv, Sv <= 128) by dot products in the merge kernel.  id -1 -> 0.0, an id outside the head -> -inf.
+// ws: score_ws_floats(R, V) floats.  heads / ids int32 [R] device, out fp32 [R] device.  K % 64 == 0, ld / ldw % 8 == 0, R <= SCORE_MAX_ROWS.
+constexpr int SCORE_TILE = 128;
+constexpr int SCORE_MAX_ROWS = 65536;
+int score_tiles(int V);
+size_t score_ws_floats(int R, int V);
+int launch_score_rows(const bf16_t* X, int ld, const bf16_t* W, int ldw, int K, int R, const int32_t* heads, const int32_t* ids, int V, int Tv, int Sv,
+                      float* ws, float* out, hipStream_t s);
 // logits processors (logits.h: repetition penalty, no-repeat n-grams, min_new_tokens) from a row of masked logits into a row of their own.
 // Loose rows: hist int32 [B][ld_hist] / hist_len / heads / steps int32 [B] (device), out [B][ldo] written whole, -inf outside the head
 // (trace_op_logits_process).  Decode step: between launch_head_logits and the selection of the same step, history = st.out_ids / st.out_len,

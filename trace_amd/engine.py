@@ -14,6 +14,7 @@ from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
 from .prefix import APPEND_GROUP_MAX, group_by_length, split_questions
 from .sampling import LogitsParams, SamplingParams, sample_rows_host
+from . import scoring
 
 __all__ = ["TraceEngine", "SamplingParams", "ops"]
 
@@ -97,7 +98,7 @@ class TraceEngine:
         self._max_new = 0
         self._stage_ev = None          # stage_timing(): [(kind, event, event)] while on
         self._stage_videos = 0
-        self.stats = {"vit_frames": 0, "prefill_rows": 0}      # frames the tower has run / rows prefilled so far (what prefix reuse saves is read off these)
+        self.stats = {"vit_frames": 0, "prefill_rows": 0, "score_rows": 0}      # frames the tower has run / rows prefilled / rows scored so far (what prefix reuse saves is read off these)
         self._prefix = None            # (key, rows): KV slot 0 holds `rows` prefilled prompt rows described by `key` (set_prefix_entry); see _drop_prefix
         self._dbg = None               # debugging hook: callable(tag, index, tensor-or-None) called between the stages (tools/pipeline_stress.py)
 
@@ -356,6 +357,85 @@ class TraceEngine:
         out = torch.empty((hidden.shape[0], self.cfg.total_vocab), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.trace_llm_head_logits(self.h, _ptr(hidden), hidden.shape[0], int(head), _ptr(out), _stream()))
         return out
+
+    # ---- scoring given tokens (trace_llm_score_rows / trace_llm_score_append; include/trace_hip.h states the semantics) ----
+    def score_rows(self, hidden: torch.Tensor, heads: Sequence[int], ids: Sequence[int]) -> np.ndarray:
+        """float32 [R]: the log-probability of ids[r] under head heads[r] from final-norm hidden row r (the rows prefill(want_hidden=True) returns);
+        id -1 gives 0.0, an id outside the head -inf.  No [R, vocabulary] logits are ever stored."""
+        assert hidden.dtype == self.dtype and hidden.is_cuda and hidden.is_contiguous() and hidden.dim() == 2 and hidden.shape[1] == self.cfg.hidden_size
+        R = hidden.shape[0]
+        if len(heads) != R or len(ids) != R:
+            raise ValueError("one head and one id per hidden row")
+        hd = torch.tensor([int(h) for h in heads], dtype=torch.int32, device=self.device)
+        ii = torch.tensor([int(t) for t in ids], dtype=torch.int32, device=self.device)
+        out = torch.empty(R, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.trace_llm_score_rows(self.h, _ptr(hidden), R, _ptr(hd), _ptr(ii), _ptr(out), _stream()))
+        self.stats["score_rows"] += R
+        return out.cpu().numpy()
+
+    def score_continuations(self, slot0: int, past_rows: int, last_prompt_embed_row: torch.Tensor, continuations: Sequence[Sequence[int]], head=1,
+                            pad_id: int = 0):
+        """Log-probabilities of given continuations of ONE prompt of past_rows rows.  last_prompt_embed_row: the embedding of the prompt's last row
+        [hidden] — or of its last k rows [k, hidden] — while slot slot0 holds the past_rows - k rows before them (it may hold more: they are rewritten).
+        Continuation b's appended rows are [those k rows, embed(c[0]), ..., embed(c[n_b - 2])] at positions past_rows - k ..., so the row at position
+        past_rows - 1 + i predicts c[i] under head_chain(c, head)[i] (head: one int, or one per continuation).  Continuations of unequal length are
+        padded to the group's longest with pad_id (any text id) and target -1: the padding follows the real rows, so causality keeps it from
+        touching them.  Groups of up to 8 consecutive slots slot0 ..., each group within the prefill workspace, the prefix fanned out with
+        kv_copy; one trace_llm_score_append per group.  Returns ([float32 array per continuation], [head list per continuation], float64 sums).
+        Afterwards the slots hold rows that belong to the continuations: only rows below past_rows - k of slot0 are still the prompt's."""
+        cfg = self.cfg
+        rows = last_prompt_embed_row.to(self.device, self.dtype)
+        rows = rows.unsqueeze(0) if rows.dim() == 1 else rows
+        if rows.dim() != 2 or rows.shape[1] != cfg.hidden_size or rows.shape[0] < 1:
+            raise ValueError("last_prompt_embed_row: [hidden] or [k, hidden]")
+        k = rows.shape[0]
+        past = int(past_rows) - k
+        if past < 0:
+            raise ValueError("past_rows counts the whole prompt: it cannot be smaller than the rows handed in")
+        nc = len(continuations)
+        if nc < 1:
+            raise ValueError("no continuation to score")
+        heads0 = [int(head)] * nc if isinstance(head, (int, np.integer)) else [int(h) for h in head]
+        if len(heads0) != nc:
+            raise ValueError("one starting head, or one per continuation")
+        conts = [scoring.check_continuation(cfg, c, h) for c, h in zip(continuations, heads0)]
+        if not 0 <= int(pad_id) < cfg.vocab_size:
+            raise ValueError("pad_id must be a text id")
+        longest = max(len(c) for c in conts)
+        if past + k - 1 + longest > self.max_ctx:
+            raise ValueError(f"prompt ({past_rows} rows) + continuation ({longest} tokens) exceeds max_ctx {self.max_ctx}")
+        gmax = min(APPEND_GROUP_MAX, self.max_batch - int(slot0))
+        if gmax < 1:
+            raise ValueError("slot0 outside the engine's KV slots")
+        chains = [scoring.head_chain(cfg, c, h) for c, h in zip(conts, heads0)]
+        out = [None] * nc
+        for run in scoring.groups_of([k - 1 + len(c) for c in conts], self.prefill_rows, gmax):
+            L = k - 1 + max(len(conts[b]) for b in run)
+            embeds, hd, tg = [], [], []
+            for b in run:
+                fed = scoring.fed_ids(conts[b], L - (k - 1), pad_id)
+                e = rows
+                if fed:
+                    e = torch.cat([rows, self.embed_rows(*scoring.embed_placeholders(cfg, fed), want_output=True)], 0)
+                embeds.append(e.contiguous())
+                t, h = scoring.targets(conts[b], chains[b], L - (k - 1))
+                tg += [scoring.IGNORE] * (k - 1) + t
+                hd += [0] * (k - 1) + h
+            n = len(run)
+            if n > 1 and past > 0:
+                self.kv_copy(slot0, list(range(slot0 + 1, slot0 + n)), past)
+            if self._prefix is not None and slot0 == 0 and past < self._prefix[1]:
+                self._drop_prefix()
+            res = (C.c_float * (n * L))()
+            ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in embeds])
+            _lib.check(self.lib.trace_llm_score_append(self.h, int(slot0), n, past, ptrs, L, _i32(hd), _i32(tg), res, _stream()))
+            self.stats["prefill_rows"] += n * L
+            self.stats["score_rows"] += n * L
+            arr = np.frombuffer(res, dtype=np.float32).reshape(n, L)
+            for j, b in enumerate(run):
+                out[b] = arr[j, k - 1:k - 1 + len(conts[b])].copy()
+        sums = np.array([np.sum(o, dtype=np.float64) for o in out], np.float64)
+        return out, chains, sums
 
     def prefill_pair(self, slot0: int, embeds0: torch.Tensor, embeds1: torch.Tensor):
         """two spliced prompts of equal length -> KV slots slot0, slot0 + 1 in one pass (trace_llm_prefill_pair)"""
@@ -883,6 +963,29 @@ class ops:
         ii = ids if isinstance(ids, torch.Tensor) else torch.tensor([int(x) for x in ids], dtype=torch.int32, device=dev)
         out = torch.empty(B, dtype=torch.float32, device=dev)
         _lib.check(lib.trace_op_token_logprob(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, _ptr(ii), _ptr(out), _stream()))
+        return out
+
+    @staticmethod
+    def score_tile(element=None) -> int:
+        return _lib.load(element or ops.element).trace_op_score_tile()
+
+    @staticmethod
+    def score_rows(hidden, W, heads, ids, V: int, Tv: int, Sv: int, element=None):
+        """trace_op_score_rows: hidden [R, K], W [V+1+Tv+Sv, K] (the element type, device) -> fp32 [R] (device): the log-probability of ids[r] under
+        head heads[r], sampling.score_logprob_ref bit for bit given the same fp32 logits; id -1 -> 0.0, outside the head -> -inf."""
+        lib = _lib.load(element or ops.element)
+        x, w = hidden.contiguous(), W.contiguous()
+        R, K = x.shape
+        dev = x.device
+        hd = heads if isinstance(heads, torch.Tensor) else torch.tensor([int(h) for h in heads], dtype=torch.int32, device=dev)
+        ii = ids if isinstance(ids, torch.Tensor) else torch.tensor([int(t) for t in ids], dtype=torch.int32, device=dev)
+        nbytes = int(lib.trace_op_score_ws_bytes(R, V, Tv, Sv))          # an int64: a negative status is not raised by the binding's errcheck
+        if nbytes < 0:
+            msg = lib.trace_last_error()
+            raise _lib.TraceHipError(f"error {nbytes} in trace_op_score_ws_bytes: {msg.decode() if msg else '?'}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(R, dtype=torch.float32, device=dev)
+        _lib.check(lib.trace_op_score_rows(_ptr(x), K, _ptr(w), K, K, R, _ptr(hd), _ptr(ii), V, Tv, Sv, _ptr(ws), _ptr(out), _stream()))
         return out
 
     @staticmethod

@@ -11,6 +11,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from .. import scoring
 from ..config import TraceConfig
 from ..constants import MMODAL_TOKEN_INDEX, NUM_FRAMES
 from ..prefix import split_questions
@@ -91,6 +92,20 @@ class TraceMistralForCausalLM:
     def prefix_cache_enabled(self) -> bool:
         return self._prefix_cache
 
+    @staticmethod
+    def _ts_key(ts):
+        """one tuple of stamps per frame"""
+        return tuple(tuple(float(v) for v in (t if hasattr(t, "__iter__") else (t,))) for t in ts)
+
+    def _prefix_lookup(self, raw, timestamps, modal, prefix):
+        """(key, hit, rows): the prefix-cache key of one video's rows through `<video>` (the caller's tensor object and its version, the stamps, the
+        modal, the ids), whether KV slot 0 still holds the rows of exactly that key, and how many rows it holds then (None on a miss).  The one
+        place the key is made and compared: generate() and score() both ask here."""
+        key = (raw, raw._version, self._ts_key(timestamps), modal, tuple(prefix))
+        ent = self.engine.prefix_entry()
+        hit = ent is not None and ent[0][0] is key[0] and ent[0][1:] == key[1:]
+        return key, hit, (ent[1] if hit else None)
+
     def _generate_prefix_cached(self, raw, vids, modals, timestamps, id_lists, heads, max_new_tokens, eos, sampling, logprobs=False, **lg):
         """generate()'s main path with the cache on; None = this call is not of the cacheable shape (today's path runs)."""
         eng, B = self.engine, len(vids)
@@ -100,22 +115,18 @@ class TraceMistralForCausalLM:
             return None
         if any(len(x) == 0 for x in suffixes):
             return None
-        ts_of = lambda ts: tuple(tuple(float(v) for v in (t if hasattr(t, "__iter__") else (t,))) for t in ts)      # one tuple of stamps per frame
+        ts_of = self._ts_key
         ts_key = ts_of(timestamps[0])
         if B > 1:
             if any(r is not raw[0] for r in raw[1:]) or any(m != modals[0] for m in modals[1:]) or any(ts_of(t) != ts_key for t in timestamps[1:]):
                 return None
             if B > eng.decode_batch_max:
                 return None
-        key = (raw[0], raw[0]._version, ts_key, modals[0], tuple(prefix))
+        key, hit, P = self._prefix_lookup(raw[0], timestamps[0], modals[0], prefix)
         if B > 1:
             return eng.generate_questions(vids[0], timestamps[0], id_lists, heads, max_new_tokens, eos=eos, sampling=sampling, prefix_key=key,
                                           logprobs=logprobs, **lg)
-        ent = eng.prefix_entry()
-        hit = ent is not None and ent[0][0] is key[0] and ent[0][1:] == key[1:]
-        if hit:
-            P = ent[1]
-        else:
+        if not hit:
             eng.encode_video(vids[0], timestamps[0])
             P = eng.splice(prefix)
             eng.prefill(0, P)
@@ -285,6 +296,75 @@ class TraceMistralForCausalLM:
             lp[j, : len(out[r])] = torch.from_numpy(np.asarray(lps[r], np.float32))
         return SimpleNamespace(sequences=seq.to(self.device), logprobs=lp.to(self.device), scores=torch.from_numpy(scores[order].copy()),
                                order=[int(r) for r in order], heads=[int(new_heads[r]) for r in order])
+
+    @torch.no_grad()
+    def score(self, inputs=None, images_or_videos=None, video_timestamps=None, continuations=None, heads=None, modal_list=None, **kwargs):
+        """How likely is each GIVEN continuation of ONE prompt?  (Multiple-choice scoring, ranking candidate captions or moments, the teacher-forced
+        log-likelihood of a [time | score | caption] stream — what generate(output_logprobs=True) cannot say: it reports the tokens the model chose.)
+        continuations: lists (or 1-D tensors) of global vocabulary ids over [text | <sync> | time | score]; heads: the head active for each one's
+        first id — one int in a list for all of them (default [1], as generate's callers pass) or one per continuation.  Token i is scored under the
+        head the fed ids c[0 .. i) lead to, from the hidden row that precedes it (include/trace_hip.h, trace_llm_score_append): all continuations
+        run as appended rows behind the prompt's KV rows, up to 8 per pass, and their log-probabilities come from the fused head kernel — no
+        [rows, vocabulary] logits exist at any point.  With enable_prefix_cache() on and a hit (same frame tensor, timestamps and ids through
+        `<video>` as the previous generate() / score()), no tower pass and no prefill of the rows through `<video>` runs, and the entry stays
+        valid afterwards: only rows behind it are rewritten.
+        Returns a scoring.ScoreResult: `.logprobs` (a float32 array per continuation), `.heads` (the head of every token), `.scores` (float64 sums) and `.order`
+        (continuation indices by descending score, ties to the lower index)."""
+        if kwargs:
+            raise TypeError(f"score() got unexpected arguments {sorted(kwargs)}")
+        if images_or_videos is None or video_timestamps is None:
+            raise ValueError("score takes one video with its timestamps")
+        if continuations is None or len(continuations) < 1:
+            raise ValueError("score needs at least one continuation")
+        ids = inputs if isinstance(inputs, torch.Tensor) else torch.tensor(inputs)
+        if ids.dim() == 1:
+            ids = ids.unsqueeze(0)
+        if ids.shape[0] != 1 or len(images_or_videos) != 1 or len(video_timestamps) != 1:
+            raise ValueError("score takes one prompt (B = 1) with any number of continuations")
+        conts = [[int(t) for t in (c.tolist() if isinstance(c, torch.Tensor) else c)] for c in continuations]
+        hd = [1] if heads is None else [int(h) for h in heads]
+        if len(hd) == 1:
+            hd = hd * len(conts)
+        if len(hd) != len(conts):
+            raise ValueError("heads: one entry, or one per continuation")
+        cfg, eng = self.config, self.engine
+        conts = [scoring.check_continuation(cfg, c, h) for c, h in zip(conts, hd)]
+        if cfg.mm_projector_type == "stc_connector":
+            raise NotImplementedError("score runs on the TRACE path (time tokens per frame), not the legacy STC connector")
+        eng.host_mode(False)
+        self._live_kv = None
+        raw = images_or_videos[0]
+        x = raw
+        modal = (modal_list or ["video"])[0]
+        if modal == "image":
+            nf = cfg.num_frames if hasattr(cfg, "num_frames") else NUM_FRAMES
+            x = x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
+        prompt = ids[0].tolist()
+        tail = None
+        if self._prefix_cache and isinstance(raw, torch.Tensor):
+            try:
+                prefix, suffixes = split_questions([prompt])
+            except ValueError:
+                prefix, suffixes = None, [[]]
+            if prefix is not None and len(suffixes[0]) > 0:
+                ts = video_timestamps[0]
+                key, hit, P0 = self._prefix_lookup(raw, ts, modal, prefix)
+                if not hit:
+                    eng.encode_video(x, ts)
+                    P0 = eng.splice(prefix)
+                    eng.prefill(0, P0)
+                    eng.set_prefix_entry(key, P0)
+                tail = eng.embed_rows(suffixes[0], want_output=True)        # the rows after <video> ride in front of every continuation: one pass
+                P = P0 + tail.shape[0]
+        if tail is None:
+            eng.encode_video(x, video_timestamps[0])
+            P, emb = eng.splice(prompt, want_output=True)
+            emb = emb.clone()
+            if P > 1:
+                eng.prefill(0, P - 1, emb[: P - 1])
+            tail = emb[P - 1:]
+        lps, chains, sums = eng.score_continuations(0, P, tail, conts, hd)
+        return scoring.ScoreResult(logprobs=lps, heads=chains, scores=sums, order=rank_samples(sums))
 
     # arguments of HF's generate() this build does not implement, with the value that means "off"
     _UNSUPPORTED = {"num_beams": 1, "num_return_sequences": 1, "typical_p": 1.0, "min_p": None, "repetition_penalty": 1.0}

@@ -6,7 +6,8 @@ arithmetic), so it returns the device's id bit for bit; it also serves as the ho
 take (top_k > 1024, or top_k = 0 with top_p < 1), where it applies the same rules.  `philox_uniform` is the RNG contract in numpy.
 `token_logprob_ref` restates the per-token log-probability (sample.h token_logprob_row) the same way: the device's float bits.
 `LogitsParams` / `process_row_ref`: the logits processors of the decode step (repetition penalty, no-repeat n-grams, min_new_tokens:
-trace_amd/csrc/logits.h) and their float32 restatement, again bit for bit."""
+trace_amd/csrc/logits.h) and their float32 restatement, again bit for bit.
+`score_logprob_ref`: the log-probability of a GIVEN id as the scoring kernels (trace_amd/csrc/score.hip) form it from column-tile partial sums."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -224,6 +225,45 @@ def token_logprob_ref(row, i):
         if not 0 <= int(i) < n:
             return _F(-np.inf)
         return _F((x[int(i)] - M) - _slog(np.array([S], np.float32))[0])
+
+
+# ---- scoring given tokens (csrc/score.hip) ----
+SCORE_TILE = 128              # kernels.h SCORE_TILE = trace_op_score_tile()
+
+
+def score_tile_partials(row, lo, hi):
+    """(m, s) float32 per column tile of the head range [lo, hi) of one whole row of fp32 logits, as score_head_kernel's epilogue leaves them:
+    tiles [j CT, (j + 1) CT) on ABSOLUTE columns clipped to the range, m_j = max x, s_j = h0 + h1 with h0 / h1 = the sums of exp(x - m_j) over the
+    tile's lower / upper CT / 2 columns, each sequential in ascending column order from 0."""
+    x = np.asarray(row, np.float32)
+    ct = SCORE_TILE
+    j0, j1 = lo // ct, (hi - 1) // ct
+    buf = np.full((j1 - j0 + 1) * ct, -np.inf, np.float32)
+    buf[lo - j0 * ct: hi - j0 * ct] = x[lo:hi]
+    t = buf.reshape(-1, 2, ct // 2)
+    m = t.max(axis=(1, 2))
+    with np.errstate(invalid="ignore"):
+        w = _sexp(t - m[:, None, None])                                    # columns outside the range weigh exactly 0: adding them changes no bit
+    h = np.cumsum(w, axis=2, dtype=np.float32)[:, :, -1]
+    return m, (h[:, 0] + h[:, 1]).astype(np.float32)
+
+
+def score_logprob_ref(row, lo, hi, t):
+    """The device's log-probability (score.hip) of global id t under the head range [lo, hi) of one whole row of fp32 logits (float32 [NV]), bit
+    for bit: M = max_j m_j, S = sum_j s_j * exp(m_j - M) sequentially in ascending j from 0 over score_tile_partials, (x[t] - M) - log S.
+    t == -1 (ignore) gives 0.0, any other t outside [lo, hi) gives -inf."""
+    t = int(t)
+    if t == -1:
+        return _F(0.0)
+    if not lo <= t < hi:
+        return _F(-np.inf)
+    x = np.asarray(row, np.float32)
+    m, s = score_tile_partials(x, lo, hi)
+    M = m.max()
+    with np.errstate(invalid="ignore"):
+        terms = (s * _sexp(m - M)).astype(np.float32)
+        S = np.cumsum(terms, dtype=np.float32)[-1]
+        return _F((x[t] - M) - _slog(np.array([S], np.float32))[0])
 
 
 # ---- logits processors (csrc/logits.h) ----
