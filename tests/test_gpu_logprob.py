@@ -15,7 +15,7 @@ if not torch.cuda.is_available():
 from trace_amd import config as tcfg, synth  # noqa: E402
 from trace_amd._lib import TraceHipError  # noqa: E402
 from trace_amd.engine import SamplingParams, TraceEngine, ops  # noqa: E402
-from trace_amd.sampling import head_bounds, token_logprob_ref  # noqa: E402
+from trace_amd.sampling import LogitsParams, head_bounds, token_logprob_ref  # noqa: E402
 
 GEOMS = [(32000, 13, 13), (320, 13, 13), (20, 3, 2)]          # TRACE-7B, the tiny config, a toy
 LOGIT_TOL = 0.15                                              # the project's logit budget against the reference fixtures (test_gpu_parity.py)
@@ -154,6 +154,43 @@ def test_toggling_between_batches_equals_fresh_engines(tiny):
         for r in (seq[1], seq[3]):
             assert r[0] == want_on[0] and r[1] == want_on[1] and _same_bits(r[2], want_on[2])
         assert want_on[0] == want_off[0]
+
+
+def test_all_eight_tail_modes_cycled_equal_fresh_engines(tiny):
+    """sampling x log-probabilities x logits processors: one engine decodes 16 tokens at B = 3 in all eight modes, twice over, no two consecutive
+    batches in one mode - the first visit captures the mode's graph, the second replays it after seven others were captured in between - and
+    then B = 1 in the plain and the all-armed mode.  Every result against an engine that only ever ran that one mode: ids and heads equal,
+    log-probabilities equal as float bits, the same seed everywhere.  A wrong index into the graph table or a buffer a mode misses shows here."""
+    cfg, _, vids, ts, ids = tiny
+    sp, lgp = SAMPLED[0], LogitsParams(1.5, 2, 0)
+
+    def run(eng, mode, B):
+        return eng.generate(vids[:B], ts[:B], ids[:B], [1] * B, 16, use_graph=True, sampling=sp if mode & 1 else None, logprobs=bool(mode & 2),
+                            logits=lgp if mode & 4 else None)
+    want = {}
+    for mode in range(8):
+        fresh = _engine(cfg)
+        try:
+            want[mode, 3] = run(fresh, mode, 3)
+            if mode in (0, 7):
+                want[mode, 1] = run(fresh, mode, 1)
+        finally:
+            fresh.close()
+    assert want[0, 3][0] != want[1, 3][0] and want[0, 3][0] != want[4, 3][0] and want[1, 3][0] != want[5, 3][0]    # the modes are not one thing
+    order = [0, 7, 1, 6, 2, 5, 3, 4]
+    eng = _engine(cfg)
+    try:
+        for B, modes in ((3, order + order), (1, [0, 7, 0, 7])):
+            assert all(a != b for a, b in zip(modes, modes[1:]))
+            for visit, mode in enumerate(modes):
+                got, w = run(eng, mode, B), want[mode, B]
+                assert len(got) == len(w) == (3 if mode & 2 else 2), (B, visit, mode)
+                assert got[0] == w[0] and got[1] == w[1], (B, visit, mode)
+                assert all(len(r) == 16 for r in got[0])
+                if mode & 2:
+                    assert _same_bits(got[2], w[2]), (B, visit, mode)
+    finally:
+        eng.close()
 
 
 def test_teacher_forced_logprobs_against_the_reference_fixture(golden_dir):

@@ -23,6 +23,7 @@ if not torch.cuda.is_available():
 import token_select_probes as P  # noqa: E402
 from trace_amd import synth  # noqa: E402
 from trace_amd.engine import TraceEngine, ops  # noqa: E402
+from trace_amd.sampling import token_logprob_ref  # noqa: E402
 
 KINDS = {"bf16": dict(dtype=torch.bfloat16), "f16": dict(dtype=torch.float16), "fp8": dict(dtype=torch.bfloat16, llm_fp8="w8a8")}
 SLOTS = {("small", "bf16"): 256, ("big", "bf16"): 100, ("small", "f16"): 17, ("small", "fp8"): 40}
@@ -212,6 +213,76 @@ def test_host_select_mode(rigs):
     finally:
         eng.host_mode(False)
     assert {h for b in range(3) for h in [rows[b][1]]} == {0, 1, 2}
+
+
+def _stepwise_rows(rig):
+    """B = 3 for decode_stepwise, one row per head, every row's first pick a tie case (so the host's pick has to be the lowest id of the range,
+    inside the head, with larger decoys outside it).  Row 0 runs free under the time head; row 1 runs free under the text head except that step 2
+    feeds the EOS emitter (step 3 then picks EOS); row 2, under the score head, is fed three more cases at steps 1, 3 and 5 and picks from each of
+    them at the free step that follows (a forced step records the fed id, so only a free step shows the pick)."""
+    plan, mn = rig.plan, rig.max_new
+    case = {c.name: c for c in plan.cases}
+    c0, c1, c2 = case["tie_same_tile@1"], case["tie3_tile_wave@0"], case["tie_same_tile@2"]
+    assert all(len(c.ties) > 1 and c.decoys for c in (c0, c1, c2))
+    f2 = [-1] * mn
+    f2[1], f2[3], f2[5] = case["decoys@2"].token, case["all_negative@2"].token, case["tie3_tile_wave@2"].token
+    return [(c0.token, 1, [-1] * mn), (c1.token, 0, [-1, -1, plan.eos_emitter] + [-1] * (mn - 3)), (c2.token, 2, f2)]
+
+
+def _stepwise_want(rig, rows, eos):
+    """P.restate_batch under host-select mode's one own rule (test_host_select_mode): the id recorded at a forced step is the fed one, not the pick.
+    No row here is fed EOS, so lengths and heads are the restatement's as they are."""
+    ids, lens, heads = P.restate_batch(rig.T, rig.cfg, rows, eos, rig.max_new)
+    ids = [[f[s] if f[s] >= 0 else t for s, t in enumerate(x)] for x, (_, _, f) in zip(ids, rows)]
+    return ids, lens, heads
+
+
+@pytest.mark.parametrize("case", ["no_eos", "eos", "stopping", "logprobs"])
+def test_decode_stepwise_equals_restate(rigs, case):
+    """TraceEngine.decode_stepwise, greedy, on the identity-layer rig: the host's pick is the device's - the lowest id among equal maxima of the
+    head's range, whatever lies outside it (every row starts at a tie case, row 2 is fed into three more).  Exact equality."""
+    rig = rigs("small")
+    cfg, T, mn, eng = rig.cfg, rig.T, rig.max_new, rig.eng
+    rows = _stepwise_rows(rig)
+    rig.place(rows)
+    heads, forced = [h for _, h, _ in rows], [f for _, _, f in rows]
+    eos = rig.plan.eos if case == "eos" else -1
+    want = _stepwise_want(rig, rows, eos)
+    named = {c.name: c for c in rig.plan.cases}
+    assert [want[0][2][s] for s in (0, 2, 4, 6)] == [named[n + "@2"].expect for n in ("tie_same_tile", "decoys", "all_negative", "tie3_tile_wave")]
+    assert want[0][0][0] == named["tie_same_tile@1"].expect and want[0][1][0] == named["tie3_tile_wave@0"].expect
+    if case in ("no_eos", "eos"):
+        ids, hd = eng.decode_stepwise([0, 1, 2], heads, mn, eos, forced=forced)
+        assert (ids, [len(x) for x in ids], hd) == want
+        assert want[1] == ([mn, 4, mn] if case == "eos" else [mn] * 3) and (case != "eos" or ids[1][-1] == eos)
+    elif case == "stopping":
+        calls = []
+
+        def stop(cur):
+            calls.append([len(x) for x in cur])
+            return [False, len(cur[1]) >= 3, False]
+        ids, hd = eng.decode_stepwise([0, 1, 2], heads, mn, -1, forced=forced, stopping=stop)
+        assert ids == [want[0][0], want[0][1][:3], want[0][2]] and hd == want[2]       # (a stopped row is still fed: its head is the full run's)
+        assert calls == [[s + 1] * 3 for s in range(mn - 1)]                           # asked after every step but the last, with the recorded ids
+    else:
+        ids, hd, lps = eng.decode_stepwise([0, 1, 2], heads, mn, -1, forced=forced, logprobs=True)
+        assert (ids, [len(x) for x in ids], hd) == want
+        n_inf = 0
+        for b, (t, h, f) in enumerate(rows):
+            tr = []
+            P.restate(T, cfg, t, h, f, -1, mn, trace=tr)
+            assert lps[b].dtype == np.float32 and len(lps[b]) == mn
+            for s, (state, head, _) in enumerate(tr):
+                lo, hi = P.head_range(cfg, head)
+                raw = T[state, lo:hi].astype(np.float32) * np.float32(rig.scale)       # the raw row, bit for bit (test_logits_rows_are_scale_times_table)
+                w = token_logprob_ref(raw, ids[b][s] - lo)
+                assert np.float32(lps[b][s]).view(np.uint32) == np.float32(w).view(np.uint32), (b, s, lps[b][s], w)
+                n_inf += int(np.isneginf(w))
+        assert n_inf == 3 and all(np.isfinite(lps[b]).all() for b in (0, 1))           # row 2 is fed three text ids under the score head (-inf); picks never are
+        dev = eng.decode([0, 1, 2], heads, mn, -1, use_graph=False, forced=[[-1] * mn, forced[1], [-1] * mn], logprobs=True)
+        free = eng.decode_stepwise([0, 1, 2], heads, mn, -1, forced=[[-1] * mn, forced[1], [-1] * mn], logprobs=True)
+        for b in (0, 2):                                                                # free rows: the device loop's ids, heads and float bits
+            assert free[0][b] == dev[0][b] and free[1][b] == dev[1][b] and np.array_equal(free[2][b].view(np.uint32), dev[2][b].view(np.uint32))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4: trace_llm_head_logits

@@ -279,8 +279,8 @@ def test_both_libraries_export_the_entries_under_abi_4():
 
 
 def test_new_kernels_have_no_scratch(tmp_path):
-    """logits.hip holds logits_process_kernel and the third form of select_next_kernel, both without scratch, in the bf16 and the fp16 build
-    (decode.hip keeps its two instantiations of the selection: tests/test_sampling_cpu.py counts them)"""
+    """logits.hip holds logits_process_kernel, select.hip the three forms of select_next_kernel (the third one is the arg-max over a processed row),
+    all without scratch, in the bf16 and the fp16 build"""
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
@@ -288,17 +288,18 @@ def test_new_kernels_have_no_scratch(tmp_path):
         pytest.skip("hipcc not available")
     csrc = os.path.join(ROOT, "trace_amd", "csrc")
     for f16 in (False, True):
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", os.path.join(csrc, "logits.hip"), "-I", csrc,
-               "-o", str(tmp_path / "logits.o"), "-Rpass-analysis=kernel-resource-usage"] + (["-DTRACE_F16"] if f16 else [])
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
         found, cur = {}, None
-        for line in r.stderr.splitlines():
-            mm = re.search(r"Function Name: (\S+)", line)
-            if mm:
-                cur = mm.group(1)
-            mm = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-            if mm and cur:
-                found[cur] = int(mm.group(1))
-        assert sum("logits_process_kernel" in k for k in found) == 1 and sum("select_next_kernel" in k for k in found) == 1, sorted(found)
+        for name in ("logits", "select"):
+            cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", os.path.join(csrc, name + ".hip"), "-I", csrc,
+                   "-o", str(tmp_path / (name + ".o")), "-Rpass-analysis=kernel-resource-usage"] + (["-DTRACE_F16"] if f16 else [])
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            assert r.returncode == 0, r.stderr[-2000:]
+            for line in r.stderr.splitlines():
+                mm = re.search(r"Function Name: (\S+)", line)
+                if mm:
+                    cur = mm.group(1)
+                mm = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+                if mm and cur:
+                    found[cur] = int(mm.group(1))
+        assert sum("logits_process_kernel" in k for k in found) == 1 and sum("select_next_kernel" in k for k in found) == 3, sorted(found)
         assert all(v == 0 for v in found.values()), found

@@ -67,9 +67,10 @@ def test_restatement_is_a_log_probability():
 @pytest.mark.skipif(HIPCC is None, reason="hipcc not available")
 def test_logprob_kernel_has_no_scratch(tmp_path):
     """the new kernel: ScratchSize 0 in the bf16 and the fp16 build; and the function-name counts the sampling test relies on still hold (one
-    sample_rows_kernel in sample.hip, two select_next_kernel in decode.hip: the log-probability is a kernel of its own, no new instantiation)"""
-    for name, pat, want in (("sample", "token_logprob_kernel", 1), ("sample", "sample_rows_kernel", 1), ("decode", "select_next_kernel", 2),
-                            ("decode", "token_logprob_kernel", 0)):
+    sample_rows_kernel in sample.hip, the three forms of select_next_kernel in select.hip and nowhere else: the log-probability is a kernel of
+    its own, no new instantiation)"""
+    for name, pat, want in (("sample", "token_logprob_kernel", 1), ("sample", "sample_rows_kernel", 1), ("select", "select_next_kernel", 3),
+                            ("decode", "select_next_kernel", 0), ("decode", "token_logprob_kernel", 0), ("select", "token_logprob_kernel", 0)):
         for f16 in (False, True):
             cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", os.path.join(CSRC, name + ".hip"), "-I", CSRC,
                    "-o", str(tmp_path / (name + ".o")), "-Rpass-analysis=kernel-resource-usage"] + (["-DTRACE_F16"] if f16 else [])

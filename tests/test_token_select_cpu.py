@@ -40,6 +40,26 @@ def test_named_cases_hold(geom):
     assert all(P.column(cfg, t) is not None for t in fed)
 
 
+def test_host_argmax_is_the_selection_rule(geom):
+    """sampling.argmax_rows, the greedy pick of the host-driven loop (TraceEngine.decode_stepwise), on every named case under every head - ties in
+    one tile, one wave, across waves, flat heads, larger decoys outside the range, all-negative ranges: P.select, the lowest id among equal maxima
+    of the head's range.  Rows of -inf give the range's first id; numpy rows and torch rows give the same ids."""
+    from trace_amd.sampling import argmax_rows
+    name, cfg, T, plan = geom
+    V, Tv, Sv, NV, _ = P.dims(cfg)
+    toks = [c.token for c in plan.cases] + [t for t, _ in plan.chain]
+    rows = T[toks, :NV].astype(np.float32) * np.float32(3.921875)
+    for head in range(3):
+        lo, hi = P.head_range(cfg, head)
+        want = [P.select(T[t], lo, hi) for t in toks]
+        assert argmax_rows(rows, [head] * len(toks), V, Tv, Sv) == want, (name, head)
+        assert argmax_rows(torch.from_numpy(rows), [head] * len(toks), V, Tv, Sv) == want
+    heads = [c.head for c in plan.cases]
+    assert argmax_rows(rows[:len(heads)], heads, V, Tv, Sv) == [c.expect for c in plan.cases]         # a batch whose rows differ in head
+    assert sum(len(c.ties) > 1 for c in plan.cases) >= 9
+    assert argmax_rows(np.full((3, NV), -np.inf, np.float32), [0, 1, 2], V, Tv, Sv) == [P.head_range(cfg, h)[0] for h in range(3)]
+
+
 def test_ordinary_rows_have_unique_maxima_that_differ_between_neighbours(geom):
     _, cfg, T, plan = geom
     V, Tv, Sv, NV, _ = P.dims(cfg)

@@ -85,6 +85,13 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Heads.  The head rows (and every logits row) follow the global vocabulary [text 0..V-1 | <sync> V | time | score]: head 0 = text + <sync>, 1 = time,
+// 2 = score.  The one device statement of the three id ranges [lo, hi).
+__device__ __forceinline__ void head_bounds(int head, int V, int Tv, int Sv, int& lo, int& hi) {
+    lo = head == 0 ? 0 : (head == 1 ? V + 1 : V + 1 + Tv);
+    hi = head == 0 ? V + 1 : (head == 1 ? V + 1 + Tv : V + 1 + Tv + Sv);
+}
+
 // XCD-aware bijective remap of a 1-D block id: the dispatcher places block b on XCD b%8, so give each
 // XCD a contiguous chunk of logical tile ids (neighbouring tiles share operand panels in that XCD's L2).
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {

@@ -18,8 +18,6 @@
 
 #include "common.h"
 #include "kernels.h"
-#include "sample.h"
-#include "select.h"
 
 namespace {
 
@@ -833,8 +831,8 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_decode_kernel(const bf16_t* _
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Heads.  Wh rows follow the global vocabulary [text 0..V-1 | <sync> V | time | score], padded to 16 (head_bounds and the token selection,
-// select_next_kernel: select.h).
+// Heads.  Wh rows follow the global vocabulary [text 0..V-1 | <sync> V | time | score], padded to 16 (head_bounds: common.h; the token selection,
+// select_next_kernel: select.hip).
 __global__ __launch_bounds__(512) void head_logits_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ Wh,
                                                           int H, const int32_t* __restrict__ heads, int V, int Tv, int Sv,
                                                           float* __restrict__ part_val, int32_t* __restrict__ part_idx,
@@ -1165,20 +1163,5 @@ int launch_head_logits(const bf16_t* X, int ldx, const bf16_t* Wh, int H, const 
         hipLaunchKernelGGL(head_logits_kernel, dim3(ntiles), dim3(512), 0, s, X + (size_t)b0 * ldx, ldx, Wh, H, heads + b0, V, Tv, Sv,
                            part_val + (size_t)b0 * ntiles, part_idx + (size_t)b0 * ntiles,
                            logits_out ? logits_out + (size_t)b0 * NV : nullptr, std::min(32, B - b0), ntiles);
-    return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
-}
-
-int launch_select_next(const float* part_val, const int32_t* part_idx, const StepState& st, const bf16_t* embed,
-                       const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B,
-                       int H, int V, int Tv, int Sv, int advance, hipStream_t s, const float* logits, const SampleParams* sp) {
-    if (B < 1 || B > SK_ROWS || H % 8) return TRACE_ERR_ARG;
-    if ((logits == nullptr) != (sp == nullptr)) return TRACE_ERR_ARG;
-    const int ntiles = (V + 1 + Tv + Sv + 15) / 16;
-    if (sp)
-        hipLaunchKernelGGL(select_next_kernel<SELECT_SAMPLE>, dim3(B), dim3(256), 0, s, part_val, part_idx, st, embed, time_tab, score_tab,
-                           sync_row, xnext, ldx, B, H, V, Tv, Sv, ntiles, advance, logits, sp);
-    else
-        hipLaunchKernelGGL(select_next_kernel<SELECT_TILES>, dim3(B), dim3(256), 0, s, part_val, part_idx, st, embed, time_tab, score_tab,
-                           sync_row, xnext, ldx, B, H, V, Tv, Sv, ntiles, advance, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

@@ -45,6 +45,11 @@ constexpr int PF_MAX_N = 8;      // SHORTER prompts while n x L fits them (round
 static size_t pf_rows(int max_ctx) { return std::max<size_t>((size_t)PF_MAX * max_ctx, std::min<size_t>(8192, (size_t)PF_MAX_N * max_ctx)); }
 constexpr int MAX_SLOTS = 512;   // KV-cache sequence slots per context (a decode batch is at most SK_ROWS of them)
 static int g_ctx_per_dev[16] = {0};
+// what the tail of a decode step does beyond the plain arg-max; index(): its place in the graph cache, 0 = the plain step
+struct TailMode {
+    bool sample = false, logprobs = false, process = false;
+    int index() const { return (sample ? 1 : 0) + (logprobs ? 2 : 0) + (process ? 4 : 0); }
+};
 
 struct trace_ctx {
     trace_config c{};
@@ -120,31 +125,27 @@ struct trace_ctx {
     double kbytes_sum = 0.0;           // algorithmic bytes of the bracketed launches (profile == 2)
     int host_mode = 0, fed = 0;        // host-driven token selection (sampling): head logits only, ids fed back by the host
     int steps_done = 0;                // decode steps taken since trace_decode_begin (bounded by max_new - 1: the KV slot and the RoPE tables end at max_ctx)
-    hipGraphExec_t graphs[SK_ROWS + 1] = {nullptr};   // one captured decode step per batch size
-    hipGraphExec_t graphs_sample[SK_ROWS + 1] = {nullptr};   // the same with the sampling form of the token selection
-    hipGraphExec_t graphs_lp[SK_ROWS + 1] = {nullptr};          // both again with the log-probability launch after the selection: a step with it is
-    hipGraphExec_t graphs_sample_lp[SK_ROWS + 1] = {nullptr};   // another graph, so toggling the setting between batches never replays the other form
-    // sampling (trace_decode_set_sampling): host copy of the params, armed at trace_decode_begin; the device copy d_sparams is what the
-    // selection kernel reads (a captured graph stays valid across calls), d_slog the [SK_ROWS][NV] masked logits it samples from
+    // What the tail of a step (head_and_select) does beyond the plain arg-max: `want` is written by the three trace_decode_set_* calls, `armed` at
+    // trace_decode_begin (= want, or all-off in host-select mode, where the host holds the logits and does all three itself).  A step of each
+    // mode is a graph of its own, graphs[armed.index()][B]: toggling a setting between batches never replays another form, and index 0 is the plain step.
+    TailMode want, armed;
+    hipGraphExec_t graphs[8][SK_ROWS + 1] = {{nullptr}};
+    // sampling (trace_decode_set_sampling): host copy of the params; the device copy d_sparams, written at trace_decode_begin, is what the selection
+    // kernel reads (a captured graph stays valid across calls).  d_slog: the [SK_ROWS][NV] raw masked logits of a step with anything armed.
     SampleParams samp{};
-    int samp_set = 0, samp_on = 0;
     SampleParams* d_sparams = nullptr;
     float* d_slog = nullptr;
-    // per-token log-probabilities (trace_decode_set_logprobs): armed at trace_decode_begin like the sampling; d_logprobs [SK_ROWS][max_new_tokens]
-    // (rows of the current batch at stride max_new), written by the launch after the selection from the same d_slog rows
-    int lp_set = 0, lp_on = 0;
+    // per-token log-probabilities (trace_decode_set_logprobs): d_logprobs [SK_ROWS][max_new_tokens] (rows of the current batch at stride max_new),
+    // written by the launch after the selection from the d_slog rows
     float* d_logprobs = nullptr;
     // scoring given tokens (trace_llm_score_rows / _append, score.hip): allocated on first use for pf_rows() rows — the tile partials, the rows' heads
     // and target ids, their log-probabilities
     float* score_ws = nullptr; int32_t* d_score_heads = nullptr; int32_t* d_score_ids = nullptr; float* d_score_out = nullptr;
-    // logits processors (trace_decode_set_logits_params): armed at trace_decode_begin like the sampling; the device copy d_lgparams is what
-    // logits_process_kernel reads, d_plog the [SK_ROWS][NV] processed rows the selection then reads (d_slog stays raw: the log-probabilities' rows).
-    // graphs_logits[sampling + 2 * logprobs]: steps with the extra launch are cached apart, so a disarmed batch replays the graphs it always did
+    // logits processors (trace_decode_set_logits_params): the device copy d_lgparams, written at trace_decode_begin, is what logits_process_kernel
+    // reads, d_plog the [SK_ROWS][NV] processed rows the selection then reads (d_slog stays raw: the log-probabilities' rows)
     LogitsParams lgp{1.f, 0, 0};
-    int lgp_set = 0, lgp_on = 0;
     LogitsParams* d_lgparams = nullptr;
     float* d_plog = nullptr;
-    hipGraphExec_t graphs_logits[4][SK_ROWS + 1] = {{nullptr}};
     hipStream_t cap_stream = nullptr;
     std::vector<hipStream_t> streams;   // trace_stream_create
     // profiling
@@ -484,11 +485,7 @@ extern "C" int trace_ctx_destroy(trace_ctx* c) {
     (void)hipSetDevice(c->dev);       // the calling thread's current device may be another GPU: everything below (and the counters' key) is this context's
     hipDeviceSynchronize();
     for (auto& st : c->streams) { gemm_pers_forget(st); hipStreamDestroy(st); }
-    for (auto& g : c->graphs) if (g) hipGraphExecDestroy(g);
-    for (auto& g : c->graphs_sample) if (g) hipGraphExecDestroy(g);
-    for (auto& g : c->graphs_lp) if (g) hipGraphExecDestroy(g);
-    for (auto& g : c->graphs_sample_lp) if (g) hipGraphExecDestroy(g);
-    for (auto& row : c->graphs_logits) for (auto& g : row) if (g) hipGraphExecDestroy(g);
+    for (auto& row : c->graphs) for (auto& g : row) if (g) hipGraphExecDestroy(g);
     for (auto& e : c->kev) if (e) hipEventDestroy(e);
     for (auto& e : c->vev) if (e) hipEventDestroy(e);
     if (c->mev0) hipEventDestroy(c->mev0);
@@ -1329,26 +1326,26 @@ static int head_only(trace_ctx* c, const bf16_t* xn, float* logits_out, hipStrea
                             c->B, s));
     return TRACE_OK;
 }
-static int select_only(trace_ctx* c, int advance, hipStream_t s, const float* sample_logits = nullptr) {
-    LCHK(launch_select_next(c->part_val, c->part_idx, step_state(c), c->embed, c->time_tab, c->score_tab, c->sync_row, c->dX,
-                            c->H, c->B, c->H, c->V, c->Tv, c->Sv, advance, s, sample_logits, sample_logits ? c->d_sparams : nullptr));
+// the selection in one of its forms; `rows`: the masked logits SELECT_SAMPLE / SELECT_ROW read (null for SELECT_TILES, which reads the tile partials)
+static int select_only(trace_ctx* c, int form, const float* rows, int advance, hipStream_t s) {
+    LCHK(launch_select(form, c->part_val, c->part_idx, rows, form == SELECT_SAMPLE ? c->d_sparams : nullptr, step_state(c), c->embed, c->time_tab,
+                       c->score_tab, c->sync_row, c->dX, c->H, c->B, c->H, c->V, c->Tv, c->Sv, advance, s));
     return TRACE_OK;
 }
 static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* logits_out, hipStream_t s) {
-    // sampling / log-probabilities: both read the masked logits rows the head kernel writes (the caller's logits_out, else d_slog)
-    float* lg = (c->samp_on || c->lp_on || c->lgp_on) && !c->host_mode && !logits_out ? c->d_slog : logits_out;
-    TRY(head_only(c, xn, lg, s));
-    if (c->host_mode) return TRACE_OK;      // the host picks the token and calls trace_decode_feed
-    if (c->lgp_on) {
-        // logits processors: the raw rows -> d_plog, and the selection (sampled, or the arg-max over the row) reads d_plog; lg stays raw for the launch below
-        LCHK(launch_step_logits_process(lg, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_lgparams, c->d_plog, s));
-        if (c->samp_on) TRY(select_only(c, advance, s, c->d_plog));
-        else LCHK(launch_select_row(c->d_plog, step_state(c), c->embed, c->time_tab, c->score_tab, c->sync_row, c->dX, c->H, c->B, c->H, c->V, c->Tv, c->Sv,
-                                    advance, s));
-    } else
-    TRY(select_only(c, advance, s, c->samp_on ? lg : nullptr));
-    // the log-probability of the token just recorded: after the selection (it reads out_ids / out_len / the advanced step counter), from the same rows
-    if (c->lp_on) LCHK(launch_step_logprob(lg, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_logprobs, s));
+    const TailMode m = c->armed;
+    // 1. the head: tile partials, and the raw masked rows into the caller's logits_out, else d_slog when anything armed will read them, else nowhere
+    float* raw = !logits_out && m.index() ? c->d_slog : logits_out;
+    TRY(head_only(c, xn, raw, s));
+    // 2. host-select mode ends here: the host picks the token and calls trace_decode_feed
+    if (c->host_mode) return TRACE_OK;
+    // 3. logits processors: the raw rows -> d_plog (raw stays as it is for step 5)
+    if (m.process) LCHK(launch_step_logits_process(raw, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_lgparams, c->d_plog, s));
+    // 4. the selection: a draw from the rows, the arg-max over a processed row, or the arg-max over the tile partials (they describe the raw row)
+    const int form = m.sample ? SELECT_SAMPLE : m.process ? SELECT_ROW : SELECT_TILES;
+    TRY(select_only(c, form, form == SELECT_TILES ? nullptr : m.process ? c->d_plog : raw, advance, s));
+    // 5. the log-probability of the token just recorded (it reads out_ids / out_len / the advanced step counter), on the raw rows
+    if (m.logprobs) LCHK(launch_step_logprob(raw, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_logprobs, s));
     return TRACE_OK;
 }
 
@@ -1551,7 +1548,7 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
         if (pos[b] + max_new > c->max_ctx) return fail(TRACE_ERR_ARG, "prefill + max_new_tokens exceeds max_ctx");
         for (int b2 = 0; b2 < b; ++b2) if (slots[b2] == slots[b]) return fail(TRACE_ERR_ARG, "duplicate slot");
     }
-    if (forced && c->lgp_set && !c->host_mode)
+    if (forced && c->want.process && !c->host_mode)
         return fail(TRACE_ERR_ARG, "logits processors (trace_decode_set_logits_params) with forced ids: the history is the recorded ids, not the fed ones");
     c->B = B; c->max_new = max_new; c->eos = eos; c->has_forced = forced != nullptr;
     c->pos_sum = 0;
@@ -1565,12 +1562,11 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     HIPCHK(hipMemsetAsync(c->d_out_ids, 0, (size_t)B * max_new * 4, s));
     const int32_t prm[3] = {max_new, eos, c->host_mode};
     HIPCHK(hipMemcpyAsync(c->d_params, prm, 12, hipMemcpyHostToDevice, s));
-    c->samp_on = c->samp_set && !c->host_mode;     // host-select mode: the host picks (trace_op_sample), the device only feeds
-    if (c->samp_on) HIPCHK(hipMemcpyAsync(c->d_sparams, &c->samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
-    c->lp_on = c->lp_set && !c->host_mode;         // host-select mode: the host has the logits and calls trace_op_token_logprob on them
-    if (c->lp_on) HIPCHK(hipMemsetAsync(c->d_logprobs, 0, (size_t)B * max_new * 4, s));    // entries past a row's length stay 0.0
-    c->lgp_on = c->lgp_set && !c->host_mode;       // host-select mode: the host holds the logits and calls trace_op_logits_process on them
-    if (c->lgp_on) HIPCHK(hipMemcpyAsync(c->d_lgparams, &c->lgp, sizeof(LogitsParams), hipMemcpyHostToDevice, s));
+    // host-select mode arms nothing: the host holds the logits and calls trace_op_logits_process / trace_op_sample / trace_op_token_logprob on them
+    c->armed = c->host_mode ? TailMode{} : c->want;
+    if (c->armed.sample) HIPCHK(hipMemcpyAsync(c->d_sparams, &c->samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+    if (c->armed.logprobs) HIPCHK(hipMemsetAsync(c->d_logprobs, 0, (size_t)B * max_new * 4, s));    // entries past a row's length stay 0.0
+    if (c->armed.process) HIPCHK(hipMemcpyAsync(c->d_lgparams, &c->lgp, sizeof(LogitsParams), hipMemcpyHostToDevice, s));
     c->fed = 0; c->steps_done = 0;
     if (forced) HIPCHK(hipMemcpyAsync(c->d_forced, forced, (size_t)B * max_new * 4, hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemsetAsync(c->d_forced, 0xff, (size_t)B * max_new * 4, s));      // -1 = not forced
@@ -1597,10 +1593,7 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
     if (!use_graph) {
         for (int i = 0; i < n; ++i) { c->step_in_call = steps_before + i; TRY(decode_step(c, logits_out, s)); }
     } else {
-        const int key = c->B;
-        hipGraphExec_t* slot_g = c->lgp_on ? &c->graphs_logits[(c->samp_on ? 1 : 0) + (c->lp_on ? 2 : 0)][key]
-                               : c->lp_on ? (c->samp_on ? &c->graphs_sample_lp[key] : &c->graphs_lp[key])
-                                          : (c->samp_on ? &c->graphs_sample[key] : &c->graphs[key]);
+        hipGraphExec_t* slot_g = &c->graphs[c->armed.index()][c->B];
         if (!*slot_g) {
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamSynchronize(s));
@@ -1666,25 +1659,32 @@ static SampleParams make_sampling(float T, int k, float p, uint64_t seed) {
     return sp;
 }
 
+// The requested tail mode becomes m, once the buffers it needs exist (allocated on first use): the raw rows for any request, the processed rows,
+// the log-probabilities.  A context that never requests anything allocates none of them.
+static int set_want(trace_ctx* c, TailMode m) {
+    if (m.index() && !c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
+    if (m.process && !c->d_plog) TRY(dalloc(c, &c->d_plog, (size_t)SK_ROWS * c->NV));
+    if (m.logprobs && !c->d_logprobs) TRY(dalloc(c, &c->d_logprobs, (size_t)SK_ROWS * c->c.max_new_tokens));
+    c->want = m;
+    return TRACE_OK;
+}
+
 extern "C" int trace_decode_set_sampling(trace_ctx* c, float temperature, int top_k, float top_p, uint64_t seed) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
     if (std::isnan(temperature)) return fail(TRACE_ERR_ARG, "temperature is NaN");
-    if (temperature <= 0.f) { c->samp_set = 0; return TRACE_OK; }          // greedy
-    if (const char* m = sampling_bad(temperature, top_k, top_p)) return fail(TRACE_ERR_ARG, m);
-    if (!c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
+    TailMode m = c->want;
+    m.sample = temperature > 0.f;                                          // <= 0: greedy
+    if (!m.sample) return set_want(c, m);
+    if (const char* e = sampling_bad(temperature, top_k, top_p)) return fail(TRACE_ERR_ARG, e);
     c->samp = make_sampling(temperature, top_k, top_p, seed);
-    c->samp_set = 1;
-    return TRACE_OK;
+    return set_want(c, m);
 }
 
 extern "C" int trace_decode_set_logprobs(trace_ctx* c, int on) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
-    if (on) {
-        if (!c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
-        if (!c->d_logprobs) TRY(dalloc(c, &c->d_logprobs, (size_t)SK_ROWS * c->c.max_new_tokens));
-    }
-    c->lp_set = on ? 1 : 0;
-    return TRACE_OK;
+    TailMode m = c->want;
+    m.logprobs = on != 0;
+    return set_want(c, m);
 }
 
 static const char* logits_params_bad(float p, int n, int m) {
@@ -1698,12 +1698,9 @@ extern "C" int trace_decode_set_logits_params(trace_ctx* c, float repetition_pen
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
     if (const char* m = logits_params_bad(repetition_penalty, no_repeat_ngram_size, min_new_tokens)) return fail(TRACE_ERR_ARG, m);
     c->lgp = LogitsParams{repetition_penalty, no_repeat_ngram_size, min_new_tokens};
-    c->lgp_set = repetition_penalty != 1.f || no_repeat_ngram_size != 0 || min_new_tokens != 0;
-    if (c->lgp_set) {
-        if (!c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
-        if (!c->d_plog) TRY(dalloc(c, &c->d_plog, (size_t)SK_ROWS * c->NV));
-    }
-    return TRACE_OK;
+    TailMode m = c->want;
+    m.process = repetition_penalty != 1.f || no_repeat_ngram_size != 0 || min_new_tokens != 0;
+    return set_want(c, m);
 }
 
 extern "C" int trace_op_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
@@ -1720,7 +1717,7 @@ extern "C" int trace_op_logits_process(const float* logits, int ld, int B, const
 
 extern "C" int trace_decode_read_logprobs(trace_ctx* c, float* out, void* stream) {
     if (!c || c->B < 1) return fail(TRACE_ERR_STATE, "trace_decode_begin not called");
-    if (!c->lp_on) return fail(TRACE_ERR_STATE, "the current batch was begun without log-probabilities (trace_decode_set_logprobs)");
+    if (!c->armed.logprobs) return fail(TRACE_ERR_STATE, "the current batch was begun without log-probabilities (trace_decode_set_logprobs)");
     if (!out) return fail(TRACE_ERR_ARG, "null pointer");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemcpyAsync(out, c->d_logprobs, (size_t)c->B * c->max_new * 4, hipMemcpyDeviceToHost, s));
@@ -1815,7 +1812,7 @@ extern "C" int trace_decode_feed(trace_ctx* c, const int32_t* tokens, int B, voi
         HIPCHK(hipMemcpyAsync(c->d_forced + (size_t)b * c->max_new + c->fed, tokens + b, 4, hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipStreamSynchronize(s));
-    TRY(select_only(c, c->fed > 0 ? 1 : 0, s));
+    TRY(select_only(c, SELECT_TILES, nullptr, c->fed > 0 ? 1 : 0, s));
     c->fed += 1;
     return TRACE_OK;
 }

@@ -210,7 +210,7 @@ int launch_attn_decode(const bf16_t* qkv, int ldq, bf16_t* kcache, bf16_t* vtcac
 // head's range are computed.  part: [B, ntiles] (max,idx).  logits_out optional [B, NV] fp32 (masked -inf).
 int launch_head_logits(const bf16_t* X, int ldx, const bf16_t* Wh, int H, const int32_t* heads, int V, int Tv, int Sv,
                        float* part_val, int32_t* part_idx, float* logits_out, int B, hipStream_t s);
-// argmax over partials + state machine + next-token embedding
+// token selection + state machine + next-token embedding (select.hip)
 struct SampleParams;   // sample.h
 struct StepState {
     int32_t* heads;       // [B] in/out
@@ -222,16 +222,19 @@ struct StepState {
     const int32_t* forced;// [B, max_new] teacher-forcing ids; negative entry = feed the arg-max
     const int32_t* params;// device [3]: max_new, eos, record_feed (device-resident so a captured graph stays valid)
 };
-int launch_select_next(const float* part_val, const int32_t* part_idx, const StepState& st, const bf16_t* embed,
-                       const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx,
-                       int B, int H, int V, int Tv, int Sv, int advance, hipStream_t s, const float* logits = nullptr,
-                       const SampleParams* sp = nullptr);
-// the sampling form above (logits + sp given) = sample.h's sampler; the same device code for loose rows (trace_op_sample): logits [B][ld] fp32,
-// heads / steps int32 [B] (device) -> out_ids [B] global ids
+// The one launcher of select_next_kernel, by form.  SELECT_TILES: the arg-max over launch_head_logits' partials (logits and sp null).  SELECT_SAMPLE:
+// a draw by sample.h's sampler from rows `logits` [B][NV] fp32 (masked, raw or processed) under the device params *sp.  SELECT_ROW: the arg-max
+// over the head's range of such rows, the lowest id among equal maxima as the partials have it (sp null).
+enum { SELECT_TILES = 0, SELECT_SAMPLE = 1, SELECT_ROW = 2 };
+int launch_select(int form, const float* part_val, const int32_t* part_idx, const float* logits, const SampleParams* sp, const StepState& st,
+                  const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H,
+                  int V, int Tv, int Sv, int advance, hipStream_t s);
+// SELECT_SAMPLE's sampler as the same device code for loose rows (trace_op_sample): logits [B][ld] fp32, heads / steps int32 [B] (device) ->
+// out_ids [B] global ids
 int launch_sample_rows(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const SampleParams& sp, const int32_t* steps,
                        int32_t* out_ids, hipStream_t s);
 // log-probability of one token per row (sample.h token_logprob_row; the raw masked logits, no warping).  Loose rows: ids / heads int32 [B],
-// out fp32 [B] (trace_op_token_logprob).  Decode step: after launch_select_next on the same stream, over the rows of masked logits the head
+// out fp32 [B] (trace_op_token_logprob).  Decode step: after launch_select on the same stream, over the rows of masked logits the head
 // kernel wrote for this step [B][NV]; writes out_logprobs[b][step] ([B][max_new]) where select_next recorded a token in this step.
 int launch_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out, hipStream_t s);
 int launch_step_logprob(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, float* out_logprobs, hipStream_t s);
@@ -249,13 +252,11 @@ int launch_score_rows(const bf16_t* X, int ld, const bf16_t* W, int ldw, int K, 
 // logits processors (logits.h: repetition penalty, no-repeat n-grams, min_new_tokens) from a row of masked logits into a row of their own.
 // Loose rows: hist int32 [B][ld_hist] / hist_len / heads / steps int32 [B] (device), out [B][ldo] written whole, -inf outside the head
 // (trace_op_logits_process).  Decode step: between launch_head_logits and the selection of the same step, history = st.out_ids / st.out_len,
-// params *dlp (device), rows [B][NV] -> [B][NV] (the head's range only).  launch_select_row: launch_select_next's greedy form over such rows.
+// params *dlp (device), rows [B][NV] -> [B][NV] (the head's range only), which launch_select's SELECT_SAMPLE / SELECT_ROW forms then read.
 struct LogitsParams;   // logits.h
 int launch_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
                           const int32_t* hist_len, const int32_t* steps, int eos, const LogitsParams& lp, float* out, int ldo, hipStream_t s);
 int launch_step_logits_process(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, const LogitsParams* dlp, float* out, hipStream_t s);
-int launch_select_row(const float* logits, const StepState& st, const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab,
-                      const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H, int V, int Tv, int Sv, int advance, hipStream_t s);
 
 // ---- fp8 (e4m3) weight path of the decoder (fp8.hip; the fp8 GEMM is launch_gemm_bf16 with GemmArgs::fp8 set) ----
 // X bf16 [rows][K] -> X8 e4m3 [rows][K] + sx[row] = amax/448 (per-row dynamic scale).  Also used row-wise on weight matrices at load.

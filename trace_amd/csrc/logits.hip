@@ -1,13 +1,11 @@
 // logits_process_kernel: the logits processors (logits.h) as a launch between head_logits_kernel and select_next_kernel, and over loose rows
-// (trace_op_logits_process: the unit tests and the host-driven decode loop) — the same device code.  Also the greedy selection over a processed
-// row, select_next_kernel<SELECT_ROW> (select.h): the tile partials of head_logits_kernel describe the raw row, so a step with processors takes
-// its arg-max from the processed one.
+// (trace_op_logits_process: the unit tests and the host-driven decode loop) — the same device code.  The tile partials of head_logits_kernel
+// describe the raw row, so a greedy step with processors takes its arg-max from the processed one: select_next_kernel<SELECT_ROW> (select.hip).
 #include <algorithm>
 
 #include "common.h"
 #include "kernels.h"
 #include "logits.h"
-#include "select.h"
 
 namespace {
 
@@ -64,13 +62,5 @@ int launch_step_logits_process(const float* logits, const StepState& st, int B, 
     if (lds > 32768) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(LOGITS_THREADS), lds, s, logits, NV, st.heads, V, Tv, Sv, st.out_ids, 0, st.out_len, st.step, -1,
                        LogitsParams{1.f, 0, 0}, st.params, dlp, out, NV, lds / 4);
-    return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
-}
-
-int launch_select_row(const float* logits, const StepState& st, const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab,
-                      const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H, int V, int Tv, int Sv, int advance, hipStream_t s) {
-    if (B < 1 || B > SK_ROWS || H % 8 || !logits) return TRACE_ERR_ARG;
-    hipLaunchKernelGGL(select_next_kernel<SELECT_ROW>, dim3(B), dim3(256), 0, s, nullptr, nullptr, st, embed, time_tab, score_tab, sync_row, xnext, ldx,
-                       B, H, V, Tv, Sv, 0, advance, logits, nullptr);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

@@ -1,5 +1,5 @@
 // trace_op_sample: the device sampler (sample.h) over loose rows of masked head logits — the kernel-level entry of the tests and the sampler of
-// the host-driven (stopping-criteria) decode loop.  The decode step itself samples inside select_next_kernel<SELECT_SAMPLE> (decode.hip): the same
+// the host-driven (stopping-criteria) decode loop.  The decode step itself samples inside select_next_kernel<SELECT_SAMPLE> (select.hip): the same
 // sample_row, so both paths pick the same id from the same row, params, step and row index.
 #include "common.h"
 #include "kernels.h"
@@ -13,7 +13,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float
     __shared__ SampleLds L;
     const int b = blockIdx.x;
     const int head = heads[b];
-    const int lo = head == 0 ? 0 : (head == 1 ? V + 1 : V + 1 + Tv);
+    const int lo = head == 0 ? 0 : (head == 1 ? V + 1 : V + 1 + Tv);       // head_bounds (common.h), written out: the call compiles to another stream here
     const int hi = head == 0 ? V + 1 : (head == 1 ? V + 1 + Tv : V + 1 + Tv + Sv);
     const int id = lo + sample_row(logits + (size_t)b * ld + lo, hi - lo, sp, (uint32_t)steps[b], (uint32_t)b, L);
     if (threadIdx.x == 0) out_ids[b] = id;
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void token_logprob_kernel(const flo
         head = id <= V ? 0 : (id < V + 1 + Tv ? 1 : 2);
         o = (size_t)b * max_new + step;
     }
-    const int lo = head == 0 ? 0 : (head == 1 ? V + 1 : V + 1 + Tv);
+    const int lo = head == 0 ? 0 : (head == 1 ? V + 1 : V + 1 + Tv);       // (head_bounds written out, as above)
     const int hi = head == 0 ? V + 1 : (head == 1 ? V + 1 + Tv : V + 1 + Tv + Sv);
     const float lp = token_logprob_row(logits + (size_t)b * ld + lo, hi - lo, id >= lo && id < hi ? id - lo : -1, fbuf, wmax);
     if (threadIdx.x == 0) out[o] = lp;

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(64) void score_merge_kernel(ScoreArgs p) {
     extern __shared__ __attribute__((aligned(16))) float buf[];
     const int row = blockIdx.x, lane = threadIdx.x;
     const int head = p.heads[row], id = p.ids[row];
-    const int lo = head == 0 ? 0 : (head == 1 ? p.V + 1 : p.V + 1 + p.Tv);
+    const int lo = head == 0 ? 0 : (head == 1 ? p.V + 1 : p.V + 1 + p.Tv);   // head_bounds (common.h), written out: the call compiles to another stream here
     const int hi = head == 0 ? p.V + 1 : (head == 1 ? p.V + 1 + p.Tv : p.V + 1 + p.Tv + p.Sv);
     if (id < lo || id >= hi) {                                  // (uniform over the wave)
         if (lane == 0) p.out[row] = id == -1 ? 0.f : -INFINITY;

@@ -1,23 +1,11 @@
-// The token selection of a decode step: select_next_kernel, one workgroup per sequence.  A header because its three forms are instantiated in two
-// translation units: the arg-max over the tile partials and the sampler in decode.hip (as before), the arg-max over a processed logits row in
-// logits.hip (the step with logits processors, logits.h).  Forced ids, EOS, record_feed, the head switch and the embedding gather are one body.
-#pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+// The token selection of a decode step: select_next_kernel, one workgroup per sequence, and its one launcher.  Three forms: the arg-max over the
+// tile partials of head_logits_kernel (greedy), the sampler (sample.h) over a row of masked logits, and the arg-max over a processed logits row
+// (the step with logits processors, logits.h).  Forced ids, EOS, record_feed, the head switch and the embedding gather are one body.
 #include "common.h"
 #include "kernels.h"
 #include "sample.h"
 
 namespace {
-
-// Heads.  Wh rows follow the global vocabulary [text 0..V-1 | <sync> V | time | score], padded to 16.
-__device__ __forceinline__ void head_bounds(int head, int V, int Tv, int Sv, int& lo, int& hi) {
-    lo = head == 0 ? 0 : (head == 1 ? V + 1 : V + 1 + Tv);
-    hi = head == 0 ? V + 1 : (head == 1 ? V + 1 + Tv : V + 1 + Tv + Sv);
-}
-
-enum { SELECT_TILES = 0, SELECT_SAMPLE = 1, SELECT_ROW = 2 };
 
 // one workgroup per sequence.  `step` is shared: every workgroup reads it first, then checks in; the last one to
 // check in advances it (so no workgroup can observe the next step's value).
@@ -122,3 +110,23 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
 }
 
 }  // namespace
+
+int launch_select(int form, const float* part_val, const int32_t* part_idx, const float* logits, const SampleParams* sp, const StepState& st,
+                  const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H,
+                  int V, int Tv, int Sv, int advance, hipStream_t s) {
+    if (B < 1 || B > SK_ROWS || H % 8) return TRACE_ERR_ARG;
+    if ((form != SELECT_TILES) != (logits != nullptr) || (form == SELECT_SAMPLE) != (sp != nullptr)) return TRACE_ERR_ARG;
+    const int ntiles = (V + 1 + Tv + Sv + 15) / 16;
+    const dim3 grid(B), block(256);
+    if (form == SELECT_TILES)
+        hipLaunchKernelGGL(select_next_kernel<SELECT_TILES>, grid, block, 0, s, part_val, part_idx, st, embed, time_tab, score_tab, sync_row, xnext, ldx, B, H, V, Tv,
+                           Sv, ntiles, advance, logits, sp);
+    else if (form == SELECT_SAMPLE)
+        hipLaunchKernelGGL(select_next_kernel<SELECT_SAMPLE>, grid, block, 0, s, part_val, part_idx, st, embed, time_tab, score_tab, sync_row, xnext, ldx, B, H, V, Tv,
+                           Sv, ntiles, advance, logits, sp);
+    else if (form == SELECT_ROW)
+        hipLaunchKernelGGL(select_next_kernel<SELECT_ROW>, grid, block, 0, s, part_val, part_idx, st, embed, time_tab, score_tab, sync_row, xnext, ldx, B, H, V, Tv,
+                           Sv, ntiles, advance, logits, sp);
+    else return TRACE_ERR_ARG;
+    return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
+}

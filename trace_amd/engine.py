@@ -13,7 +13,7 @@ from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
 from .prefix import APPEND_GROUP_MAX, group_by_length, split_questions
-from .sampling import LogitsParams, SamplingParams, sample_rows_host
+from .sampling import LogitsParams, SamplingParams, argmax_rows, sample_rows_host
 from . import scoring
 
 __all__ = ["TraceEngine", "SamplingParams", "ops"]
@@ -693,7 +693,7 @@ class TraceEngine:
         if armed and forced is not None:
             raise ValueError("logits processors act on the ids a row has recorded; under forced ids those are not the fed ones (forced= with logits=)")
         if sampling is not None and not sampling.greedy and not sampling.on_device:
-            return self._decode_host_sampled(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits if armed else None)
+            return self.decode_stepwise(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits)
         on_dev = sampling is not None and not sampling.greedy
         if on_dev:
             self.set_sampling(sampling)
@@ -711,32 +711,52 @@ class TraceEngine:
             if on_dev:
                 self.set_sampling(None)
 
-    def _decode_host_sampled(self, slots, heads, max_new_tokens, eos, forced, sampling: SamplingParams, logprobs: bool = False,
-                             logits: Optional[LogitsParams] = None):
-        B = len(slots)
+    def decode_stepwise(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1,
+                        forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
+                        logits: Optional[LogitsParams] = None, stopping=None):
+        """decode() one eager step at a time with the token picked on the host: the one loop in host-select mode (sampling parameters outside the
+        device sampler's domain, stopping criteria).  Every rule is the device step's.  The row the pick reads is the processed one
+        (logits_process: the history is the ids recorded so far) when `logits` is armed, else the raw one; sampled rows go through sample(),
+        greedy rows take the lowest id among equal maxima of the head's range; a forced id overrides the pick; the log-probability is the fed
+        token's on the raw row.  A row is finished when its recorded ids end in `eos` or `stopping` fired for it - stopping(ids per row) ->
+        one bool per row, asked after every step but the last while some row is unfinished; a row it fired for keeps the ids (and log-probabilities) it held then,
+        while its returned head is the whole run's: the device goes on feeding it, as it does a row past its EOS.  The greedy pick is taken on the
+        device (sampling.argmax_rows: B ids come back); the recorded ids are read back after every step, since both finished rules look at them.  The
+        loop ends when every row is finished or max_new_tokens ids were fed.  Returns what decode() returns."""
+        B, cfg = len(slots), self.cfg
+        greedy = sampling is None or sampling.greedy
+        armed = logits is not None and not logits.off
         self.host_mode(True)
         try:
-            lg = self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, want_logits=True)
-            cur = list(heads)
-            ids = [[] for _ in range(B)]
+            raw = self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, want_logits=True)
+            ids, cur = [[] for _ in range(B)], list(heads)
             lp = np.zeros((B, max_new_tokens), np.float32)
+            stopped = [None] * B                          # the length at which `stopping` fired for the row
             for step in range(max_new_tokens):
-                # (logits processors: the loose op on the rows brought back, the history = the ids recorded so far; the log-probability stays the raw row's)
-                tok = self.sample(self.logits_process(lg, cur, ids, logits, [step] * B, eos) if logits is not None else lg, cur, sampling, [step] * B)
+                rows = self.logits_process(raw, cur, ids, logits, [step] * B, eos) if armed else raw
+                if greedy:
+                    tok = argmax_rows(rows, cur, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size)
+                else:
+                    tok = self.sample(rows, cur, sampling, [step] * B)
                 if forced is not None:
                     tok = [f[step] if step < len(f) and f[step] >= 0 else t for t, f in zip(tok, forced)]
-                val = self.token_logprob(lg, cur, tok) if logprobs else None       # host-select mode: the fed token, under the head it was drawn from
+                val = self.token_logprob(raw, cur, tok) if logprobs else None       # under the head the token was picked from
                 self.feed(tok)
                 ids, cur = self.decode_read()
                 if logprobs:
                     for b in range(B):
                         if len(ids[b]) == step + 1:
                             lp[b, step] = val[b]
-                if step == max_new_tokens - 1 or (eos >= 0 and all(len(x) and x[-1] == eos for x in ids)):
+                if step == max_new_tokens - 1:
                     break
-                lg = self.decode_steps(1, use_graph=False, want_logits=True)
-            ids, hd = self.decode_read()
-            return (ids, hd, [lp[b, : len(x)].copy() for b, x in enumerate(ids)]) if logprobs else (ids, hd)
+                done = [eos >= 0 and len(x) > 0 and x[-1] == eos for x in ids]
+                if stopping is not None and not all(done):
+                    stopped = [len(x) if n is None and f else n for x, n, f in zip(ids, stopped, stopping(ids))]
+                if all(d or n is not None for d, n in zip(done, stopped)):
+                    break
+                raw = self.decode_steps(1, use_graph=False, want_logits=True)
+            ids = [x if n is None else x[:n] for x, n in zip(ids, stopped)]
+            return (ids, cur, [lp[b, : len(x)].copy() for b, x in enumerate(ids)]) if logprobs else (ids, cur)
         finally:
             self.host_mode(False)
 

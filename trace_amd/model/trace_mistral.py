@@ -15,7 +15,7 @@ from .. import scoring
 from ..config import TraceConfig
 from ..constants import MMODAL_TOKEN_INDEX, NUM_FRAMES
 from ..prefix import split_questions
-from ..sampling import LogitsParams, SamplingParams, check_sampling, head_bounds
+from ..sampling import LogitsParams, SamplingParams, check_sampling
 from .encoders import NumberTokenizer, ScoreTower, TimeTower
 
 
@@ -198,16 +198,9 @@ class TraceMistralForCausalLM:
         legacy_stc = video_timestamps is None and cfg.mm_projector_type == "stc_connector"
         if video_timestamps is None and not legacy_stc:
             raise ValueError("video_timestamps is required on the TRACE path (time tokens per frame)")
-        nf = cfg.num_frames if hasattr(cfg, "num_frames") else NUM_FRAMES
-        vids = []
         modals = list(modal_list or ["video"] * B)
-        for x, modal in zip(images_or_videos, modals):
-            if modal == "image":                                                  # trace_arch.py:221
-                x = x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
-            vids.append(x)
-        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
-        if eos is None:
-            eos = -1
+        vids = [self._as_frames(x, modal) for x, modal in zip(images_or_videos, modals)]
+        eos = self._eos(eos_token_id)
         id_lists = [row.tolist() for row in ids]
         if B > eng.max_batch:
             raise ValueError(f"batch {B} exceeds the engine's max_batch {eng.max_batch}")
@@ -217,13 +210,7 @@ class TraceMistralForCausalLM:
                 eng.vit_forward(vids[b])
                 eng.stc_connector(None, vids[b].shape[0])
                 eng.prefill(b, eng.splice(id_lists[b]))
-            if sampling is not None or output_logprobs or lgp is not None:
-                out, new_heads, *lps = eng.decode(list(range(B)), [0] * B, max_new_tokens, eos, sampling=sampling, logprobs=output_logprobs, **lg)
-            else:
-                eng.decode_begin(list(range(B)), [0] * B, max_new_tokens, eos)
-                if max_new_tokens > 1:
-                    eng.decode_steps(max_new_tokens - 1)
-                out, new_heads = eng.decode_read()
+            out, new_heads, *lps = eng.decode(list(range(B)), [0] * B, max_new_tokens, eos, sampling=sampling, logprobs=output_logprobs, **lg)
         elif not stopping_criteria:
             res = None
             if self._prefix_cache and all(isinstance(x, torch.Tensor) for x in images_or_videos):
@@ -233,20 +220,13 @@ class TraceMistralForCausalLM:
                                                                             sampling=sampling, logprobs=output_logprobs, **lg)
         else:
             out, new_heads, *lps = self._generate_stepwise(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos,
-                                                           sampling, stopping_criteria, ids, output_logprobs, lgp)
+                                                           sampling, stopping_criteria, output_logprobs, lgp)
         for b in range(B):                       # the reference mutates `heads` in place (trace_mistral.py:342)
             heads[b] = int(new_heads[b])
-        pad = eos if pad_token_id is None else pad_token_id
-        n = max(len(x) for x in out)
-        res = torch.full((B, n), pad if pad is not None and pad >= 0 else 0, dtype=torch.long)
-        for b, row in enumerate(out):
-            res[b, : len(row)] = torch.tensor(row, dtype=torch.long)
+        res, lp = self._padded(out, lps[0] if output_logprobs else None, eos if pad_token_id is None else pad_token_id)
         if not output_logprobs:
-            return res.to(self.device)
-        lp = torch.zeros((B, n), dtype=torch.float32)
-        for b, row in enumerate(lps[0]):
-            lp[b, : len(row)] = torch.from_numpy(np.asarray(row, np.float32))
-        return SimpleNamespace(sequences=res.to(self.device), logprobs=lp.to(self.device), heads=[int(h) for h in new_heads])
+            return res
+        return SimpleNamespace(sequences=res, logprobs=lp, heads=[int(h) for h in new_heads])
 
     @torch.no_grad()
     def generate_samples(self, inputs=None, images_or_videos=None, video_timestamps=None, n: int = 1, heads=None, max_new_tokens: int = 128,
@@ -272,29 +252,18 @@ class TraceMistralForCausalLM:
         sampling = self._sampling_params(True, temperature, top_k, top_p, _ProcessorsOff(generation_config, self.generation_config), kwargs)
         if sampling is None:
             raise ValueError("generate_samples needs temperature > 0: greedy rows would all be identical")
-        cfg, eng = self.config, self.engine
+        eng = self.engine
         head = 0 if heads is None else int(heads[0])
         eng.host_mode(False)
         self._live_kv = None
-        x = images_or_videos[0]
-        if (modal_list or ["video"])[0] == "image":
-            nf = cfg.num_frames if hasattr(cfg, "num_frames") else NUM_FRAMES
-            x = x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
-        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
-        if eos is None:
-            eos = -1
+        x = self._as_frames(images_or_videos[0], (modal_list or ["video"])[0])
+        eos = self._eos(eos_token_id)
         out, new_heads, lps = eng.generate_samples(x, video_timestamps[0], ids[0].tolist(), head, n, max_new_tokens, eos=eos, sampling=sampling,
                                                    **({} if lgp is None else {"logits": lgp}))
         scores = np.array([np.sum(np.asarray(r, np.float32), dtype=np.float64) for r in lps], np.float64)
         order = rank_samples(scores) if best_first else list(range(n))
-        pad = eos if pad_token_id is None else pad_token_id
-        m = max(len(r) for r in out)
-        seq = torch.full((n, m), pad if pad is not None and pad >= 0 else 0, dtype=torch.long)
-        lp = torch.zeros((n, m), dtype=torch.float32)
-        for j, r in enumerate(order):
-            seq[j, : len(out[r])] = torch.tensor(out[r], dtype=torch.long)
-            lp[j, : len(out[r])] = torch.from_numpy(np.asarray(lps[r], np.float32))
-        return SimpleNamespace(sequences=seq.to(self.device), logprobs=lp.to(self.device), scores=torch.from_numpy(scores[order].copy()),
+        seq, lp = self._padded([out[r] for r in order], [lps[r] for r in order], eos if pad_token_id is None else pad_token_id)
+        return SimpleNamespace(sequences=seq, logprobs=lp, scores=torch.from_numpy(scores[order].copy()),
                                order=[int(r) for r in order], heads=[int(new_heads[r]) for r in order])
 
     @torch.no_grad()
@@ -334,11 +303,8 @@ class TraceMistralForCausalLM:
         eng.host_mode(False)
         self._live_kv = None
         raw = images_or_videos[0]
-        x = raw
         modal = (modal_list or ["video"])[0]
-        if modal == "image":
-            nf = cfg.num_frames if hasattr(cfg, "num_frames") else NUM_FRAMES
-            x = x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
+        x = self._as_frames(raw, modal)
         prompt = ids[0].tolist()
         tail = None
         if self._prefix_cache and isinstance(raw, torch.Tensor):
@@ -366,28 +332,52 @@ class TraceMistralForCausalLM:
         lps, chains, sums = eng.score_continuations(0, P, tail, conts, hd)
         return scoring.ScoreResult(logprobs=lps, heads=chains, scores=sums, order=rank_samples(sums))
 
+    # ---- what generate(), generate_samples() and score() share ----
+    def _as_frames(self, x, modal):
+        """an image stands for num_frames copies of itself (trace_arch.py:221); a video is taken as it is"""
+        if modal != "image":
+            return x
+        nf = getattr(self.config, "num_frames", NUM_FRAMES)
+        return x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
+
+    def _eos(self, eos_token_id) -> int:
+        """the argument, else the config's; -1 = no eos"""
+        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
+        return -1 if eos is None else eos
+
+    def _padded(self, rows, lps, pad):
+        """(ids int64 [B, n] padded with `pad` (0 when it is None or negative), log-probabilities float32 [B, n] zero padded, or None), on the device"""
+        n = max(len(r) for r in rows)
+        res = torch.full((len(rows), n), pad if pad is not None and pad >= 0 else 0, dtype=torch.long)
+        lp = None if lps is None else torch.zeros((len(rows), n), dtype=torch.float32)
+        for b, row in enumerate(rows):
+            res[b, : len(row)] = torch.tensor(row, dtype=torch.long)
+            if lp is not None:
+                lp[b, : len(row)] = torch.from_numpy(np.asarray(lps[b], np.float32))
+        return res.to(self.device), None if lp is None else lp.to(self.device)
+
+    def _pick(self, name, value, generation_config, default=None):
+        """HF's precedence: explicit argument > generation_config > the model's defaults > `default`"""
+        if value is not None:
+            return value
+        for src in (generation_config, self.generation_config):
+            v = None if src is None else src.get(name) if isinstance(src, dict) else getattr(src, name, None)
+            if v is not None:
+                return v
+        return default
+
     # arguments of HF's generate() this build does not implement, with the value that means "off"
     _UNSUPPORTED = {"num_beams": 1, "num_return_sequences": 1, "typical_p": 1.0, "min_p": None, "repetition_penalty": 1.0}
 
     def _sampling_params(self, do_sample, temperature, top_k, top_p, generation_config, kwargs) -> Optional[SamplingParams]:
-        """HF's precedence: explicit argument > generation_config > the model's defaults.  None = greedy."""
-        srcs = [s for s in (generation_config, self.generation_config) if s is not None]
-
-        def pick(name, val):
-            if val is not None:
-                return val
-            for src in srcs:
-                v = src.get(name) if isinstance(src, dict) else getattr(src, name, None)
-                if v is not None:
-                    return v
-            return None
+        """HF's precedence (_pick).  None = greedy."""
+        gc = generation_config
         for name, off in self._UNSUPPORTED.items():
-            v = pick(name, kwargs.get(name))
+            v = self._pick(name, kwargs.get(name), gc)
             if v is not None and v != off:
                 raise NotImplementedError(f"{name}={v!r} is not implemented on the MI355X path (only {name}={off!r})")
-        do_sample, temperature = bool(pick("do_sample", do_sample)), float(pick("temperature", temperature))
-        top_k, top_p = pick("top_k", top_k), float(pick("top_p", top_p))
-        top_k = 0 if top_k is None else top_k
+        do_sample, temperature = bool(self._pick("do_sample", do_sample, gc)), float(self._pick("temperature", temperature, gc))
+        top_k, top_p = self._pick("top_k", top_k, gc, 0), float(self._pick("top_p", top_p, gc))
         check_sampling(temperature, top_k, top_p)
         if not do_sample or temperature <= 0:
             return None
@@ -395,81 +385,31 @@ class TraceMistralForCausalLM:
         return SamplingParams(temperature, int(top_k), top_p, (int(g[0]) << 32) | int(g[1]))
 
     def _logits_params(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, generation_config) -> Optional[LogitsParams]:
-        """repetition_penalty / no_repeat_ngram_size / min_new_tokens with HF's precedence: explicit argument > generation_config > the model's
-        defaults.  None = all three off (the decode step then is what it is without them).  ValueError outside HF's domains, and for an n-gram
-        size above 64 (the device's bound)."""
-        srcs = [s for s in (generation_config, self.generation_config) if s is not None]
-
-        def pick(name, val, off):
-            if val is not None:
-                return val
-            for src in srcs:
-                v = src.get(name) if isinstance(src, dict) else getattr(src, name, None)
-                if v is not None:
-                    return v
-            return off
-        lgp = LogitsParams(pick("repetition_penalty", repetition_penalty, 1.0), pick("no_repeat_ngram_size", no_repeat_ngram_size, 0),
-                           pick("min_new_tokens", min_new_tokens, 0))
+        """repetition_penalty / no_repeat_ngram_size / min_new_tokens with HF's precedence (_pick).  None = all three off (the decode step then
+        is what it is without them).  ValueError outside HF's domains, and for an n-gram size above 64 (the device's bound)."""
+        gc = generation_config
+        lgp = LogitsParams(self._pick("repetition_penalty", repetition_penalty, gc, 1.0), self._pick("no_repeat_ngram_size", no_repeat_ngram_size, gc, 0),
+                           self._pick("min_new_tokens", min_new_tokens, gc, 0))
         return None if lgp.off else lgp
 
-    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, prompt_ids, logprobs=False, lgp=None):
-        """Stopping-criteria path: one device step at a time with the masked logits brought back; ids from the device sampler
-        (trace_op_sample: the same draw a device decode step makes at that step and row) or the arg-max.  lgp (LogitsParams): the logits
-        processors through the loose-row op (trace_op_logits_process: the decode step's device code) on those rows, history = the recorded ids."""
-        eng = self.engine
-        B = len(vids)
+    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, logprobs=False, lgp=None):
+        """Stopping-criteria path: encode and prefill row by row, then TraceEngine.decode_stepwise with HF's StoppingCriteriaList as its callback.
+        A row stops when ANY criterion fires for it; generate(inputs_embeds=...) hands the criteria the generated ids only (the reference calls
+        super().generate with inputs_embeds, trace_mistral.py:301-312)."""
+        eng, B = self.engine, len(vids)
         for b in range(B):
             eng.encode_video(vids[b], timestamps[b])
             eng.prefill(b, eng.splice(id_lists[b]))
-        done = [False] * B
-        cur_heads = list(heads)
-        lp = np.zeros((B, max_new), np.float32)
-        eng.host_mode(True)
-        try:
-            lg = eng.decode_begin(list(range(B)), heads, max_new, eos=eos, want_logits=True)
-            rec = [[] for _ in range(B)]
-            cfg = self.config
-            for step in range(max_new):
-                sel = lg if lgp is None else eng.logits_process(lg, cur_heads, rec, lgp, [step] * B, eos)     # (lg stays raw: the log-probabilities' row)
-                if sampling is not None:
-                    tok = eng.sample(sel, cur_heads, sampling, [step] * B)
-                elif lgp is None:
-                    tok = torch.argmax(lg, dim=-1).tolist()
-                else:                           # the device's rule: the lowest id among equal maxima of the head's range (all banned: its first id)
-                    rows = sel.cpu().numpy()
-                    tok = [lo + int(np.argmax(rows[b, lo:hi])) for b, (lo, hi) in
-                           enumerate(head_bounds(h, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size) for h in cur_heads)]
-                val = eng.token_logprob(lg, cur_heads, tok) if logprobs else None      # the loose-row op on the logits this path brings back anyway
-                eng.feed(tok)
-                if sampling is not None or logprobs or lgp is not None:
-                    rec, cur_heads = eng.decode_read()
-                if logprobs:
-                    for b in range(B):
-                        if len(rec[b]) == step + 1:
-                            lp[b, step] = val[b]
-                for b in range(B):
-                    done[b] = done[b] or (eos >= 0 and tok[b] == eos)
-                if all(done) or step == max_new - 1:
-                    break
-                if stopping:
-                    # HF StoppingCriteriaList: a row stops when ANY criterion fires for it; generate(inputs_embeds=...) hands the
-                    # criteria the generated ids only (the reference calls super().generate with inputs_embeds, trace_mistral.py:301-312)
-                    cur, _ = eng.decode_read()
-                    n = max(len(x) for x in cur)
-                    gen = torch.tensor([x + [0] * (n - len(x)) for x in cur], dtype=torch.long)
-                    fired = torch.zeros(B, dtype=torch.bool)
-                    for sc in stopping:
-                        r = sc(gen, None)
-                        fired |= (r.view(-1).bool().cpu() if isinstance(r, torch.Tensor) else torch.full((B,), bool(r)))
-                    for b in range(B):
-                        done[b] = done[b] or bool(fired[b])
-                    if all(done):
-                        break
-                lg = eng.decode_steps(1, use_graph=False, want_logits=True)
-            out, hd = eng.decode_read()
-            return (out, hd, [lp[b, : len(x)].copy() for b, x in enumerate(out)]) if logprobs else (out, hd)
-        finally:
-            eng.host_mode(False)
+
+        def fired(rows):
+            n = max(len(x) for x in rows)
+            gen = torch.tensor([x + [0] * (n - len(x)) for x in rows], dtype=torch.long)
+            out = torch.zeros(B, dtype=torch.bool)
+            for sc in stopping:
+                r = sc(gen, None)
+                out |= (r.view(-1).bool().cpu() if isinstance(r, torch.Tensor) else torch.full((B,), bool(r)))
+            return out.tolist()
+        return eng.decode_stepwise(range(B), heads, max_new, eos, sampling=sampling, logprobs=logprobs, logits=lgp, stopping=fired)
 
     # ---- forward (trace_mistral.py:114-264) ----
     @torch.no_grad()
@@ -518,10 +458,7 @@ class TraceMistralForCausalLM:
             raise ValueError(f"batch {B} exceeds the engine's max_batch {eng.max_batch}")
         rows = []
         for b in range(B):
-            x = vids[b]
-            if (modals[b] if modals else "video") == "image":
-                nf = cfg.num_frames if hasattr(cfg, "num_frames") else NUM_FRAMES
-                x = x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
+            x = self._as_frames(vids[b], modals[b] if modals else "video")
             eng.encode_video(x, video_timestamps[b])
             trow = [int(i) for ev in (times[b] if times is not None else []) for i in self.model.time_tower.encode(ev)]
             srow = [int(i) for ev in (scores[b] if scores is not None else []) for i in self.model.score_tower.encode(ev)]

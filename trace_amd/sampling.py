@@ -332,6 +332,20 @@ def head_bounds(head: int, V: int, Tv: int, Sv: int):
     return ((0, V + 1), (V + 1, V + 1 + Tv), (V + 1 + Tv, V + 1 + Tv + Sv))[int(head)]
 
 
+def argmax_rows(logits, heads, V, Tv, Sv):
+    """The greedy pick of a host-driven step: per row of masked logits [B, NV] (a torch tensor, taken where it lives, or numpy) the lowest id
+    among equal maxima of the head's range - the device's rule (select_next_kernel); a range that is -inf throughout gives its first id.
+    Only the B ids come back to the host."""
+    import torch
+    lg = logits.detach().float() if hasattr(logits, "detach") else torch.from_numpy(np.asarray(logits, np.float32))
+    NV = lg.shape[1]
+    lo, hi = (torch.tensor(x, device=lg.device).unsqueeze(1) for x in zip(*(head_bounds(h, V, Tv, Sv) for h in heads)))
+    col = torch.arange(NV, device=lg.device).unsqueeze(0)
+    inside = (col >= lo) & (col < hi)
+    best = torch.where(inside, lg, torch.full_like(lg, -np.inf)).max(dim=1, keepdim=True).values
+    return torch.where(inside & (lg == best), col, torch.full_like(col, NV)).min(dim=1).values.tolist()
+
+
 def sample_rows_host(logits, heads, V, Tv, Sv, params: SamplingParams, steps):
     """The host path (parameters outside the device sampler's domain): one id per row of masked logits [B, NV] (numpy or a torch tensor)
     under the same rules and the same RNG contract as the device."""
