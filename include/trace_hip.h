@@ -149,6 +149,13 @@ int trace_llm_prefill_append(trace_ctx* ctx, int slot0, int n, int past, const v
  * positions more: finite values that a later append overwrites and the attention masks).  rows == the source's length: the copies can be decoded from as
  * the source can.  TRACE_ERR_STATE: rows above the source's length; TRACE_ERR_ARG: a slot out of range, src_slot among the destinations. */
 int trace_kv_copy(trace_ctx* ctx, int src_slot, const int32_t* dst_slots, int n, int rows, void* stream);
+/* A batch whose prompts all begin with the same `past` rows (the ids before <video>, one question for every video): prefill those rows ONCE into one
+ * slot (trace_llm_prefill), then call this for every run of n <= 8 equal-length prompts: rows [0, past) of src_slot are copied to the run's slots
+ * (trace_kv_copy's launches; src_slot may be one of them and may by then hold more rows) and the n prompts continue with their own L rows each
+ * (trace_llm_prefill_append(past)'s body, no hidden_out) — one call per run.  By the promise above the slots end up with the bits n whole prefills would
+ * have left.  TRACE_ERR_STATE: an e4m3 KV cache or fp8 weights (a continuation is not bit-identical there), past above the source's length; otherwise
+ * trace_llm_prefill_append's argument rules, all checked before the first launch. */
+int trace_llm_prefill_shared(trace_ctx* ctx, int src_slot, int slot0, int n, int past, const void* const* embeds, int L, void* stream);
 /* trace_splice_embeds for rows that hold no <video> (the part of a prompt after the placeholder, trace/model/trace_arch.py:410-427 for those rows):
  * token / <sync> / <time> / <score> ids -> [n_ids, hidden] (internal buffer; embeds_out may be NULL).  A video placeholder among the ids is
  * TRACE_ERR_ARG; trace_splice_embeds itself keeps its "only have one video" rule. */
@@ -246,6 +253,14 @@ int trace_decode_set_sampling(trace_ctx* ctx, float temperature, int top_k, floa
  * trace_decode_read_logprobs: synchronises and copies [B, max_new] floats to a HOST buffer; TRACE_ERR_STATE if the current batch was begun
  * without log-probabilities. */
 int trace_decode_set_logprobs(trace_ctx* ctx, int on);
+/* Shared prompt prefix of a decode batch: every slot the NEXT trace_decode_begin is given holds the same K / V rows at positions [0, rows) (a batch
+ * prefilled through trace_llm_prefill_shared, or copies made by trace_kv_copy), and `slot` is one that holds them.  The decode attention then reads
+ * those positions of every sequence from that one slot — one copy that stays in cache instead of B from memory; ids, heads and log-probabilities are
+ * bit-identical to the unshared batch.  Whole 32-position blocks only: rows is floored to a multiple of 32; rows < 32 or slot < 0 = off.  The
+ * request is consumed by the next trace_decode_begin (which answers TRACE_ERR_ARG if a sequence is shorter than the shared rows, TRACE_ERR_STATE if
+ * the slot is); a begin with no request before it decodes unshared.  A batch of one never shares.  Steps captured for another (slot, rows) pair are
+ * cached apart (two pairs per batch size).  TRACE_ERR_ARG: slot / rows out of range; TRACE_ERR_STATE: an e4m3 KV cache. */
+int trace_decode_set_shared_prefix(trace_ctx* ctx, int slot, int rows);
 int trace_decode_read_logprobs(trace_ctx* ctx, float* out, void* stream);
 
 /* Logits processors (generate(repetition_penalty=, no_repeat_ngram_size=, min_new_tokens=): HF RepetitionPenaltyLogitsProcessor ->
@@ -399,6 +414,11 @@ int trace_op_logits_process(const float* logits, int ld, int B, const int32_t* h
  * above. */
 int trace_op_attn_decode(const void* q, const void* kcache, const void* vtcache, const int32_t* pos, void* O, float* ws,
                          int B, int nq, int nkv, int max_ctx, int nsplit, float scale, void* stream);
+/* The same over caches of num_slots >= B slots (row b in slot b), with positions [0, shared_rows) of EVERY row read from slot shared_slot instead
+ * of the row's own (trace_decode_set_shared_prefix; shared_rows floored to a multiple of 32, 0 = trace_op_attn_decode).  TRACE_ERR_ARG before any
+ * launch, beyond the above: shared_slot outside [0, num_slots), a position outside [0, max_ctx) or below shared_rows. */
+int trace_op_attn_decode_shared(const void* q, const void* kcache, const void* vtcache, const int32_t* pos, void* O, float* ws, int B, int nq,
+                                int nkv, int num_slots, int max_ctx, int nsplit, float scale, int shared_slot, int shared_rows, void* stream);
 /* The decode step's qkv epilogue as a kernel of its own (the wide step's form): part = the qkv GEMV's fp32 k-chunk partial rows
  * [ks][trace_op_sk_rows()][(nq + 2 nkv) * 128] (q heads | k heads | v heads), summed in chunk order and rounded to the element type; rotate-half RoPE of
  * q and the new k from the caller's tables cos_t / sin_t [max_ctx][64] fp32 at row pos[b]; q_out [B][(nq + 2 nkv) * 128] receives the roped q heads in

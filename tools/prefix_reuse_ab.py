@@ -8,7 +8,12 @@ rows, 25 after), one process, warmed, arms alternated:
   copy       device ms of trace_kv_copy of 1942 rows to 1, 2 and 7 slots and the achieved bytes/s (one read + n writes of the rows' K and V^T
              bytes) against the 8 TB/s HBM3E spec
 
+  batch      (--batch-shared B, a run of its own) B different videos with ONE prompt through generate(), the batch's 150 rows before <video>
+             prefilled once and read from one slot by the decode attention (share_prefix_min_batch = 2) against every video on its own (off), in one
+             process with interleaved rounds: wall ms per call, the prefill stage's device ms, rows prefilled, ids identical
+
   python tools/prefix_reuse_ab.py [--rounds 5] [--new 8 128] [--only questions append copy]
+  python tools/prefix_reuse_ab.py --batch-shared 32 [--rounds 3] [--new 64]
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/prefix_reuse_ab.py --only append --append-reps 20
   python tools/prefix_reuse_ab.py --summarize DIR      # kernel time of the traced run by (kernel, grid): the append's attention launches are the
                                                        # 8-workgroup ones (grid 2048), the prefix prefill's the large ones
@@ -28,6 +33,7 @@ ap.add_argument("--only", nargs="+", default=["questions", "append", "copy"])
 ap.add_argument("--append-reps", type=int, default=10)
 ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--summarize", default=None)
+ap.add_argument("--batch-shared", type=int, default=0, metavar="B", help="the batch arm alone: B videos, one prompt, sharing on against off")
 a = ap.parse_args()
 
 
@@ -68,6 +74,50 @@ if not torch.cuda.is_available():
 cfg = tcfg.trace_7b(128)
 if a.layers != cfg.num_hidden_layers:
     cfg = dataclasses.replace(cfg, num_hidden_layers=a.layers)
+
+
+def batch_shared(B):
+    L, n_new = 1967, a.new[0]
+    eng = TraceEngine(cfg, max_batch=B, max_ctx=(L + n_new + 63) // 64 * 64, max_frames=128, max_new_tokens=n_new)
+    eng.load_weights(synth.iter_weights(cfg, device="cuda:0"))
+    vids = [synth.synth_frames(cfg, b, num_frames=128, device="cuda").to(torch.bfloat16) for b in range(B)]
+    ts = [[[i * 2.0] for i in range(128)]] * B
+    ids = [synth.synth_prompt_ids(cfg, n_text=176, video_pos=150).tolist()] * B
+    res = {arm: {"wall": [], "prefill": [], "rows": []} for arm in ("off", "on")}
+    first = None
+    for rnd in range(a.rounds + 1):                          # round 0 warms both arms (graphs of both (slot, rows) pairs) and is dropped
+        for arm in ("off", "on"):
+            eng.share_prefix_min_batch = 2 if arm == "on" else B + 1
+            eng.stage_timing(True)
+            rows0 = eng.stats["prefill_rows"]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = eng.generate(vids, ts, ids, [1] * B, n_new)
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - t0) * 1e3
+            st = eng.stage_times()
+            eng.stage_timing(False)
+            first = first or out
+            assert out == first, "ids / heads differ between the arms or rounds"
+            if rnd:
+                res[arm]["wall"].append(wall); res[arm]["prefill"].append(st["prefill_ms"]); res[arm]["rows"].append(eng.stats["prefill_rows"] - rows0)
+    print(f"synthetic TRACE-7B, {cfg.num_hidden_layers} layers, {B} videos x 128 frames, one prompt (150 rows before <video>, L = {L}), {n_new} new tokens; "
+          f"{a.rounds} interleaved rounds after a warm-up round; median [min .. max]; ids and heads identical in both arms and every round: True")
+    for arm, r in res.items():
+        print(f"   sharing {arm:3s}: generate() wall ms {fmt(r['wall'])}   prefill stage device ms {fmt(r['prefill'])}   rows prefilled {r['rows'][0]}")
+    m = lambda k: statistics.median(res["on"][k]) / statistics.median(res["off"][k])
+    print(f"   on / off: wall {m('wall'):.4f}   prefill stage {m('prefill'):.4f}")
+    eng.close()
+
+
+def fmt(v):
+    return f"{statistics.median(v):9.2f} [{min(v):8.2f} .. {max(v):8.2f}]"
+
+
+if a.batch_shared:
+    batch_shared(a.batch_shared)
+    sys.exit(0)
+
 L, P = 1967, 1942
 max_new = max(a.new)
 eng = TraceEngine(cfg, max_batch=8, max_ctx=(L + max_new + 63) // 64 * 64, max_frames=128, max_new_tokens=max_new)
@@ -85,10 +135,6 @@ for q in range(3):
 assert cut + 1792 - 1 == P and len(base) - cut == L - P
 print(f"synthetic TRACE-7B, {cfg.num_hidden_layers} layers, 128 frames, L = {L} = {P} rows through <video> + {L - P}; {a.rounds} alternated rounds; "
       f"median [min .. max]")
-
-
-def fmt(v):
-    return f"{statistics.median(v):9.2f} [{min(v):8.2f} .. {max(v):8.2f}]"
 
 
 def timed(fn):

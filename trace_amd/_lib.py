@@ -57,6 +57,7 @@ SIGNATURES = {
     "trace_llm_prefill_multi": (I, [P, I, C.POINTER(P), I, I, P]),
     "trace_llm_prefill_append": (I, [P, I, I, I, C.POINTER(P), I, P, P]),
     "trace_kv_copy": (I, [P, I, P, I, I, P]),
+    "trace_llm_prefill_shared": (I, [P, I, I, I, I, C.POINTER(P), I, P]),
     "trace_embed_rows": (I, [P, P, I, P, I, P, I, P, P]),
     "trace_llm_head_logits": (I, [P, P, I, I, P, P]),
     "trace_op_score_tile": (I, []),
@@ -64,6 +65,7 @@ SIGNATURES = {
     "trace_op_score_rows": (I, [P, I, P, I, I, I, P, P, I, I, I, P, P, P]),
     "trace_llm_score_rows": (I, [P, P, I, P, P, P, P]),
     "trace_llm_score_append": (I, [P, I, I, I, C.POINTER(P), I, P, P, P, P]),
+    "trace_decode_set_shared_prefix": (I, [P, I, I]),
     "trace_decode_begin": (I, [P, P, I, P, I, I, P, P, P]),
     "trace_decode_steps": (I, [P, I, I, P, P]),
     "trace_decode_read": (I, [P, P, P, P, P]),
@@ -112,6 +114,7 @@ SIGNATURES = {
     "trace_op_token_logprob": (I, [P, I, I, P, I, I, I, P, P, P]),
     "trace_op_logits_process": (I, [P, I, I, P, I, I, I, P, I, P, P, I, F, I, I, P, P]),
     "trace_op_attn_decode": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
+    "trace_op_attn_decode_shared": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, I, I, P]),
     "trace_op_qkv_finish": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "trace_op_attn_decode_fused": (I, [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P]),
     "trace_op_attn_decode_kv8": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, P]),

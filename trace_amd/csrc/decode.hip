@@ -524,7 +524,8 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_decode_kernel(const bf16_t* _
                                                              unsigned int* __restrict__ tickets, bf16_t* __restrict__ O, int ldo,
                                                              int nq, int nkv, int nsplit, float scale, int fuse_rope,
                                                              const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                                             const float* __restrict__ qpart, int qks, int dbg) {
+                                                             const float* __restrict__ qpart, int qks, int dbg, int shared_slot,
+                                                             int shared_rows) {
     constexpr int HD = 128, GQ = 4;
     __shared__ __attribute__((aligned(16))) float s_acc[NW][GQ][HD];
     __shared__ float s_m[NW][GQ], s_l[NW][GQ];
@@ -542,6 +543,10 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_decode_kernel(const bf16_t* _
     const int nit = (len + 31) >> 5;                  // 32-position blocks in this split
     bf16_t* kb = kcache + (size_t)slots[b] * slot_stride + (size_t)kvh * kv_head_stride;
     bf16_t* vb = vtcache + (size_t)slots[b] * slot_stride + (size_t)kvh * kv_head_stride;
+    // Shared prompt prefix (shared_rows > 0, a multiple of 32): positions below shared_rows hold the same K / V^T rows in every sequence's slot, so their
+    // 32-position blocks are read from slot `shared_slot` by all sequences — one copy that stays in L2 instead of B private ones from HBM.  Nothing is
+    // ever written below shared_rows (the newest position lies at or above it).  sh_off: elements from this sequence's slot to the shared one.
+    const long sh_off = shared_rows > 0 ? ((long)shared_slot - slots[b]) * slot_stride : 0;
     // the qkv row of this sequence: bf16 [ldq], or (qpart) the qkv GEMV's fp32 k-chunk partial rows [qks][SK_ROWS][ldq], summed
     // and rounded to bf16 here (what the GEMV epilogue would have stored)
     const bf16_t* row = qkv + (size_t)b * ldq;
@@ -583,20 +588,21 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_decode_kernel(const bf16_t* _
     // per-lane predicates the loads sat in exec-masked branches, the number in flight was unknown at the joins, and hipcc put s_waitcnt vmcnt(0) in front of the
     // QK MFMAs: every wave waited for the V^T block it had requested a moment earlier instead of computing S under it (ISA read, round 6; measured against the
     // predicated form in profiles/r06_decode_attn_waits_ab.txt: equal at batch 128, where 12 waves per CU cover the latency anyway, -1.4 % per step at batch 16).
-    auto load_k = [&](int it) {
+    // (a block's base: the select is uniform over the block and scalar, the per-lane part of the address is what it was)
+    auto load_k_tile = [&](int it, int t) {
         const int P0 = beg + it * 32;
+        const bf16_t* kbase = kb + (__builtin_amdgcn_readfirstlane(P0) < shared_rows ? sh_off : 0);
+        const int p = P0 + prow + 4 * t;
+        const bf16_t* src = kbase + (size_t)p * HD + g * 16;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int p = P0 + prow + 4 * t;
-            const bf16_t* src = kb + (size_t)p * HD + g * 16;
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) kr[t][s4] = ldc(src + (s4 >> 1) * 64 + (s4 & 1) * 8);
-        }
+        for (int s4 = 0; s4 < 4; ++s4) kr[t][s4] = ldc(src + (s4 >> 1) * 64 + (s4 & 1) * 8);
     };
+    auto load_k = [&](int it) { load_k_tile(it, 0); load_k_tile(it, 1); };
     auto load_v = [&](int it) {
         const int P0 = beg + it * 32;
+        const bf16_t* vbase = vb + (__builtin_amdgcn_readfirstlane(P0) < shared_rows ? sh_off : 0);
         // (dbg == 8, timing only: the same 8 KB read as ONE contiguous block [128 d][32 positions] — what a position-blocked V^T cache would give)
-        const bf16_t* vsrc = dbg == 8 ? vb + ((size_t)(P0 >> 5) * HD + i) * 32 + g * 8 : vb + (size_t)i * ctx_stride + P0 + g * 8;
+        const bf16_t* vsrc = dbg == 8 ? vbase + ((size_t)(P0 >> 5) * HD + i) * 32 + g * 8 : vbase + (size_t)i * ctx_stride + P0 + g * 8;
         const size_t vstep = dbg == 8 ? 16 * 32 : (size_t)16 * ctx_stride;
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) vr[dt] = ldc(vsrc + dt * vstep);
@@ -702,7 +708,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_decode_kernel(const bf16_t* _
                 S[t] = mfma16(__builtin_bit_cast(bf16x8_t, kr[t][s4]),
                                                                __builtin_bit_cast(bf16x8_t, qf[s4]), S[t]);
         }
-        if constexpr (decltype(prefetch)::value) load_k(it + NW);
+        if constexpr (decltype(prefetch)::value) { load_k_tile(it + NW, 0); __builtin_amdgcn_sched_barrier(0); }
         // lane (head i, group g): S[t][r] is the score of position P0 + g*8 + t*4 + r
         float sv[8];
         float mx = -1e30f;
@@ -737,6 +743,11 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_decode_kernel(const bf16_t* _
             acc[dt] *= a;
             acc[dt] = mfma16(__builtin_bit_cast(bf16x8_t, vr[dt]),
                                                               __builtin_bit_cast(bf16x8_t, pf), acc[dt]);
+            if constexpr (decltype(prefetch)::value) {
+                // the second K tile's registers carry the softmax temporaries until here: its request sits between the PV products' halves, where the
+                // scheduler has always put it — pinned, so that every wait below stays a count of at least the 8 pieces just requested
+                if (dt == 3) { load_k_tile(it + NW, 1); __builtin_amdgcn_sched_barrier(0); }
+            }
         }
         if constexpr (decltype(prefetch)::value) load_v(it + NW);
     };
@@ -1140,13 +1151,15 @@ int launch_qkv_finish(const float* part, int ks, int ldq, bf16_t* qout, bf16_t* 
 int launch_attn_decode(const bf16_t* qkv, int ldq, bf16_t* kcache, bf16_t* vtcache, long slot_stride, long kv_head_stride,
                        int ctx_stride, const int32_t* slots, const int32_t* pos, bf16_t* O, int ldo, float* ws, unsigned int* tickets, int B,
                        int nq, int nkv, int hd, int nsplit, float scale, int fuse_rope, const float* cos_t, const float* sin_t,
-                       const float* qpart, int qks, hipStream_t s) {
+                       const float* qpart, int qks, hipStream_t s, int shared_slot, int shared_rows) {
     if (hd != 128 || nq != 4 * nkv || nsplit < 1 || B < 1 || !tickets || ctx_stride % 32) return TRACE_ERR_ARG;
+    if (shared_rows < 0 || shared_rows % 32 || shared_rows > ctx_stride || (shared_rows > 0 && (shared_slot < 0 || slot_stride % hd))) return TRACE_ERR_ARG;
     const int w = g_tune.attn_decode_waves, nw = w == 1 ? 3 : w == 3 ? 6 : w == 4 ? 8 : 4;
     const size_t pad = (size_t)g_tune.attn_decode_lds_pad_kb * 1024;       // A/B: dynamic LDS nobody uses, caps the workgroups per CU
 #define ATTN_DEC(NW_, NT_) do { static LdsGrantSized grant_; if (pad && !grant_dynamic_lds(grant_, reinterpret_cast<const void*>(attn_decode_kernel<NW_, NT_>), pad)) return TRACE_ERR_HIP; \
     hipLaunchKernelGGL((attn_decode_kernel<NW_, NT_>), dim3(nsplit, nkv, B), dim3(NW_ * 64), pad, s, qkv, ldq, kcache, vtcache, slot_stride, \
-                       kv_head_stride, ctx_stride, slots, pos, ws, tickets, O, ldo, nq, nkv, nsplit, scale, fuse_rope, cos_t, sin_t, qpart, qks, g_tune.attn_decode_debug); } while (0)
+                       kv_head_stride, ctx_stride, slots, pos, ws, tickets, O, ldo, nq, nkv, nsplit, scale, fuse_rope, cos_t, sin_t, qpart, qks, g_tune.attn_decode_debug, \
+                       shared_slot, shared_rows); } while (0)
     if (nw == 3) { if (g_tune.attn_decode_nt) ATTN_DEC(3, true); else ATTN_DEC(3, false); }
     else if (nw == 6) ATTN_DEC(6, false);
     else if (nw == 8) ATTN_DEC(8, false);

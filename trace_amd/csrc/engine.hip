@@ -129,7 +129,13 @@ struct trace_ctx {
     // trace_decode_begin (= want, or all-off in host-select mode, where the host holds the logits and does all three itself).  A step of each
     // mode is a graph of its own, graphs[armed.index()][B]: toggling a setting between batches never replays another form, and index 0 is the plain step.
     TailMode want, armed;
-    hipGraphExec_t graphs[8][SK_ROWS + 1] = {{nullptr}};
+    // Shared prompt prefix of the batch being decoded (trace_decode_set_shared_prefix): the decode attention reads positions below sh_rows (a multiple of
+    // 32, 0 = off) of every sequence from slot sh_slot.  sh_want_* is the request the next trace_decode_begin consumes.  Both are launch arguments of the
+    // attention, so a captured step is good for one (slot, rows) pair: a graph entry has two ways keyed by it (the two banks of a pipelined caller).
+    int sh_want_slot = -1, sh_want_rows = 0, sh_slot = -1, sh_rows = 0;
+    struct StepGraph { hipGraphExec_t exec = nullptr; int sh_slot = -1, sh_rows = 0; };
+    StepGraph graphs[8][SK_ROWS + 1][2];
+    int graph_evict = 0;               // the way the next miss of a full entry replaces
     // sampling (trace_decode_set_sampling): host copy of the params; the device copy d_sparams, written at trace_decode_begin, is what the selection
     // kernel reads (a captured graph stays valid across calls).  d_slog: the [SK_ROWS][NV] raw masked logits of a step with anything armed.
     SampleParams samp{};
@@ -485,7 +491,7 @@ extern "C" int trace_ctx_destroy(trace_ctx* c) {
     (void)hipSetDevice(c->dev);       // the calling thread's current device may be another GPU: everything below (and the counters' key) is this context's
     hipDeviceSynchronize();
     for (auto& st : c->streams) { gemm_pers_forget(st); hipStreamDestroy(st); }
-    for (auto& row : c->graphs) for (auto& g : row) if (g) hipGraphExecDestroy(g);
+    for (auto& row : c->graphs) for (auto& e : row) for (auto& g : e) if (g.exec) hipGraphExecDestroy(g.exec);
     for (auto& e : c->kev) if (e) hipEventDestroy(e);
     for (auto& e : c->vev) if (e) hipEventDestroy(e);
     if (c->mev0) hipEventDestroy(c->mev0);
@@ -1243,7 +1249,8 @@ extern "C" int trace_llm_prefill_multi(trace_ctx* c, int slot0, const void* cons
 // Continue n slots that hold at least `past` rows each (a prompt prefix prefilled or copied there earlier) with L new rows per slot: what
 // trace_llm_prefill_multi is for whole prompts.  Everything is checked before the first launch.
 // the argument rules of an append, for trace_llm_prefill_append and trace_llm_score_append alike (the latter has no hidden_out and passes NULL)
-static int append_check(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, const void* hidden_out) {
+// (have >= 0: the rows every slot WILL hold when the append runs, for a caller that fills them first)
+static int append_check(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, const void* hidden_out, int have = -1) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
     if (n < 1 || n > PF_MAX_N || slot0 < 0 || slot0 + n > c->max_B) return fail(TRACE_ERR_ARG, "bad slot / n");
     if (L < 1 || past < 0) return fail(TRACE_ERR_ARG, "bad L / past");
@@ -1253,7 +1260,7 @@ static int append_check(trace_ctx* c, int slot0, int n, int past, const void* co
     if (hidden_out && n != 1) return fail(TRACE_ERR_ARG, "hidden_out with n == 1 only");
     for (int i = 0; i < n; ++i) {
         if (embeds && !embeds[i]) return fail(TRACE_ERR_ARG, "null embeds");
-        if (past > c->slot_len[slot0 + i]) return fail(TRACE_ERR_STATE, "past exceeds the rows the slot holds");
+        if (past > (have >= 0 ? have : c->slot_len[slot0 + i])) return fail(TRACE_ERR_STATE, "past exceeds the rows the slot holds");
     }
     return TRACE_OK;
 }
@@ -1297,6 +1304,25 @@ extern "C" int trace_kv_copy(trace_ctx* c, int src_slot, const int32_t* dst_slot
         c->slot_len[dst_slots[i]] = rows;
     }
     return TRACE_OK;
+}
+
+// A run of a batch that shares its first `past` prompt rows: slot src_slot holds them (prefilled once for the batch); they are copied to the run's other
+// slots (trace_kv_copy's launches) and the n prompts continue with their own L rows (trace_llm_prefill_append's body) — one call per run, everything checked
+// before the first launch.  src_slot may be one of the run's slots (it is, in the batch's first run) and may hold more than `past` rows (in the later ones).
+extern "C" int trace_llm_prefill_shared(trace_ctx* c, int src_slot, int slot0, int n, int past, const void* const* embeds, int L, void* stream) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (c->kv8 || c->fp8) return fail(TRACE_ERR_STATE, "a shared prefix needs the 16-bit KV cache and 16-bit weights (a continuation is bit-identical there only)");
+    if (src_slot < 0 || src_slot >= c->max_B || past < 1) return fail(TRACE_ERR_ARG, "bad source slot / past");
+    if (past > c->slot_len[src_slot]) return fail(TRACE_ERR_STATE, "past exceeds the rows the source slot holds");
+    if (!embeds) return fail(TRACE_ERR_ARG, "null embeds");
+    TRY(append_check(c, slot0, n, past, embeds, L, nullptr, past));
+    int32_t dst[PF_MAX_N];
+    int m = 0;
+    for (int i = 0; i < n; ++i) if (slot0 + i != src_slot) dst[m++] = slot0 + i;
+    if (m) TRY(trace_kv_copy(c, src_slot, dst, m, past, stream));
+    hipStream_t s = (hipStream_t)stream;
+    TRY(append_stage_embeds(c, n, embeds, L, s));
+    return prefill_impl(c, slot0, n, L, nullptr, s, past);
 }
 
 // masked logits of R final-norm hidden rows under ONE head: what forward() returns for every position of a sequence
@@ -1401,7 +1427,7 @@ static int attn_decode_layer(trace_ctx* c, int l, const DecodeRoute& r, const fl
     return launch_attn_decode(c->dQKV, c->QKV, c->kcache + (size_t)l * c->layer_stride, c->vcache + (size_t)l * c->layer_stride, (long)c->slot_stride,
                               (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->dO, c->H, c->attn_ws, c->tickets, c->B, c->NQ, c->NKV, c->HD,
                               r.nsplit, 1.0f / sqrtf((float)c->HD), fused ? 1 : 0, fused ? c->rope_cos : nullptr, fused ? c->rope_sin : nullptr,
-                              fused ? part : nullptr, fused ? r.ks_q : 0, s);
+                              fused ? part : nullptr, fused ? r.ks_q : 0, s, c->sh_slot, c->sh_rows);
 }
 // that prologue as a launch of its own: the qkv partial rows in sk_ws -> roped q rows in dQKV, k / v of layer l appended
 static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s, const float* part = nullptr) {
@@ -1534,15 +1560,33 @@ static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
     return r.step == 3 ? decode_step_wide(c, r, logits_out, s) : r.step == 2 ? decode_step_fused(c, r, logits_out, s) : decode_step_skinny(c, r, logits_out, s);
 }
 
+// The batch the NEXT trace_decode_begin starts holds the same K / V rows at positions below `rows` in every slot, and `slot` is one that holds them: the
+// decode attention then reads those positions from that slot alone (whole 32-position blocks: rows is floored to a multiple of 32; below 32, or
+// slot < 0, = off).  Consumed by that begin; a begin without a request before it decodes unshared.
+extern "C" int trace_decode_set_shared_prefix(trace_ctx* c, int slot, int rows) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    c->sh_want_slot = -1; c->sh_want_rows = 0;
+    if (slot < 0 || rows < 32) return TRACE_OK;
+    if (slot >= c->max_B || rows > c->max_ctx) return fail(TRACE_ERR_ARG, "shared slot / rows out of range");
+    if (c->kv8) return fail(TRACE_ERR_STATE, "the shared prefix needs the 16-bit KV cache");
+    c->sh_want_slot = slot; c->sh_want_rows = rows & ~31;
+    return TRACE_OK;
+}
+
 extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, const int32_t* heads, int max_new, int eos,
                                   const int32_t* forced, float* logits_out, void* stream) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
     if (!slots || !heads || B < 1 || B > c->max_B || B > (c->fp8 ? SKINNY_ROWS : SK_ROWS)) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(c->fp8 ? SKINNY_ROWS : SK_ROWS) + " sequences decode together)");
     if (max_new < 1 || max_new > c->c.max_new_tokens) return fail(TRACE_ERR_ARG, "max_new exceeds capacity");
     hipStream_t s = (hipStream_t)stream;
+    // the shared-prefix request is this call's alone: taken here, whatever the call then answers (one sequence shares with nobody)
+    const int sh_slot = c->sh_want_slot, sh_rows = B > 1 ? c->sh_want_rows : 0;
+    c->sh_want_slot = -1; c->sh_want_rows = 0;
+    if (sh_rows > 0 && c->slot_len[sh_slot] < sh_rows) return fail(TRACE_ERR_STATE, "the shared slot holds fewer rows than the shared prefix");
     int32_t pos[SK_ROWS], zero[SK_ROWS] = {0};
     for (int b = 0; b < B; ++b) {
         if (slots[b] < 0 || slots[b] >= c->max_B || c->slot_len[slots[b]] <= 0) return fail(TRACE_ERR_STATE, "slot not prefilled");
+        if (c->slot_len[slots[b]] < sh_rows) return fail(TRACE_ERR_ARG, "a sequence is shorter than the shared prefix");
         if (heads[b] < 0 || heads[b] > 2) return fail(TRACE_ERR_ARG, "head must be 0, 1 or 2");
         pos[b] = c->slot_len[slots[b]];
         if (pos[b] + max_new > c->max_ctx) return fail(TRACE_ERR_ARG, "prefill + max_new_tokens exceeds max_ctx");
@@ -1551,6 +1595,7 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     if (forced && c->want.process && !c->host_mode)
         return fail(TRACE_ERR_ARG, "logits processors (trace_decode_set_logits_params) with forced ids: the history is the recorded ids, not the fed ones");
     c->B = B; c->max_new = max_new; c->eos = eos; c->has_forced = forced != nullptr;
+    c->sh_slot = sh_rows > 0 ? sh_slot : -1; c->sh_rows = sh_rows;
     c->pos_sum = 0;
     for (int b = 0; b < B; ++b) c->pos_sum += pos[b];
     HIPCHK(hipMemcpyAsync(c->d_slots, slots, B * 4, hipMemcpyHostToDevice, s));
@@ -1593,7 +1638,16 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
     if (!use_graph) {
         for (int i = 0; i < n; ++i) { c->step_in_call = steps_before + i; TRY(decode_step(c, logits_out, s)); }
     } else {
-        hipGraphExec_t* slot_g = &c->graphs[c->armed.index()][c->B];
+        trace_ctx::StepGraph* ways = c->graphs[c->armed.index()][c->B];
+        trace_ctx::StepGraph* way = nullptr;
+        for (int w = 0; w < 2 && !way; ++w)
+            if (ways[w].exec && ways[w].sh_slot == c->sh_slot && ways[w].sh_rows == c->sh_rows) way = &ways[w];
+        if (!way) {
+            way = !ways[0].exec ? &ways[0] : !ways[1].exec ? &ways[1] : &ways[c->graph_evict ^= 1];
+            if (way->exec) { HIPCHK(hipStreamSynchronize(s)); hipGraphExecDestroy(way->exec); way->exec = nullptr; }
+            way->sh_slot = c->sh_slot; way->sh_rows = c->sh_rows;
+        }
+        hipGraphExec_t* slot_g = &way->exec;
         if (!*slot_g) {
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamSynchronize(s));
@@ -2099,6 +2153,29 @@ extern "C" int trace_op_attn_decode(const void* q, const void* kcache, const voi
     LCHK(launch_attn_decode((const bf16_t*)q, nq * 128, (bf16_t*)kcache, (bf16_t*)vcache, (long)nkv * max_ctx * 128,
                             (long)max_ctx * 128, max_ctx, g_op_slots, pos, (bf16_t*)O, nq * 128, ws, g_op_tickets, B, nq, nkv, 128, nsplit, scale, 0,
                             nullptr, nullptr, nullptr, 0, (hipStream_t)stream));
+    return TRACE_OK;
+}
+// trace_op_attn_decode over caches of num_slots >= B slots (sequence b in slot b), positions below shared_rows (floored to a multiple of 32) of every
+// sequence read from slot shared_slot; a sequence whose newest position lies below them is refused before the launch.
+extern "C" int trace_op_attn_decode_shared(const void* q, const void* kcache, const void* vcache, const int32_t* pos, void* O, float* ws, int B, int nq,
+                                           int nkv, int num_slots, int max_ctx, int nsplit, float scale, int shared_slot, int shared_rows, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!q || !kcache || !vcache || !O || !ws) return fail(TRACE_ERR_ARG, "null argument");
+    TRY(op_attn_decode_state(B, nq, nkv, max_ctx, nsplit));
+    if (num_slots < B || shared_rows < 0 || shared_rows > max_ctx) return fail(TRACE_ERR_ARG, "bad num_slots / shared_rows");
+    shared_rows &= ~31;
+    if (shared_rows > 0 && (shared_slot < 0 || shared_slot >= num_slots)) return fail(TRACE_ERR_ARG, "shared slot out of range");
+    if (!pos) return fail(TRACE_ERR_ARG, "null pos");
+    std::vector<int32_t> hp(B);
+    HIPCHK(hipMemcpyAsync(hp.data(), pos, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) {
+        if (hp[b] < 0 || hp[b] >= max_ctx) return fail(TRACE_ERR_ARG, "position out of range");
+        if (hp[b] < shared_rows) return fail(TRACE_ERR_ARG, "a sequence is shorter than the shared prefix");
+    }
+    LCHK(launch_attn_decode((const bf16_t*)q, nq * 128, (bf16_t*)kcache, (bf16_t*)vcache, (long)nkv * max_ctx * 128, (long)max_ctx * 128, max_ctx, g_op_slots,
+                            pos, (bf16_t*)O, nq * 128, ws, g_op_tickets, B, nq, nkv, 128, nsplit, scale, 0, nullptr, nullptr, nullptr, 0, s,
+                            shared_rows > 0 ? shared_slot : -1, shared_rows));
     return TRACE_OK;
 }
 extern "C" int trace_op_qkv_finish(const float* part, int ks, void* q_out, void* kcache, void* vtcache, const int32_t* slots, const int32_t* pos,

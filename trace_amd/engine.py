@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
-from .prefix import APPEND_GROUP_MAX, group_by_length, split_questions
+from .prefix import APPEND_GROUP_MAX, SHARE_PREFIX_MIN_BATCH, group_by_length, shared_prefix_len, split_questions
 from .sampling import LogitsParams, SamplingParams, argmax_rows, sample_rows_host
 from . import scoring
 
@@ -35,6 +35,10 @@ def _i32(seq) -> "C.Array":
 
 
 class TraceEngine:
+    # Batches of at least this many videos prefill the prompt rows they have in common before <video> once and share them (encode_prefill; the
+    # break-even: prefix.SHARE_PREFIX_MIN_BATCH).  An instance may set its own.
+    share_prefix_min_batch = SHARE_PREFIX_MIN_BATCH
+
     def __init__(self, cfg: TraceConfig, device: int = 0, max_batch: int = 1, max_ctx: Optional[int] = None,
                  max_frames: Optional[int] = None, max_new_tokens: int = 1024, vit_batch_frames: Optional[int] = None,
                  llm_fp8=False, dtype: torch.dtype = torch.bfloat16, kv_cache=None):
@@ -339,6 +343,18 @@ class TraceEngine:
             self._drop_prefix()
         _lib.check(self.lib.trace_kv_copy(self.h, int(src), _i32(dsts), len(dsts), int(rows), _stream()))
 
+    def prefill_shared(self, src: int, slot0: int, past: int, embeds: Sequence[torch.Tensor]):
+        """A run of a batch that shares its first `past` prompt rows, held by slot `src` (trace_llm_prefill_shared): the rows are copied to slots
+        slot0 .. slot0 + n - 1 (those that are not `src`) and every slot continues with its own rows embeds[i] [L, hidden] (equal shapes)."""
+        keep = [e.contiguous() for e in embeds]
+        n = len(keep)
+        assert 1 <= n <= APPEND_GROUP_MAX and all(e.shape == keep[0].shape and e.dtype == self.dtype and e.is_cuda for e in keep)
+        ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in keep])
+        if slot0 == 0:
+            self._drop_prefix()
+        _lib.check(self.lib.trace_llm_prefill_shared(self.h, int(src), int(slot0), n, int(past), ptrs, keep[0].shape[0], _stream()))
+        self.stats["prefill_rows"] += n * keep[0].shape[0]
+
     # The model's prefix cache (TraceMistralForCausalLM.enable_prefix_cache) keeps its one entry in KV slot 0.  Whether the slot still holds those rows is
     # decided here: every call that rewrites slot 0 from row 0 or below the entry's length, or encodes a video (the entry's owner then no longer knows
     # which video the engine last saw), drops it.  Decoding never does: it writes rows at and above the slot's length.
@@ -487,8 +503,12 @@ class TraceEngine:
 
     # ---- decode --------------------------------------------------------------------------------
     def decode_begin(self, slots: Sequence[int], heads: Sequence[int], max_new: int, eos: int = -1,
-                     forced: Optional[Sequence[Sequence[int]]] = None, want_logits: bool = False):
+                     forced: Optional[Sequence[Sequence[int]]] = None, want_logits: bool = False, shared_prefix=None):
+        """shared_prefix: (slot, rows) as encode_prefill returns it — every slot of the batch holds the same first `rows` rows, `slot` among them:
+        the decode attention reads whole 32-position blocks of them from that slot alone (trace_decode_set_shared_prefix)."""
         B = len(slots)
+        if shared_prefix is not None:
+            _lib.check(self.lib.trace_decode_set_shared_prefix(self.h, int(shared_prefix[0]), int(shared_prefix[1]) & ~31))
         self._B, self._max_new = B, max_new
         f = None
         if forced is not None:
@@ -631,7 +651,11 @@ class TraceEngine:
                        record_stages: bool = False):
         """Stage 1 of generate() for a batch: CLIP tower (over the batch's frame stream) -> slot pool + time rows -> splice -> prefill
         into KV slots slot0 .. slot0 + B - 1.  Runs on the current stream; touches no decode state, so it may run on another stream
-        while an earlier batch (other slots) is being decoded (generate_stream)."""
+        while an earlier batch (other slots) is being decoded (generate_stream).
+        A batch of share_prefix_min_batch videos or more whose prompts agree before <video> (one question for every video: the evaluation loops)
+        prefills those P rows once, into the batch's first slot, and every run continues from a copy of them (trace_llm_prefill_shared): the same
+        bits in every slot as whole prefills leave (16-bit KV cache and 16-bit weights only: a continuation is not bit-identical under the others).
+        Returns (first slot, P) then — what decode(shared_prefix=) takes — and None otherwise."""
         B = len(videos)
         if slot0 < 0 or slot0 + B > self.max_batch:
             raise ValueError(f"slots {slot0}..{slot0 + B - 1} exceed the engine's {self.max_batch} KV slots")
@@ -642,10 +666,20 @@ class TraceEngine:
         # rounds of the CUs); the spliced embeddings of a run wait in `held`
         held: List[torch.Tensor] = []                 # spliced embeds of slots held_slot0 .. (equal lengths)
         held_slot0 = 0
+        P = 0                                         # prompt rows shared by the batch
+        if 2 <= B and B >= self.share_prefix_min_batch and not self.kv_cache and not self.llm_fp8:
+            P = shared_prefix_len(input_ids)
+        if P:
+            def prefix():
+                self.embed_rows(input_ids[0][:P])
+                self.prefill(slot0, P)
+            self._bracket("prefill", prefix, rec)
 
         def flush():
             nonlocal held
-            if len(held) == 1:
+            if held and P:
+                self._bracket("prefill", lambda: self.prefill_shared(slot0, held_slot0, P, [e[P:] for e in held]), rec)
+            elif len(held) == 1:
                 self._bracket("prefill", lambda: self.prefill(held_slot0, held[0].shape[0], embeds=held[0]), rec)
             elif len(held) == 2:
                 self._bracket("prefill", lambda: self.prefill_pair(held_slot0, held[0], held[1]), rec)
@@ -672,17 +706,19 @@ class TraceEngine:
                 self._bracket("prefill", lambda: self.prefill(slot0, L1), rec)
                 continue
             L, emb = self.splice(input_ids[b], want_output=True)
-            if held and (held[0].shape[0] != L or len(held) == self.prefill_group(held[0].shape[0])):
+            if held and (held[0].shape[0] != L or len(held) == self.prefill_group(held[0].shape[0] - P)):
                 flush()
             if not held:
                 held_slot0 = slot0 + b
             held.append(emb)
         flush()
+        return (slot0, P) if P else None
 
     def decode(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
                forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-               logits: Optional[LogitsParams] = None):
+               logits: Optional[LogitsParams] = None, shared_prefix=None):
         """Stage 2 of generate(): the decode loop over prefilled KV slots, on the current stream -> (ids per sequence, final heads).
+        shared_prefix: what encode_prefill returned for these slots (decode_begin: the attention reads the shared rows from one slot; same results).
         logits: repetition penalty / no-repeat n-grams / min_new_tokens (LogitsParams; None or all off = today's launches and graphs), applied
         inside the decode step to the ids each row has generated so far (set_logits_params); not together with forced ids.
         sampling: None / temperature <= 0 = greedy; otherwise every id is drawn on the device (trace_decode_set_sampling: same graphs, same
@@ -693,7 +729,7 @@ class TraceEngine:
         if armed and forced is not None:
             raise ValueError("logits processors act on the ids a row has recorded; under forced ids those are not the fed ones (forced= with logits=)")
         if sampling is not None and not sampling.greedy and not sampling.on_device:
-            return self.decode_stepwise(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits)
+            return self.decode_stepwise(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits, shared_prefix=shared_prefix)
         on_dev = sampling is not None and not sampling.greedy
         if on_dev:
             self.set_sampling(sampling)
@@ -702,7 +738,7 @@ class TraceEngine:
         if armed:
             self.set_logits_params(logits)
         try:
-            return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs)
+            return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs, shared_prefix)
         finally:
             if armed:
                 self.set_logits_params(None)
@@ -713,7 +749,7 @@ class TraceEngine:
 
     def decode_stepwise(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1,
                         forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-                        logits: Optional[LogitsParams] = None, stopping=None):
+                        logits: Optional[LogitsParams] = None, stopping=None, shared_prefix=None):
         """decode() one eager step at a time with the token picked on the host: the one loop in host-select mode (sampling parameters outside the
         device sampler's domain, stopping criteria).  Every rule is the device step's.  The row the pick reads is the processed one
         (logits_process: the history is the ids recorded so far) when `logits` is armed, else the raw one; sampled rows go through sample(),
@@ -728,7 +764,7 @@ class TraceEngine:
         armed = logits is not None and not logits.off
         self.host_mode(True)
         try:
-            raw = self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, want_logits=True)
+            raw = self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, want_logits=True, shared_prefix=shared_prefix)
             ids, cur = [[] for _ in range(B)], list(heads)
             lp = np.zeros((B, max_new_tokens), np.float32)
             stopped = [None] * B                          # the length at which `stopping` fired for the row
@@ -760,8 +796,8 @@ class TraceEngine:
         finally:
             self.host_mode(False)
 
-    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False):
-        self.decode_begin(list(slots), heads, max_new_tokens, eos, forced)
+    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False, shared_prefix=None):
+        self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, shared_prefix=shared_prefix)
         if max_new_tokens > 1:
             if eos < 0:
                 self.decode_steps(max_new_tokens - 1, use_graph)
@@ -784,8 +820,8 @@ class TraceEngine:
         B = len(videos)
         if B > self.decode_batch_max:
             raise ValueError(f"batch {B} exceeds the engine's decode batch {self.decode_batch_max}")
-        self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
-        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits)
+        shared = self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
+        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits, shared_prefix=shared)
 
     def generate_samples(self, video: torch.Tensor, timestamps, prompt_ids: Sequence[int], head: int, n: int, max_new_tokens: int, eos: int = -1,
                          sampling: Optional[SamplingParams] = None, use_graph: bool = True, logits: Optional[LogitsParams] = None):
@@ -877,15 +913,15 @@ class TraceEngine:
         cur = torch.cuda.current_stream(self.device)
         enc_s.wait_stream(cur); dec_s.wait_stream(cur)
 
-        def dec_job(bank, heads, forced, B, ready):
+        def dec_job(bank, heads, forced, B, ready, shared):
             torch.cuda.set_device(self.device)
             with torch.cuda.stream(dec_s):
                 dec_s.wait_event(ready)
                 # (logprobs: read inside this job, right after the ids — decode() returns them, nothing goes through engine state afterwards)
                 return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs,
-                                   logits=logits)
+                                   logits=logits, shared_prefix=shared)
 
-        pending = None                                  # (bank, heads, forced, B, ready event): prefilled, waiting for its decode
+        pending = None                                  # (bank, heads, forced, B, ready event, shared prefix): prefilled, waiting for its decode
         bank = 0
         # profiling mode 2 brackets single launches with HIP events: meaningful only while a stage has the GPU to itself — the first batch's
         # encode (pipeline fill) and the last batch's decode (drain); in between the brackets are off
@@ -901,7 +937,7 @@ class TraceEngine:
                     enc_s.wait_stream(cur)                  # the batch's frames may have been made on the caller's stream (device preprocessing)
                     try:
                         with torch.cuda.stream(enc_s):
-                            self.encode_prefill(videos, timestamps, input_ids, bank * half, record_stages=pending is None)
+                            shared = self.encode_prefill(videos, timestamps, input_ids, bank * half, record_stages=pending is None)      # (the bank's own shared slot)
                             if self._dbg is not None:
                                 self._dbg("prefilled", bank * half, None)
                             ready = torch.cuda.Event()
@@ -910,7 +946,7 @@ class TraceEngine:
                         out = fut.result() if fut is not None else None      # also drains the decode stage before an exception propagates
                     if out is not None:
                         yield out
-                    pending = (bank, list(heads), forced, len(videos), ready)
+                    pending = (bank, list(heads), forced, len(videos), ready, shared)
                     bank ^= 1
                 if pending is not None:
                     brackets(2)
@@ -1189,6 +1225,20 @@ class ops:
         o = torch.empty_like(q)
         _lib.check(lib.trace_op_attn_decode(_ptr(q), _ptr(kcache), _ptr(vcache), _ptr(pos), _ptr(o), _ptr(ws), Bn, nq, nkv,
                                             max_ctx, nsplit, scale, _stream()))
+        return o
+
+    @staticmethod
+    def attn_decode_shared(q, kcache, vtcache, pos, nsplit, scale, shared_slot, shared_rows):
+        """attn_decode over caches of S >= B slots (kcache [S, nkv, max_ctx, 128], vtcache [S, nkv, 128, max_ctx]; row b in slot b) with positions
+        below shared_rows of every row read from slot shared_slot (trace_op_attn_decode_shared)."""
+        lib = _lib.load(ops.element)
+        Bn = q.shape[0]
+        S, nkv, max_ctx = kcache.shape[0], kcache.shape[1], kcache.shape[2]
+        nq = q.shape[1] // 128
+        ws = torch.zeros((Bn * nq * nsplit * 130,), dtype=torch.float32, device=q.device)
+        o = torch.empty_like(q)
+        _lib.check(lib.trace_op_attn_decode_shared(_ptr(q), _ptr(kcache), _ptr(vtcache), _ptr(pos), _ptr(o), _ptr(ws), Bn, nq, nkv, S, max_ctx, nsplit,
+                                                   scale, int(shared_slot), int(shared_rows), _stream()))
         return o
 
     @staticmethod

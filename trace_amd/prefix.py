@@ -9,6 +9,10 @@ from .constants import MMODAL_TOKEN_INDEX
 
 VIDEO_IDS = (MMODAL_TOKEN_INDEX["VIDEO"], MMODAL_TOKEN_INDEX["IMAGE"])      # both expand to the encoded rows (trace_splice_embeds)
 APPEND_GROUP_MAX = 8                                                        # slots one trace_llm_prefill_append call takes
+# Smallest batch whose common prompt rows are prefilled once and shared (TraceEngine.share_prefix_min_batch).  Sharing P rows saves (B - 1) x P prefill
+# rows (about 0.9 ms per video at P = 150 on the 7B decoder) for one P-row prefill on its own (about 15 ms, a launch-bound pass) and one copy of the rows
+# into every slot: break-even near 16 - 20 videos.
+SHARE_PREFIX_MIN_BATCH = 32
 
 
 def split_prompt(ids: Sequence[int]) -> Tuple[List[int], List[int]]:
@@ -47,3 +51,19 @@ def group_by_length(lengths: Sequence[int], max_group: int = APPEND_GROUP_MAX) -
         for o in range(0, len(idx), max_group):
             out.append((n, idx[o:o + max_group]))
     return out
+
+
+def shared_prefix_len(prompts: Sequence[Sequence[int]]) -> int:
+    """Rows a batch shares before the video: P, the number of ids in front of the first prompt's video placeholder, if EVERY prompt has those
+    same P ids followed by its placeholder (one question put to every video — the evaluation loops); otherwise 0, the batch shares nothing.
+    Those ids are plain embedding rows, the same in every prompt, and the decoder is causal: their K / V rows are the same bits for every
+    sequence.  What follows the placeholder may differ.  0 as well for an empty batch, a prompt without a placeholder, or a placeholder in
+    front; a single prompt "shares" its own P rows (the caller decides whether one prompt is a batch)."""
+    prompts = [[int(x) for x in p] for p in prompts]
+    if not prompts:
+        return 0
+    first = prompts[0]
+    at = next((i for i, x in enumerate(first) if x in VIDEO_IDS), None)
+    if at is None or any(p[: at + 1] != first[: at + 1] for p in prompts):
+        return 0
+    return at
