@@ -1082,13 +1082,36 @@ class ops:
                 _lib.check(lib.trace_op_tuning_set(name.encode(), value))
 
     @staticmethod
-    def gemm(A, W, bias=None, R=None, epilogue=EPI_NONE):
+    def gemm(A, W, bias=None, R=None, epilogue=EPI_NONE, out=None, ldc=None, out_offset=0):
+        """trace_op_gemm.  A [M, K], W [N, K] and R [M, No] may be strided views (unit column stride): a view's row stride is the leading dimension the
+        kernel gets, its storage offset the base pointer's.  `out`: where to store instead of a fresh [M, No] tensor — a 2-D view [M, No] (ldc = its row
+        stride; R itself for the in-place residual), or a flat buffer with `ldc` and `out_offset` (elements: C[m, n] = out[out_offset + m ldc + n]).
+        Returns the [M, No] window that was written."""
         lib = _lib.load(ops.element)
         M, K = A.shape
         N = W.shape[0]
         No = N // 2 if epilogue == EPI_SWIGLU else N
-        Cc = torch.empty((M, No), dtype=ops.dtype(), device=A.device)
-        _lib.check(lib.trace_op_gemm(_ptr(A), A.stride(0), _ptr(W), W.stride(0), _ptr(Cc), No, _ptr(bias), _ptr(R),
+        for t in (A, W) + (() if R is None else (R,)):
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError("operands must be 2-D with unit column stride")
+        if out is None:
+            if ldc is not None or out_offset:
+                raise ValueError("ldc / out_offset describe `out`")
+            Cc = torch.empty((M, No), dtype=ops.dtype(), device=A.device)
+        else:
+            if out.dtype != ops.dtype() or out.device != A.device:
+                raise ValueError("out: wrong element type or device")
+            if out.dim() == 2 and ldc is None and not out_offset:
+                if tuple(out.shape) != (M, No) or out.stride(1) != 1:
+                    raise ValueError(f"out: expected a [{M}, {No}] view with unit column stride")
+                Cc = out
+            elif out.dim() == 1 and out.is_contiguous() and ldc is not None and ldc >= No and out_offset >= 0:
+                if out_offset + (M - 1) * ldc + No > out.numel():
+                    raise ValueError("out: the window leaves the buffer")
+                Cc = out.as_strided((M, No), (ldc, 1), out.storage_offset() + out_offset)
+            else:
+                raise ValueError("out: a 2-D view, or a flat buffer with ldc (>= the output width) and out_offset")
+        _lib.check(lib.trace_op_gemm(_ptr(A), A.stride(0), _ptr(W), W.stride(0), _ptr(Cc), Cc.stride(0), _ptr(bias), _ptr(R),
                                      0 if R is None else R.stride(0), M, N, K, epilogue, _stream()))
         return Cc
 
