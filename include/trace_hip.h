@@ -340,6 +340,25 @@ int trace_op_gemm_route(int M, int N, int K, int lda, int ldw, int ldc, int ldr,
 int trace_op_set_gemm_trace(void* buf);
 int trace_op_layernorm(const void* x, void* y, const void* w, const void* b, int rows, int D, float eps, void* stream);
 int trace_op_rmsnorm(const void* x, void* y, const void* w, int rows, int D, float eps, void* stream);
+/* The same two with what the engine's call sites use: row strides ldx / ldy (elements, multiples of 8; y may be x), and for the LayerNorm silu = 1
+ * (y = SiLU(el(LN(x)))) and res / ldres (y = act(el(LN(x)) + res), y may be res; NULL = none) — el() rounds to the 16-bit element type first. */
+int trace_op_layernorm_ex(const void* x, int ldx, void* y, int ldy, const void* w, const void* b, int rows, int D, float eps, int silu,
+                          const void* res, int ldres, void* stream);
+int trace_op_rmsnorm_ex(const void* x, int ldx, void* y, int ldy, const void* w, int rows, int D, float eps, void* stream);
+/* SpatialSlotPool before `readout` (trace_slot_pool without its GEMM): feats + t * frame_stride + p * row_stride is patch p of frame t (elements;
+ * frame_stride a multiple of 8, row_stride a multiple of 8 and >= D), ln_w / ln_b [D], slots [D, 8], cos_t / sin_t fp32 [n, D / 2] (the caller's
+ * tables), res_out [T, 8, D], D a multiple of 16 up to 1024.  ws: trace_op_slot_pool_ws_floats(T, D) floats of device scratch. */
+int64_t trace_op_slot_pool_ws_floats(int T, int D);
+int trace_op_slot_pool(const void* feats, int64_t frame_stride, int row_stride, const void* ln_w, const void* ln_b, const void* slots,
+                       const float* cos_t, const float* sin_t, void* res_out, int T, int n, int D, float eps, float* ws, int64_t ws_floats,
+                       void* stream);
+/* The fused ViT front end from checkpoint-layout tensors, run as the load and forward paths run it (weight repack, CLS row, patch-embed kernel):
+ * frames [T, 3, S, S] (frames_dtype as in trace_vit_forward), conv_w [D, 3 P P], cls [D], pos [G G + 1, D] (G = S / P), pre_layrnorm weight / bias
+ * [D] -> X_out [T, G G + 1, D].  ws: trace_op_patch_embed_ws_elems(P, D) 16-bit elements of device scratch.  TRACE_ERR_ARG for a geometry the
+ * fused kernel does not take (P outside {14, 16}, S % P != 0, D outside {128, 256, 512, 1024}) — there the engine runs im2col + GEMM + assemble. */
+int64_t trace_op_patch_embed_ws_elems(int P, int D);
+int trace_op_patch_embed(const void* frames, int frames_dtype, const void* conv_w, const void* cls, const void* pos, const void* pre_w,
+                         const void* pre_b, void* X_out, int T, int S, int P, int D, float eps, void* ws, int64_t ws_elems, void* stream);
 int trace_op_attention(const void* Q, const void* K, const void* V, void* O, void* vt_scratch, int batch, int heads,
                        int kv_heads, int nq, int nkv, int head_dim, int causal, float scale, void* stream);
 /* Decode GEMV out[b,n] = sum_k X[b,k] W[n,k], B <= 64.  w_tiled: W in the decode tile layout written by

@@ -92,6 +92,12 @@ SIGNATURES = {
     "trace_op_gemm_route": (I, [I, I, I, I, I, I, I, I, I]),
     "trace_op_layernorm": (I, [P, P, P, P, I, I, F, P]),
     "trace_op_rmsnorm": (I, [P, P, P, I, I, F, P]),
+    "trace_op_layernorm_ex": (I, [P, I, P, I, P, P, I, I, F, I, P, I, P]),
+    "trace_op_rmsnorm_ex": (I, [P, I, P, I, P, I, I, F, P]),
+    "trace_op_slot_pool_ws_floats": (C.c_int64, [I, I]),
+    "trace_op_slot_pool": (I, [P, C.c_int64, I, P, P, P, P, P, P, I, I, I, F, P, C.c_int64, P]),
+    "trace_op_patch_embed_ws_elems": (C.c_int64, [I, I]),
+    "trace_op_patch_embed": (I, [P, I, P, P, P, P, P, P, I, I, I, I, F, P, C.c_int64, P]),
     "trace_op_attention": (I, [P, P, P, P, P, I, I, I, I, I, I, I, F, P]),
     "trace_op_skinny_gemm": (I, [P, P, P, P, I, I, I, I, I, P]),
     "trace_op_set_gemm_trace": (I, [P]),

@@ -1963,6 +1963,51 @@ extern "C" int trace_op_rmsnorm(const void* x, void* y, const void* w, int rows,
     LCHK(launch_rmsnorm((const bf16_t*)x, D, (bf16_t*)y, D, (const bf16_t*)w, rows, D, eps, (hipStream_t)stream));
     return TRACE_OK;
 }
+// The norms with everything the engine's call sites use: row strides, the SiLU and residual tails of the LayerNorm (y may alias x or res)
+extern "C" int trace_op_layernorm_ex(const void* x, int ldx, void* y, int ldy, const void* w, const void* b, int rows, int D, float eps, int silu,
+                                     const void* res, int ldres, void* stream) {
+    if (!x || !y || !w || !b) return fail(TRACE_ERR_ARG, "null argument");
+    LCHK(launch_layernorm((const bf16_t*)x, ldx, (bf16_t*)y, ldy, (const bf16_t*)w, (const bf16_t*)b, rows, D, eps, (hipStream_t)stream, silu,
+                          (const bf16_t*)res, ldres));
+    return TRACE_OK;
+}
+extern "C" int trace_op_rmsnorm_ex(const void* x, int ldx, void* y, int ldy, const void* w, int rows, int D, float eps, void* stream) {
+    if (!x || !y || !w) return fail(TRACE_ERR_ARG, "null argument");
+    LCHK(launch_rmsnorm((const bf16_t*)x, ldx, (bf16_t*)y, ldy, (const bf16_t*)w, rows, D, eps, (hipStream_t)stream));
+    return TRACE_OK;
+}
+// launch_slot_pool alone (no readout GEMM): res_out [T, 8, D].  ws: trace_op_slot_pool_ws_floats(T, D) floats.
+extern "C" int64_t trace_op_slot_pool_ws_floats(int T, int D) { return T > 0 && D > 0 ? (int64_t)launch_slot_pool_ws_floats(T, D) : (int64_t)TRACE_ERR_ARG; }
+extern "C" int trace_op_slot_pool(const void* feats, int64_t frame_stride, int row_stride, const void* ln_w, const void* ln_b, const void* slots,
+                                  const float* cos_t, const float* sin_t, void* res_out, int T, int n, int D, float eps, float* ws, int64_t ws_floats,
+                                  void* stream) {
+    if (!feats || !ln_w || !ln_b || !slots || !cos_t || !sin_t || !res_out) return fail(TRACE_ERR_ARG, "null argument");
+    if (frame_stride < 0 || (frame_stride % 8) || row_stride < D) return fail(TRACE_ERR_ARG, "strides: frame_stride a multiple of 8 elements, row_stride >= D");
+    if (ws_floats < 0) return fail(TRACE_ERR_ARG, "bad workspace size");
+    LCHK(launch_slot_pool((const bf16_t*)feats, (long)frame_stride, row_stride, (const bf16_t*)ln_w, (const bf16_t*)ln_b, (const bf16_t*)slots, cos_t, sin_t,
+                          (bf16_t*)res_out, T, n, D, 8, eps, ws, (size_t)ws_floats, (hipStream_t)stream));
+    return TRACE_OK;
+}
+// The fused ViT front end from checkpoint-layout tensors, as trace_ctx_finalize + trace_vit_forward run it: launch_patch_pack, launch_cls_row, launch_patch_embed.
+// conv_w [D, 3 P P], cls [D], pos [G G + 1, D], X_out [T, G G + 1, D]; ws: trace_op_patch_embed_ws_elems(P, D) 16-bit elements (packed weight + CLS row).
+extern "C" int64_t trace_op_patch_embed_ws_elems(int P, int D) {
+    return patch_embed_supported(P, P, D) ? (int64_t)(patch_embed_packed_elems(P, D) + (size_t)D) : (int64_t)TRACE_ERR_ARG;
+}
+extern "C" int trace_op_patch_embed(const void* frames, int frames_dtype, const void* conv_w, const void* cls, const void* pos, const void* pre_w,
+                                    const void* pre_b, void* X_out, int T, int S, int P, int D, float eps, void* ws, int64_t ws_elems, void* stream) {
+    if (!frames || !conv_w || !cls || !pos || !pre_w || !pre_b || !X_out) return fail(TRACE_ERR_ARG, "null argument");
+    if (T < 1 || S < 1 || !patch_embed_supported(S, P, D)) return fail(TRACE_ERR_ARG, "geometry the fused front end does not take (P in {14, 16}, S % P == 0, D in {128, 256, 512, 1024})");
+    if (frames_dtype != 0 && frames_dtype != 1) return fail(TRACE_ERR_ARG, "frames_dtype: 0 = 16-bit, 1 = fp32");
+    if (!ws || ws_elems < trace_op_patch_embed_ws_elems(P, D)) return fail(TRACE_ERR_ARG, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t* wp = (bf16_t*)ws;
+    bf16_t* cls_row = wp + patch_embed_packed_elems(P, D);
+    LCHK(launch_patch_pack((const bf16_t*)conv_w, 3 * P * P, wp, D, P, s));
+    LCHK(launch_cls_row((const bf16_t*)cls, (const bf16_t*)pos, (const bf16_t*)pre_w, (const bf16_t*)pre_b, cls_row, D, eps, s));
+    LCHK(launch_patch_embed(frames, frames_dtype == 1, wp, (const bf16_t*)pos, (const bf16_t*)pre_w, (const bf16_t*)pre_b, cls_row, (bf16_t*)X_out, T, S, P, D,
+                            eps, s));
+    return TRACE_OK;
+}
 // Q [batch, nq, heads, hd], K/V [batch, nkv, kv_heads, hd] (token-major, heads interleaved), O like Q.
 // vt_scratch: batch*kv_heads*hd*round_up(nkv,64) bf16.
 extern "C" int trace_op_attention(const void* Q, const void* K, const void* V, void* O, void* vt_scratch, int batch, int heads,

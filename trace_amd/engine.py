@@ -1130,6 +1130,88 @@ class ops:
         return y
 
     @staticmethod
+    def _rows2d(t, name):
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{name}: a 2-D tensor or view with unit column stride")
+        return t
+
+    @staticmethod
+    def layernorm_ex(x, w, b, eps, out=None, silu=False, res=None):
+        """trace_op_layernorm_ex.  x [rows, D], `out` and `res` may be strided views (unit column stride; a view's row stride is the leading dimension
+        the kernel gets); out=None: a fresh contiguous tensor; out may be x (in place) or res.  Returns the window written."""
+        lib = _lib.load(ops.element)
+        ops._rows2d(x, "x")
+        y = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device) if out is None else ops._rows2d(out, "out")
+        if tuple(y.shape) != tuple(x.shape) or (res is not None and tuple(ops._rows2d(res, "res").shape) != tuple(x.shape)):
+            raise ValueError("out / res: the shape of x")
+        _lib.check(lib.trace_op_layernorm_ex(_ptr(x), x.stride(0), _ptr(y), y.stride(0), _ptr(w), _ptr(b), x.shape[0], x.shape[1], float(eps),
+                                             int(bool(silu)), _ptr(res), 0 if res is None else res.stride(0), _stream()))
+        return y
+
+    @staticmethod
+    def rmsnorm_ex(x, w, eps, out=None):
+        """trace_op_rmsnorm_ex: as layernorm_ex, without bias, SiLU or residual"""
+        lib = _lib.load(ops.element)
+        ops._rows2d(x, "x")
+        y = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device) if out is None else ops._rows2d(out, "out")
+        if tuple(y.shape) != tuple(x.shape):
+            raise ValueError("out: the shape of x")
+        _lib.check(lib.trace_op_rmsnorm_ex(_ptr(x), x.stride(0), _ptr(y), y.stride(0), _ptr(w), x.shape[0], x.shape[1], float(eps), _stream()))
+        return y
+
+    @staticmethod
+    def slot_pool(feats, ln_w, ln_b, slots, cos_t, sin_t, eps):
+        """trace_op_slot_pool: feats [T, n, D] — a view with unit channel stride, any frame / row strides that are multiples of 8 elements — ln_w / ln_b
+        [D], slots [D, 8], cos_t / sin_t fp32 [n, D / 2] -> res [T, 8, D] (SpatialSlotPool before `readout`)."""
+        lib = _lib.load(ops.element)
+        if feats.dim() != 3 or feats.stride(2) != 1:
+            raise ValueError("feats: [T, n, D] with unit channel stride")
+        T, n, D = feats.shape
+        cos_t, sin_t = cos_t.contiguous(), sin_t.contiguous()
+        if tuple(slots.shape) != (D, 8) or tuple(cos_t.shape) != (n, D // 2) or tuple(sin_t.shape) != (n, D // 2) or cos_t.dtype != torch.float32 \
+                or sin_t.dtype != torch.float32:
+            raise ValueError("slots [D, 8]; cos_t / sin_t fp32 [n, D / 2]")
+        nws = int(lib.trace_op_slot_pool_ws_floats(T, D))
+        if nws < 0:
+            raise _lib.TraceHipError(f"error {nws} in trace_op_slot_pool_ws_floats")
+        ws = torch.empty(nws, dtype=torch.float32, device=feats.device)
+        out = torch.empty((T, 8, D), dtype=feats.dtype, device=feats.device)
+        _lib.check(lib.trace_op_slot_pool(_ptr(feats), feats.stride(0) if T > 1 else n * feats.stride(1), feats.stride(1), _ptr(ln_w.contiguous()),
+                                          _ptr(ln_b.contiguous()), _ptr(slots.contiguous()), _ptr(cos_t), _ptr(sin_t), _ptr(out), T, n, D, float(eps),
+                                          _ptr(ws), nws, _stream()))
+        return out
+
+    @staticmethod
+    def patch_embed(frames, conv_w, cls, pos, pre_w, pre_b, P, eps, out=None):
+        """trace_op_patch_embed: frames [T, 3, S, S] (the element type, or fp32), conv_w [D, 3 P P] (or [D, 3, P, P]), cls [D], pos [G G + 1, D],
+        pre_w / pre_b [D] -> X [T, G G + 1, D] = pre_layrnorm(cat(CLS, conv(frames)) + pos).  `out`: a flat buffer of at least T (G G + 1) D elements to
+        store into (a test's buffer with guard rows) instead of a fresh tensor.  TraceHipError (TRACE_ERR_ARG) for a geometry the fused kernel does not
+        take."""
+        lib = _lib.load(ops.element)
+        dt = ops.dtype()
+        if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[2] != frames.shape[3] or frames.dtype not in (dt, torch.float32):
+            raise ValueError("frames: [T, 3, S, S] in the element type or fp32")
+        frames = frames.contiguous()
+        T, S = frames.shape[0], frames.shape[2]
+        D = conv_w.shape[0]
+        w = conv_w.reshape(D, -1).contiguous()
+        G = S // max(P, 1)
+        nws = int(lib.trace_op_patch_embed_ws_elems(P, D))
+        taken = nws >= 0 and S % P == 0                                        # (else the op answers TRACE_ERR_ARG before it reads anything)
+        if any(t.dtype != dt for t in (w, cls, pos, pre_w, pre_b)) or (taken and (w.shape[1] != 3 * P * P or tuple(pos.shape) != (G * G + 1, D)
+                                                                                  or cls.numel() != D or pre_w.numel() != D or pre_b.numel() != D)):
+            raise ValueError("conv_w [D, 3 P P], cls / pre_w / pre_b [D], pos [G G + 1, D], all in the element type")
+        ws = torch.empty(max(nws, 8), dtype=dt, device=frames.device)          # (a refused geometry: the op itself answers TRACE_ERR_ARG)
+        if out is None:
+            out = torch.empty(T * (G * G + 1) * D, dtype=dt, device=frames.device)
+        elif out.dim() != 1 or not out.is_contiguous() or out.dtype != dt or out.device != frames.device or out.numel() < T * (G * G + 1) * D:
+            raise ValueError("out: a flat contiguous buffer of the element type with room for [T, G G + 1, D]")
+        _lib.check(lib.trace_op_patch_embed(_ptr(frames), 1 if frames.dtype == torch.float32 else 0, _ptr(w), _ptr(cls.contiguous()),
+                                            _ptr(pos.contiguous()), _ptr(pre_w.contiguous()), _ptr(pre_b.contiguous()), _ptr(out), T, S, P, D,
+                                            float(eps), _ptr(ws), max(nws, 0), _stream()))
+        return out[:T * (G * G + 1) * D].view(T, G * G + 1, D)
+
+    @staticmethod
     def attention(q, k, v, causal, scale):
         """q [B, nq, heads, hd]; k, v [B, nkv, kv_heads, hd] -> [B, nq, heads, hd]"""
         lib = _lib.load(ops.element)
