@@ -286,6 +286,44 @@ int trace_decode_read_logprobs(trace_ctx* ctx, float* out, void* stream);
  * setting together with forced != NULL (the history is the recorded ids, which under forced ids are not the fed ones). */
 int trace_decode_set_logits_params(trace_ctx* ctx, float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens);
 
+/* Constraints (generate(bad_words_ids=, suppress_tokens=, begin_suppress_tokens=, stop_sequences=, eos_token_id=[a, b, ...])): HF
+ * NoBadWordsLogitsProcessor, SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor and id-level stop sequences, on the device inside
+ * the decode step.  Notation as above: row b, device step s, head range [lo, hi), history h = out_ids[b][0 .. out_len[b]): generated ids only, as
+ * global vocabulary ids; it never holds the prompt.  The ban rules write -inf into the processed row, after rule 2 above, so a ban overwrites a
+ * penalised value:
+ *   4. bad_words: for every sequence w of k ids: k == 1: x[w[0]] = -inf; k > 1: if len(h) >= k - 1 and the last k - 1 ids of h equal
+ *      w[0 .. k-1): x[w[k-1]] = -inf.  The prefix comparison is over global ids whatever head emitted them: a bad word may cross heads (text id,
+ *      <sync>, time digit).
+ *   5. suppress: x[t] = -inf for every listed t, at every step.
+ *   6. begin_suppress: the same at s == 0 only (HF's begin_index is 0 when generate() is handed inputs_embeds, as the reference does).
+ *   3. (widened) while s < min_new_tokens: eos and the id of every stop sequence of length 1 are banned: HF bans every id of its EOS list.
+ * An id to ban outside [lo, hi) touches nothing.
+ * Stop rule, in the selection, after the step's token is recorded for a row that was not done: a stop sequence w of k ids fires iff
+ * out_len[b] >= k and the last k recorded ids equal w; the row is then done exactly as an EOS row is.  The stop ids stay in the row's output and
+ * out_len counts them, as with EOS.  Matching is over global ids and never reaches into the prompt or another row's history.  A done row keeps
+ * stepping and records nothing.  Several EOS ids are stop sequences of length 1.
+ * Bounds: at most 64 stop sequences and 64 bad-word sequences of 1..32 ids each, at most 1024 ids in each suppress list; every id inside
+ * [0, V+1+Tv+Sv).  Anything else is TRACE_ERR_ARG, before any launch; nothing is truncated.
+ * trace_constraints: size = sizeof(trace_constraints) of the caller; the two sequence lists in CSR form (offsets of n + 1 entries, offsets[0] = 0,
+ * sequence i = ids[offsets[i] .. offsets[i+1])); all pointers are host pointers, read during the call only.
+ * trace_decode_set_constraints: NULL or all counts zero disarms.  Set before trace_decode_begin; it holds for every later batch until changed.  The
+ * first arming call allocates the device table, and the masked / processed logits rows if nothing has allocated them yet.  The table is copied to
+ * device memory at trace_decode_begin and read from there, so a captured step stays valid when it changes between batches; steps with the stop
+ * match are cached apart, and with nothing armed a batch issues the launches and replays the graphs it did before.  Log-probabilities keep
+ * describing the RAW row.  Host-select mode ignores the setting (the host calls trace_op_logits_process_ex / trace_op_stop_match).  An armed
+ * setting together with forced != NULL is TRACE_ERR_ARG at trace_decode_begin, as for the logits params. */
+typedef struct trace_constraints {
+    int32_t size;
+    int32_t n_stop, n_bad_words, n_suppress, n_begin_suppress;
+    const int32_t* stop_offsets;        /* n_stop + 1 */
+    const int32_t* stop_ids;
+    const int32_t* bad_word_offsets;    /* n_bad_words + 1 */
+    const int32_t* bad_word_ids;
+    const int32_t* suppress_ids;
+    const int32_t* begin_suppress_ids;
+} trace_constraints;
+int trace_decode_set_constraints(trace_ctx* ctx, const trace_constraints* constraints);
+
 /* Two-stage pipeline support (trace/eval/evaluate.py:298-417 loops over independent videos: while one batch decodes — HBM-bound —
  * the next batch's ViT + prefill — MFMA-bound — can run on another stream into other KV slots; the stages share no buffers).
  * trace_stream_create: a HIP stream confined to cu_count CUs starting at logical CU cu_first (hipExtStreamCreateWithCUMask; mask bit i
@@ -426,6 +464,16 @@ int trace_op_token_logprob(const float* logits, int ld, int B, const int32_t* he
 int trace_op_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
                             const int32_t* hist_len, const int32_t* steps, int eos, float repetition_penalty, int no_repeat_ngram_size,
                             int min_new_tokens, float* out, void* stream);
+/* trace_op_logits_process with the ban rules of a constraint table behind the three processors (rules 4 - 6 and the widened rule 3 of
+ * trace_decode_set_constraints; `constraints` NULL = none): the device code the decode step runs.  The stop sequences of the table take part only
+ * through rule 3.  The call returns after the stream has run it (the table is staged per call). */
+int trace_op_logits_process_ex(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
+                               const int32_t* hist_len, const int32_t* steps, int eos, float repetition_penalty, int no_repeat_ngram_size,
+                               int min_new_tokens, const trace_constraints* constraints, float* out, void* stream);
+/* The stop rule over loose histories, the same device code: hist int32 [B][ld_hist] / hist_len int32 [B] device as above; fired_out int32 [B] device:
+ * 1 where some stop sequence of `constraints` equals the last ids of hist[b][0 .. hist_len[b]), else 0.  Returns after the stream has run it. */
+int trace_op_stop_match(const int32_t* hist, int ld_hist, const int32_t* hist_len, int B, const trace_constraints* constraints, int32_t* fired_out,
+                        void* stream);
 /* Single-query decode attention over loose caches (head_dim 128, nq == 4 nkv, nkv <= 64, max_ctx % 32 == 0): kcache [B][nkv][max_ctx][128],
  * vtcache [B][nkv][128][max_ctx] (V transposed), row b in slot b; pos[b] (device) = index of the newest token, already in the caches (ctx = pos + 1);
  * q [B][nq * 128] ready (rotated) -> O [B][nq * 128]; ws: B * nq * nsplit * 130 floats.  Cache positions past pos[b] inside a 32-position block are

@@ -32,6 +32,12 @@ class TraceCtxOptsC(C.Structure):
     _fields_ = [("size", C.c_int32), ("kv_cache_fp8", C.c_int32)]
 
 
+class TraceConstraintsC(C.Structure):
+    _fields_ = [("size", C.c_int32), ("n_stop", C.c_int32), ("n_bad_words", C.c_int32), ("n_suppress", C.c_int32), ("n_begin_suppress", C.c_int32),
+                ("stop_offsets", C.c_void_p), ("stop_ids", C.c_void_p), ("bad_word_offsets", C.c_void_p), ("bad_word_ids", C.c_void_p),
+                ("suppress_ids", C.c_void_p), ("begin_suppress_ids", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/trace_hip.h declares
 P, I, F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
@@ -75,6 +81,7 @@ SIGNATURES = {
     "trace_decode_set_logprobs": (I, [P, I]),
     "trace_decode_read_logprobs": (I, [P, P, P]),
     "trace_decode_set_logits_params": (I, [P, F, I, I]),
+    "trace_decode_set_constraints": (I, [P, C.POINTER(TraceConstraintsC)]),
     "trace_stream_create": (I, [P, I, I, C.POINTER(P)]),
     "trace_stream_destroy": (I, [P, P]),
     "trace_set_gemm_cus": (I, [P, I]),
@@ -119,6 +126,8 @@ SIGNATURES = {
     "trace_op_sample": (I, [P, I, I, P, I, I, I, F, I, F, C.c_uint64, P, P, P]),
     "trace_op_token_logprob": (I, [P, I, I, P, I, I, I, P, P, P]),
     "trace_op_logits_process": (I, [P, I, I, P, I, I, I, P, I, P, P, I, F, I, I, P, P]),
+    "trace_op_logits_process_ex": (I, [P, I, I, P, I, I, I, P, I, P, P, I, F, I, I, C.POINTER(TraceConstraintsC), P, P]),
+    "trace_op_stop_match": (I, [P, I, P, I, C.POINTER(TraceConstraintsC), P, P]),
     "trace_op_attn_decode": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
     "trace_op_attn_decode_shared": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, I, I, P]),
     "trace_op_qkv_finish": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, I, P]),

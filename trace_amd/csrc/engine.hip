@@ -17,6 +17,7 @@
 
 #include "../../include/trace_hip.h"
 #include "common.h"
+#include "constrain.h"
 #include "kernels.h"
 #include "logits.h"
 #include "sample.h"
@@ -47,9 +48,11 @@ constexpr int MAX_SLOTS = 512;   // KV-cache sequence slots per context (a decod
 static int g_ctx_per_dev[16] = {0};
 // what the tail of a decode step does beyond the plain arg-max; index(): its place in the graph cache, 0 = the plain step
 struct TailMode {
-    bool sample = false, logprobs = false, process = false;
-    int index() const { return (sample ? 1 : 0) + (logprobs ? 2 : 0) + (process ? 4 : 0); }
+    bool sample = false, logprobs = false, process = false, stop = false;
+    int index() const { return (sample ? 1 : 0) + (logprobs ? 2 : 0) + (process ? 4 : 0) + (stop ? 8 : 0); }
 };
+
+static bool constraints_on(const ConstrainTable& t) { return t.n_stop || t.n_bad || t.n_suppress || t.n_begin; }
 
 struct trace_ctx {
     trace_config c{};
@@ -125,8 +128,8 @@ struct trace_ctx {
     double kbytes_sum = 0.0;           // algorithmic bytes of the bracketed launches (profile == 2)
     int host_mode = 0, fed = 0;        // host-driven token selection (sampling): head logits only, ids fed back by the host
     int steps_done = 0;                // decode steps taken since trace_decode_begin (bounded by max_new - 1: the KV slot and the RoPE tables end at max_ctx)
-    // What the tail of a step (head_and_select) does beyond the plain arg-max: `want` is written by the three trace_decode_set_* calls, `armed` at
-    // trace_decode_begin (= want, or all-off in host-select mode, where the host holds the logits and does all three itself).  A step of each
+    // What the tail of a step (head_and_select) does beyond the plain arg-max: `want` is written by the four trace_decode_set_* calls, `armed` at
+    // trace_decode_begin (= want, or all-off in host-select mode, where the host holds the logits and does all of it itself).  A step of each
     // mode is a graph of its own, graphs[armed.index()][B]: toggling a setting between batches never replays another form, and index 0 is the plain step.
     TailMode want, armed;
     // Shared prompt prefix of the batch being decoded (trace_decode_set_shared_prefix): the decode attention reads positions below sh_rows (a multiple of
@@ -134,7 +137,7 @@ struct trace_ctx {
     // attention, so a captured step is good for one (slot, rows) pair: a graph entry has two ways keyed by it (the two banks of a pipelined caller).
     int sh_want_slot = -1, sh_want_rows = 0, sh_slot = -1, sh_rows = 0;
     struct StepGraph { hipGraphExec_t exec = nullptr; int sh_slot = -1, sh_rows = 0; };
-    StepGraph graphs[8][SK_ROWS + 1][2];
+    StepGraph graphs[16][SK_ROWS + 1][2];
     int graph_evict = 0;               // the way the next miss of a full entry replaces
     // sampling (trace_decode_set_sampling): host copy of the params; the device copy d_sparams, written at trace_decode_begin, is what the selection
     // kernel reads (a captured graph stays valid across calls).  d_slog: the [SK_ROWS][NV] raw masked logits of a step with anything armed.
@@ -152,6 +155,11 @@ struct trace_ctx {
     LogitsParams lgp{1.f, 0, 0};
     LogitsParams* d_lgparams = nullptr;
     float* d_plog = nullptr;
+    // constraints (trace_decode_set_constraints, constrain.h): the host copy of the table; the device copy d_ctab, written at trace_decode_begin, is what
+    // logits_process_kernel (the ban rules: want.process is "any logits param or any ban rule") and select_next_kernel (want.stop) read.  It exists from
+    // the first arming of either, so a captured step of either kind always holds its address.
+    ConstrainTable ctab{};
+    ConstrainTable* d_ctab = nullptr;
     hipStream_t cap_stream = nullptr;
     std::vector<hipStream_t> streams;   // trace_stream_create
     // profiling
@@ -1355,7 +1363,7 @@ static int head_only(trace_ctx* c, const bf16_t* xn, float* logits_out, hipStrea
 // the selection in one of its forms; `rows`: the masked logits SELECT_SAMPLE / SELECT_ROW read (null for SELECT_TILES, which reads the tile partials)
 static int select_only(trace_ctx* c, int form, const float* rows, int advance, hipStream_t s) {
     LCHK(launch_select(form, c->part_val, c->part_idx, rows, form == SELECT_SAMPLE ? c->d_sparams : nullptr, step_state(c), c->embed, c->time_tab,
-                       c->score_tab, c->sync_row, c->dX, c->H, c->B, c->H, c->V, c->Tv, c->Sv, advance, s));
+                       c->score_tab, c->sync_row, c->dX, c->H, c->B, c->H, c->V, c->Tv, c->Sv, advance, s, c->armed.stop ? c->d_ctab : nullptr));
     return TRACE_OK;
 }
 static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* logits_out, hipStream_t s) {
@@ -1365,9 +1373,10 @@ static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* l
     TRY(head_only(c, xn, raw, s));
     // 2. host-select mode ends here: the host picks the token and calls trace_decode_feed
     if (c->host_mode) return TRACE_OK;
-    // 3. logits processors: the raw rows -> d_plog (raw stays as it is for step 5)
-    if (m.process) LCHK(launch_step_logits_process(raw, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_lgparams, c->d_plog, s));
-    // 4. the selection: a draw from the rows, the arg-max over a processed row, or the arg-max over the tile partials (they describe the raw row)
+    // 3. logits processors and the ban rules of the constraints: the raw rows -> d_plog (raw stays as it is for step 5)
+    if (m.process) LCHK(launch_step_logits_process(raw, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_lgparams, c->d_plog, s, c->d_ctab));
+    // 4. the selection: a draw from the rows, the arg-max over a processed row, or the arg-max over the tile partials (they describe the raw row);
+    //    with stop sequences armed, the instantiation that matches them against the recorded ids
     const int form = m.sample ? SELECT_SAMPLE : m.process ? SELECT_ROW : SELECT_TILES;
     TRY(select_only(c, form, form == SELECT_TILES ? nullptr : m.process ? c->d_plog : raw, advance, s));
     // 5. the log-probability of the token just recorded (it reads out_ids / out_len / the advanced step counter), on the raw rows
@@ -1592,8 +1601,9 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
         if (pos[b] + max_new > c->max_ctx) return fail(TRACE_ERR_ARG, "prefill + max_new_tokens exceeds max_ctx");
         for (int b2 = 0; b2 < b; ++b2) if (slots[b2] == slots[b]) return fail(TRACE_ERR_ARG, "duplicate slot");
     }
-    if (forced && c->want.process && !c->host_mode)
-        return fail(TRACE_ERR_ARG, "logits processors (trace_decode_set_logits_params) with forced ids: the history is the recorded ids, not the fed ones");
+    if (forced && (c->want.process || c->want.stop) && !c->host_mode)
+        return fail(TRACE_ERR_ARG, "logits processors / constraints (trace_decode_set_logits_params, trace_decode_set_constraints) with forced ids: the "
+                                   "history is the recorded ids, not the fed ones");
     c->B = B; c->max_new = max_new; c->eos = eos; c->has_forced = forced != nullptr;
     c->sh_slot = sh_rows > 0 ? sh_slot : -1; c->sh_rows = sh_rows;
     c->pos_sum = 0;
@@ -1612,6 +1622,8 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     if (c->armed.sample) HIPCHK(hipMemcpyAsync(c->d_sparams, &c->samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     if (c->armed.logprobs) HIPCHK(hipMemsetAsync(c->d_logprobs, 0, (size_t)B * max_new * 4, s));    // entries past a row's length stay 0.0
     if (c->armed.process) HIPCHK(hipMemcpyAsync(c->d_lgparams, &c->lgp, sizeof(LogitsParams), hipMemcpyHostToDevice, s));
+    if (c->armed.process || c->armed.stop)       // the whole table, or the header alone when it is empty (the processors' kernel reads its four counts)
+        HIPCHK(hipMemcpyAsync(c->d_ctab, &c->ctab, constraints_on(c->ctab) ? sizeof(ConstrainTable) : 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     c->fed = 0; c->steps_done = 0;
     if (forced) HIPCHK(hipMemcpyAsync(c->d_forced, forced, (size_t)B * max_new * 4, hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemsetAsync(c->d_forced, 0xff, (size_t)B * max_new * 4, s));      // -1 = not forced
@@ -1714,8 +1726,15 @@ static SampleParams make_sampling(float T, int k, float p, uint64_t seed) {
 }
 
 // The requested tail mode becomes m, once the buffers it needs exist (allocated on first use): the raw rows for any request, the processed rows,
-// the log-probabilities.  A context that never requests anything allocates none of them.
+// the log-probabilities, the constraint table.  A context that never requests anything allocates none of them.  m.process and m.stop follow from the
+// logits params and the constraint table the context holds: process = any param or any ban rule armed, stop = any stop sequence.
 static int set_want(trace_ctx* c, TailMode m) {
+    m.process = c->lgp.penalty != 1.f || c->lgp.ngram != 0 || c->lgp.min_new != 0 || c->ctab.n_bad || c->ctab.n_suppress || c->ctab.n_begin;
+    m.stop = c->ctab.n_stop != 0;
+    if ((m.process || m.stop) && !c->d_ctab) {
+        TRY(dalloc(c, &c->d_ctab, 1));
+        HIPCHK(hipMemset(c->d_ctab, 0, sizeof(ConstrainTable)));
+    }
     if (m.index() && !c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
     if (m.process && !c->d_plog) TRY(dalloc(c, &c->d_plog, (size_t)SK_ROWS * c->NV));
     if (m.logprobs && !c->d_logprobs) TRY(dalloc(c, &c->d_logprobs, (size_t)SK_ROWS * c->c.max_new_tokens));
@@ -1752,9 +1771,105 @@ extern "C" int trace_decode_set_logits_params(trace_ctx* c, float repetition_pen
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
     if (const char* m = logits_params_bad(repetition_penalty, no_repeat_ngram_size, min_new_tokens)) return fail(TRACE_ERR_ARG, m);
     c->lgp = LogitsParams{repetition_penalty, no_repeat_ngram_size, min_new_tokens};
-    TailMode m = c->want;
-    m.process = repetition_penalty != 1.f || no_repeat_ngram_size != 0 || min_new_tokens != 0;
-    return set_want(c, m);
+    return set_want(c, c->want);
+}
+
+// trace_constraints -> the table, bounded and checked: a message, or null.  NV > 0: every id must lie in [0, NV).
+static const char* constraints_table(const trace_constraints* k, int NV, ConstrainTable& t) {
+    memset(&t, 0, sizeof(t));
+    if (!k) return nullptr;
+    if (k->size < (int32_t)sizeof(trace_constraints)) return "trace_constraints.size is smaller than the struct";
+    if (k->n_stop < 0 || k->n_stop > CONSTRAIN_MAX_SEQS) return "at most 64 stop sequences";
+    if (k->n_bad_words < 0 || k->n_bad_words > CONSTRAIN_MAX_SEQS) return "at most 64 bad-word sequences";
+    if (k->n_suppress < 0 || k->n_suppress > CONSTRAIN_MAX_SUPPRESS || k->n_begin_suppress < 0 || k->n_begin_suppress > CONSTRAIN_MAX_SUPPRESS)
+        return "at most 1024 ids in each suppress list";
+    auto id_ok = [NV](int32_t v) { return v >= 0 && (NV <= 0 || v < NV); };
+    auto csr = [&](int n, const int32_t* off, const int32_t* ids, int32_t* toff, int32_t* tids) -> const char* {
+        if (n == 0) return nullptr;
+        if (!off || !ids) return "null offsets / ids of a sequence list";
+        if (off[0] != 0) return "sequence offsets must start at 0";
+        for (int i = 0; i < n; ++i) {
+            const int len = off[i + 1] - off[i];
+            if (len < 1) return "an empty sequence (or offsets that do not ascend)";
+            if (len > CONSTRAIN_MAX_SEQ_LEN) return "at most 32 ids per sequence";
+        }
+        for (int i = 0; i <= n; ++i) toff[i] = off[i];
+        for (int j = 0; j < off[n]; ++j) {
+            if (!id_ok(ids[j])) return "a sequence id outside the vocabulary";
+            tids[j] = ids[j];
+        }
+        return nullptr;
+    };
+    auto flat = [&](int n, const int32_t* ids, int32_t* tids) -> const char* {
+        if (n == 0) return nullptr;
+        if (!ids) return "null suppress list";
+        for (int j = 0; j < n; ++j) {
+            if (!id_ok(ids[j])) return "a suppressed id outside the vocabulary";
+            tids[j] = ids[j];
+        }
+        return nullptr;
+    };
+    if (const char* m = csr(k->n_stop, k->stop_offsets, k->stop_ids, t.stop_off, t.stop_ids)) return m;
+    if (const char* m = csr(k->n_bad_words, k->bad_word_offsets, k->bad_word_ids, t.bad_off, t.bad_ids)) return m;
+    if (const char* m = flat(k->n_suppress, k->suppress_ids, t.suppress)) return m;
+    if (const char* m = flat(k->n_begin_suppress, k->begin_suppress_ids, t.begin)) return m;
+    t.n_stop = k->n_stop; t.n_bad = k->n_bad_words; t.n_suppress = k->n_suppress; t.n_begin = k->n_begin_suppress;
+    return nullptr;
+}
+
+extern "C" int trace_decode_set_constraints(trace_ctx* c, const trace_constraints* k) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    ConstrainTable t;
+    if (const char* m = constraints_table(k, c->NV, t)) return fail(TRACE_ERR_ARG, m);
+    c->ctab = t;
+    return set_want(c, c->want);
+}
+
+// the loose-row ops' device copy of a table: one buffer per device for the life of the process, rewritten by every call on the call's stream (the
+// stream is drained before the call returns: the host copy is a local, and a later call may rewrite the buffer)
+static int loose_table(const ConstrainTable& t, hipStream_t s, ConstrainTable** out) {
+    static ConstrainTable* d_tab[16] = {nullptr};
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 16) return fail(TRACE_ERR_ARG, "device index out of range");
+    if (!d_tab[dev]) HIPCHK(hipMalloc((void**)&d_tab[dev], sizeof(ConstrainTable)));
+    HIPCHK(hipMemcpyAsync(d_tab[dev], &t, sizeof(ConstrainTable), hipMemcpyHostToDevice, s));
+    *out = d_tab[dev];
+    return TRACE_OK;
+}
+
+extern "C" int trace_op_logits_process_ex(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
+                                          const int32_t* hist_len, const int32_t* steps, int eos, float repetition_penalty, int no_repeat_ngram_size,
+                                          int min_new_tokens, const trace_constraints* constraints, float* out, void* stream) {
+    if (!logits || !heads || !hist || !hist_len || !steps || !out) return fail(TRACE_ERR_ARG, "null pointer");
+    if (out == logits) return fail(TRACE_ERR_ARG, "out may not alias logits");
+    if (const char* m = logits_params_bad(repetition_penalty, no_repeat_ngram_size, min_new_tokens)) return fail(TRACE_ERR_ARG, m);
+    if (V < 1 || Tv < 1 || Sv < 1) return fail(TRACE_ERR_ARG, "bad head widths");
+    ConstrainTable t;
+    if (const char* m = constraints_table(constraints, V + 1 + Tv + Sv, t)) return fail(TRACE_ERR_ARG, m);
+    hipStream_t s = (hipStream_t)stream;
+    ConstrainTable* dt = nullptr;
+    TRY(loose_table(t, s, &dt));
+    const int rc = launch_logits_process(logits, ld, B, heads, V, Tv, Sv, hist, ld_hist, hist_len, steps, eos,
+                                         LogitsParams{repetition_penalty, no_repeat_ngram_size, min_new_tokens}, out, ld, s, dt);
+    HIPCHK(hipStreamSynchronize(s));
+    if (rc != TRACE_OK) return fail(rc, "logits_process launch failed (B, ld, ld_hist or head widths out of range)");
+    return TRACE_OK;
+}
+
+extern "C" int trace_op_stop_match(const int32_t* hist, int ld_hist, const int32_t* hist_len, int B, const trace_constraints* constraints,
+                                   int32_t* fired_out, void* stream) {
+    if (!hist || !hist_len || !fired_out) return fail(TRACE_ERR_ARG, "null pointer");
+    if (B < 1 || B > 65535 || ld_hist < 0) return fail(TRACE_ERR_ARG, "bad B / ld_hist");
+    ConstrainTable t;
+    if (const char* m = constraints_table(constraints, 0, t)) return fail(TRACE_ERR_ARG, m);
+    hipStream_t s = (hipStream_t)stream;
+    ConstrainTable* dt = nullptr;
+    TRY(loose_table(t, s, &dt));
+    const int rc = launch_stop_match(hist, ld_hist, hist_len, B, dt, fired_out, s);
+    HIPCHK(hipStreamSynchronize(s));
+    if (rc != TRACE_OK) return fail(rc, "stop_match launch failed");
+    return TRACE_OK;
 }
 
 extern "C" int trace_op_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,

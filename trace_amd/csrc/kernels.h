@@ -227,9 +227,14 @@ struct StepState {
 // a draw by sample.h's sampler from rows `logits` [B][NV] fp32 (masked, raw or processed) under the device params *sp.  SELECT_ROW: the arg-max
 // over the head's range of such rows, the lowest id among equal maxima as the partials have it (sp null).
 enum { SELECT_TILES = 0, SELECT_SAMPLE = 1, SELECT_ROW = 2 };
+// stop: a device-resident constraint table (constrain.h) whose stop sequences end a row like EOS — the instantiations with the stop match; null: the plain ones.
+struct ConstrainTable; // constrain.h
 int launch_select(int form, const float* part_val, const int32_t* part_idx, const float* logits, const SampleParams* sp, const StepState& st,
                   const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H,
-                  int V, int Tv, int Sv, int advance, hipStream_t s);
+                  int V, int Tv, int Sv, int advance, hipStream_t s, const ConstrainTable* stop = nullptr);
+int launch_select_stop(int form, const float* part_val, const int32_t* part_idx, const float* logits, const SampleParams* sp, const StepState& st,
+                       const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H,
+                       int V, int Tv, int Sv, int advance, hipStream_t s, const ConstrainTable* ct);      // (constrain.hip; launch_select routes to it)
 // SELECT_SAMPLE's sampler as the same device code for loose rows (trace_op_sample): logits [B][ld] fp32, heads / steps int32 [B] (device) ->
 // out_ids [B] global ids
 int launch_sample_rows(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const SampleParams& sp, const int32_t* steps,
@@ -254,10 +259,16 @@ int launch_score_rows(const bf16_t* X, int ld, const bf16_t* W, int ldw, int K, 
 // Loose rows: hist int32 [B][ld_hist] / hist_len / heads / steps int32 [B] (device), out [B][ldo] written whole, -inf outside the head
 // (trace_op_logits_process).  Decode step: between launch_head_logits and the selection of the same step, history = st.out_ids / st.out_len,
 // params *dlp (device), rows [B][NV] -> [B][NV] (the head's range only), which launch_select's SELECT_SAMPLE / SELECT_ROW forms then read.
+// ct: the device-resident constraint table (constrain.h) whose ban rules follow the three processors in the same launch — bad words, suppress,
+// begin-suppress, and min_new_tokens over every stop sequence of one id; null = none (loose rows only: the step always passes the context's table).
+// launch_stop_match: the stop rule over loose histories, fired int32 [B] device = 1 where a stop sequence equals the tail of hist[b][0 .. hist_len[b]).
 struct LogitsParams;   // logits.h
 int launch_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
-                          const int32_t* hist_len, const int32_t* steps, int eos, const LogitsParams& lp, float* out, int ldo, hipStream_t s);
-int launch_step_logits_process(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, const LogitsParams* dlp, float* out, hipStream_t s);
+                          const int32_t* hist_len, const int32_t* steps, int eos, const LogitsParams& lp, float* out, int ldo, hipStream_t s,
+                          const ConstrainTable* ct = nullptr);
+int launch_step_logits_process(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, const LogitsParams* dlp, float* out, hipStream_t s,
+                               const ConstrainTable* ct);
+int launch_stop_match(const int32_t* hist, int ld_hist, const int32_t* hist_len, int B, const ConstrainTable* ct, int32_t* fired, hipStream_t s);
 
 // ---- fp8 (e4m3) weight path of the decoder (fp8.hip; the fp8 GEMM is launch_gemm_bf16 with GemmArgs::fp8 set) ----
 // X bf16 [rows][K] -> X8 e4m3 [rows][K] + sx[row] = amax/448 (per-row dynamic scale).  Also used row-wise on weight matrices at load.

@@ -8,12 +8,16 @@
 //      y[h[i + n - 1]] = -inf (n = 1: every id of h);
 //   3. min_new_tokens m: while s < m and eos lies in [lo, hi): y[eos] = -inf.
 // Ids of h outside [lo, hi) touch nothing.  The three rules commute: 1 writes finite-or-unchanged values first, 2 and 3 only store -inf afterwards.
+// Given a constraint table (constrain.h), its ban rules follow rule 2 behind the same barrier: 4 bad words, 5 suppress, 6 begin-suppress, and rule 3
+// over every stop sequence of one id as well (HF bans every id of its EOS list).  They too only store -inf.
 // One workgroup of 256 threads per row.  Rule 1 claims an id in a seen-bitmap in LDS (ceil((hi - lo) / 32) words of dynamic LDS) with a
 // workgroup-scope atomic OR; only the thread that flips the bit writes, so no value is written twice and nothing on the row is read-modify-written.
 // trace_amd/sampling.py process_row_ref restates it in float32 numpy bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "constrain.h"
 
 struct LogitsParams {            // device-resident next to SampleParams (a captured graph reads them at replay)
     float penalty;               // > 0, 1 = off
@@ -24,9 +28,11 @@ constexpr int LOGITS_THREADS = 256;
 constexpr int LOGITS_MAX_NGRAM = 64;
 
 // src / dst: the head's range of the raw and of the processed row (dst != src), n = hi - lo; h: the row's history, L ids; seen: (n + 31) / 32
-// words of LDS, suffix: LOGITS_MAX_NGRAM ints of LDS.  Every branch on lp / L / step is uniform over the workgroup.
+// words of LDS, suffix: LOGITS_MAX_NGRAM ints of LDS.  ct: the constraint table whose ban rules (constrain.h, rules 4 - 6 and rule 3 for every stop
+// sequence of one id) follow rule 2 behind the same barrier, or null.  Every branch on lp / L / step / ct is uniform over the workgroup.
 __device__ inline void logits_process_row(const float* __restrict__ src, float* __restrict__ dst, int lo, int n, const int32_t* __restrict__ h, int L,
-                                          const LogitsParams lp, int step, int eos, uint32_t* seen, int32_t* suffix) {
+                                          const LogitsParams lp, int step, int eos, uint32_t* seen, int32_t* suffix,
+                                          const ConstrainTable* __restrict__ ct = nullptr) {
     const int tid = threadIdx.x;
     // ---- the copy: scalars up to the source's first 16-byte boundary, then float4 loads (and float4 stores where the destination is aligned alike)
     const int lead = min(n, (int)(((16u - (uint32_t)((uintptr_t)src & 15u)) & 15u) >> 2));
@@ -77,4 +83,5 @@ __device__ inline void logits_process_row(const float* __restrict__ src, float* 
         }
     }
     if (tid == 0 && step < lp.min_new && eos >= lo && eos - lo < n) dst[eos - lo] = -INFINITY;
+    if (ct) constrain_ban_row(dst, lo, n, h, L, ct, step, lp.min_new);
 }

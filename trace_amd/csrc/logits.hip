@@ -1,6 +1,7 @@
 // logits_process_kernel: the logits processors (logits.h) as a launch between head_logits_kernel and select_next_kernel, and over loose rows
 // (trace_op_logits_process: the unit tests and the host-driven decode loop) — the same device code.  The tile partials of head_logits_kernel
 // describe the raw row, so a greedy step with processors takes its arg-max from the processed one: select_next_kernel<SELECT_ROW> (select.hip).
+// The ban rules of constrain.h ride in the same kernel (a device-resident table, or none).
 #include <algorithm>
 
 #include "common.h"
@@ -20,7 +21,7 @@ __global__ __launch_bounds__(LOGITS_THREADS) void logits_process_kernel(const fl
                                                                         const int32_t* __restrict__ hist_len, const int32_t* __restrict__ steps,
                                                                         int eos, LogitsParams lpv, const int32_t* __restrict__ dparams,
                                                                         const LogitsParams* __restrict__ dlp, float* __restrict__ out, int ldo,
-                                                                        int seen_words) {
+                                                                        int seen_words, const ConstrainTable* __restrict__ ct) {
     extern __shared__ __attribute__((aligned(16))) uint32_t seen[];
     __shared__ int32_t suffix[LOGITS_MAX_NGRAM];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(LOGITS_THREADS) void logits_process_kernel(const fl
         for (int i = tid; i < lo; i += LOGITS_THREADS) orow[i] = -INFINITY;
         for (int i = hi + tid; i < NV; i += LOGITS_THREADS) orow[i] = -INFINITY;
     }
-    logits_process_row(logits + (size_t)b * ld + lo, orow + lo, lo, hi - lo, hist + (size_t)b * ld_hist, L, lp, step, eos, seen, suffix);
+    logits_process_row(logits + (size_t)b * ld + lo, orow + lo, lo, hi - lo, hist + (size_t)b * ld_hist, L, lp, step, eos, seen, suffix, ct);
 }
 
 int seen_bytes(int V, int Tv, int Sv) { return (std::max(V + 1, std::max(Tv, Sv)) + 31) / 32 * 4; }
@@ -46,21 +47,23 @@ int seen_bytes(int V, int Tv, int Sv) { return (std::max(V + 1, std::max(Tv, Sv)
 }  // namespace
 
 int launch_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
-                          const int32_t* hist_len, const int32_t* steps, int eos, const LogitsParams& lp, float* out, int ldo, hipStream_t s) {
+                          const int32_t* hist_len, const int32_t* steps, int eos, const LogitsParams& lp, float* out, int ldo, hipStream_t s,
+                          const ConstrainTable* ct) {
     const int NV = V + 1 + Tv + Sv;
     if (B < 1 || B > 65535 || ld < NV || ldo < NV || ld_hist < 0 || V < 1 || Tv < 1 || Sv < 1) return TRACE_ERR_ARG;
     const int lds = seen_bytes(V, Tv, Sv);
     if (lds > 32768) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(LOGITS_THREADS), lds, s, logits, ld, heads, V, Tv, Sv, hist, ld_hist, hist_len, steps, eos, lp,
-                       nullptr, nullptr, out, ldo, lds / 4);
+                       nullptr, nullptr, out, ldo, lds / 4, ct);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
 
-int launch_step_logits_process(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, const LogitsParams* dlp, float* out, hipStream_t s) {
-    if (B < 1 || B > SK_ROWS || !logits || !out || !dlp) return TRACE_ERR_ARG;
+int launch_step_logits_process(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, const LogitsParams* dlp, float* out, hipStream_t s,
+                               const ConstrainTable* ct) {
+    if (B < 1 || B > SK_ROWS || !logits || !out || !dlp || !ct) return TRACE_ERR_ARG;
     const int NV = V + 1 + Tv + Sv, lds = seen_bytes(V, Tv, Sv);
     if (lds > 32768) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(LOGITS_THREADS), lds, s, logits, NV, st.heads, V, Tv, Sv, st.out_ids, 0, st.out_len, st.step, -1,
-                       LogitsParams{1.f, 0, 0}, st.params, dlp, out, NV, lds / 4);
+                       LogitsParams{1.f, 0, 0}, st.params, dlp, out, NV, lds / 4, ct);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

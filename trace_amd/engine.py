@@ -13,7 +13,7 @@ from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
 from .prefix import APPEND_GROUP_MAX, SHARE_PREFIX_MIN_BATCH, group_by_length, shared_prefix_len, split_questions
-from .sampling import LogitsParams, SamplingParams, argmax_rows, sample_rows_host
+from .sampling import Constraints, LogitsParams, SamplingParams, argmax_rows, check_constraints, ends_stopped, sample_rows_host
 from . import scoring
 
 __all__ = ["TraceEngine", "SamplingParams", "ops"]
@@ -590,6 +590,25 @@ class TraceEngine:
         return ops.logits_process(logits, heads, hist, params, steps, eos, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size,
                                   element=_lib.element_of(self.dtype))
 
+    def set_constraints(self, constraints: Optional[Constraints]):
+        """Bad words, suppressed ids and stop sequences for the decode batches begun from now on (trace_decode_set_constraints, csrc/constrain.h):
+        the bans join the logits processors' launch, the stop sequences end a row inside the selection as EOS does.  None or Constraints()
+        disarms them.  ValueError for an id outside the vocabulary or a list beyond the device's bounds."""
+        if constraints is None or constraints.off:
+            _lib.check(self.lib.trace_decode_set_constraints(self.h, None))
+            return
+        k, keep = constraints_c(constraints, self.cfg.total_vocab)
+        _lib.check(self.lib.trace_decode_set_constraints(self.h, C.byref(k)))
+        del keep
+
+    def logits_process_ex(self, logits: torch.Tensor, heads: Sequence[int], hist: Sequence[Sequence[int]], params: Optional[LogitsParams],
+                          steps: Sequence[int], eos: int = -1, constraints: Optional[Constraints] = None) -> torch.Tensor:
+        """logits_process with the ban rules of `constraints` behind the processors (trace_op_logits_process_ex: the device code of the decode step;
+        sampling.constrain_row_ref of sampling.process_row_ref)."""
+        cfg = self.cfg
+        return ops.logits_process_ex(logits, heads, hist, params, steps, eos, constraints, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size,
+                                     element=_lib.element_of(self.dtype))
+
     def sample(self, logits: torch.Tensor, heads: Sequence[int], sampling: SamplingParams, steps: Sequence[int]) -> List[int]:
         """One id per row of masked logits [B, NV] fp32 (device), drawn as a decode step draws them (row b: Philox step steps[b], row index b):
         the device sampler (trace_op_sample) inside its domain, the host statement of the same rules outside it."""
@@ -716,8 +735,10 @@ class TraceEngine:
 
     def decode(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
                forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-               logits: Optional[LogitsParams] = None, shared_prefix=None):
+               logits: Optional[LogitsParams] = None, shared_prefix=None, constraints: Optional[Constraints] = None):
         """Stage 2 of generate(): the decode loop over prefilled KV slots, on the current stream -> (ids per sequence, final heads).
+        constraints: bad words / suppressed ids / stop sequences (Constraints; None or all off = today's launches and graphs), inside the decode
+        step like `logits` (set_constraints); not together with forced ids.
         shared_prefix: what encode_prefill returned for these slots (decode_begin: the attention reads the shared rows from one slot; same results).
         logits: repetition penalty / no-repeat n-grams / min_new_tokens (LogitsParams; None or all off = today's launches and graphs), applied
         inside the decode step to the ids each row has generated so far (set_logits_params); not together with forced ids.
@@ -726,10 +747,16 @@ class TraceEngine:
         logprobs: the result gains a third element, one float32 array per row as long as that row's ids: the log-probability of every emitted
         token under the model's own (unwarped) distribution, computed inside the decode step (trace_decode_set_logprobs)."""
         armed = logits is not None and not logits.off
-        if armed and forced is not None:
-            raise ValueError("logits processors act on the ids a row has recorded; under forced ids those are not the fed ones (forced= with logits=)")
+        bound = constraints is not None and not constraints.off
+        if (armed or bound) and forced is not None:
+            raise ValueError("logits processors and constraints act on the ids a row has recorded; under forced ids those are not the fed ones "
+                             "(forced= with logits= / constraints=)")
+        if bound:
+            check_constraints(constraints.stop_sequences, constraints.bad_words_ids, constraints.suppress_tokens, constraints.begin_suppress_tokens,
+                              self.cfg.total_vocab)
         if sampling is not None and not sampling.greedy and not sampling.on_device:
-            return self.decode_stepwise(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits, shared_prefix=shared_prefix)
+            return self.decode_stepwise(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits, shared_prefix=shared_prefix,
+                                        constraints=constraints)
         on_dev = sampling is not None and not sampling.greedy
         if on_dev:
             self.set_sampling(sampling)
@@ -738,8 +765,12 @@ class TraceEngine:
         if armed:
             self.set_logits_params(logits)
         try:
-            return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs, shared_prefix)
+            if bound:
+                self.set_constraints(constraints)
+            return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs, shared_prefix, constraints if bound else None)
         finally:
+            if bound:
+                self.set_constraints(None)
             if armed:
                 self.set_logits_params(None)
             if logprobs:
@@ -749,12 +780,14 @@ class TraceEngine:
 
     def decode_stepwise(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1,
                         forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-                        logits: Optional[LogitsParams] = None, stopping=None, shared_prefix=None):
+                        logits: Optional[LogitsParams] = None, stopping=None, shared_prefix=None, constraints: Optional[Constraints] = None):
         """decode() one eager step at a time with the token picked on the host: the one loop in host-select mode (sampling parameters outside the
         device sampler's domain, stopping criteria).  Every rule is the device step's.  The row the pick reads is the processed one
         (logits_process: the history is the ids recorded so far) when `logits` is armed, else the raw one; sampled rows go through sample(),
         greedy rows take the lowest id among equal maxima of the head's range; a forced id overrides the pick; the log-probability is the fed
-        token's on the raw row.  A row is finished when its recorded ids end in `eos` or `stopping` fired for it - stopping(ids per row) ->
+        token's on the raw row.  `constraints`: the ban rules ride behind the processors in the same loose-row op (logits_process_ex), and a row
+        whose ids end in a stop sequence is finished as the device step finishes it (sampling.ends_stopped): it keeps the ids it held then, and the
+        history its later picks see is that.  A row is finished when its recorded ids end in `eos` or `stopping` fired for it - stopping(ids per row) ->
         one bool per row, asked after every step but the last while some row is unfinished; a row it fired for keeps the ids (and log-probabilities) it held then,
         while its returned head is the whole run's: the device goes on feeding it, as it does a row past its EOS.  The greedy pick is taken on the
         device (sampling.argmax_rows: B ids come back); the recorded ids are read back after every step, since both finished rules look at them.  The
@@ -762,6 +795,9 @@ class TraceEngine:
         B, cfg = len(slots), self.cfg
         greedy = sampling is None or sampling.greedy
         armed = logits is not None and not logits.off
+        bound = constraints is not None and not constraints.off
+        if bound and forced is not None:
+            raise ValueError("constraints act on the ids a row has recorded; under forced ids those are not the fed ones (forced= with constraints=)")
         self.host_mode(True)
         try:
             raw = self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, want_logits=True, shared_prefix=shared_prefix)
@@ -769,7 +805,11 @@ class TraceEngine:
             lp = np.zeros((B, max_new_tokens), np.float32)
             stopped = [None] * B                          # the length at which `stopping` fired for the row
             for step in range(max_new_tokens):
-                rows = self.logits_process(raw, cur, ids, logits, [step] * B, eos) if armed else raw
+                if bound:
+                    hist = [x if n is None else x[:n] for x, n in zip(ids, stopped)]
+                    rows = self.logits_process_ex(raw, cur, hist, logits, [step] * B, eos, constraints)
+                else:
+                    rows = self.logits_process(raw, cur, ids, logits, [step] * B, eos) if armed else raw
                 if greedy:
                     tok = argmax_rows(rows, cur, cfg.vocab_size, cfg.time_vocab_size, cfg.score_vocab_size)
                 else:
@@ -783,9 +823,11 @@ class TraceEngine:
                     for b in range(B):
                         if len(ids[b]) == step + 1:
                             lp[b, step] = val[b]
+                if bound:                                 # (the device records on in host-select mode: the length at which the stop rule fired is kept here)
+                    stopped = [len(x) if n is None and ends_stopped(x, -1, constraints) else n for x, n in zip(ids, stopped)]
                 if step == max_new_tokens - 1:
                     break
-                done = [eos >= 0 and len(x) > 0 and x[-1] == eos for x in ids]
+                done = [ends_stopped(x, eos) for x in ids]
                 if stopping is not None and not all(done):
                     stopped = [len(x) if n is None and f else n for x, n, f in zip(ids, stopped, stopping(ids))]
                 if all(d or n is not None for d, n in zip(done, stopped)):
@@ -796,10 +838,10 @@ class TraceEngine:
         finally:
             self.host_mode(False)
 
-    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False, shared_prefix=None):
+    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False, shared_prefix=None, constraints=None):
         self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, shared_prefix=shared_prefix)
         if max_new_tokens > 1:
-            if eos < 0:
+            if eos < 0 and not (constraints is not None and constraints.stop_sequences):
                 self.decode_steps(max_new_tokens - 1, use_graph)
             else:
                 done, chunk = 0, 32
@@ -808,7 +850,7 @@ class TraceEngine:
                     self.decode_steps(n, use_graph)
                     done += n
                     ids, _ = self.decode_read()
-                    if all(len(x) and x[-1] == eos for x in ids):
+                    if all(ends_stopped(x, eos, constraints) for x in ids):
                         break
         ids, hd = self.decode_read()
         return (ids, hd, self.decode_read_logprobs([len(x) for x in ids])) if logprobs else (ids, hd)
@@ -816,15 +858,17 @@ class TraceEngine:
     def generate(self, videos: Sequence[torch.Tensor], timestamps: Sequence, input_ids: Sequence[Sequence[int]],
                  heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
                  forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-                 logits: Optional[LogitsParams] = None):
+                 logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None):
         B = len(videos)
         if B > self.decode_batch_max:
             raise ValueError(f"batch {B} exceeds the engine's decode batch {self.decode_batch_max}")
         shared = self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
-        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits, shared_prefix=shared)
+        return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits, shared_prefix=shared,
+                           constraints=constraints)
 
     def generate_samples(self, video: torch.Tensor, timestamps, prompt_ids: Sequence[int], head: int, n: int, max_new_tokens: int, eos: int = -1,
-                         sampling: Optional[SamplingParams] = None, use_graph: bool = True, logits: Optional[LogitsParams] = None):
+                         sampling: Optional[SamplingParams] = None, use_graph: bool = True, logits: Optional[LogitsParams] = None,
+                         constraints: Optional[Constraints] = None):
         """n sampled continuations of ONE prompt from one tower pass and one prefill: the prompt is encoded and prefilled into KV slot 0, its rows
         are copied to slots 1 .. n - 1 (kv_copy), and slots 0 .. n - 1 decode as one batch with log-probabilities on.  Row r draws with Philox
         row index r, as any decode batch does, so the result equals generate() of the prompt repeated n times with the same SamplingParams:
@@ -838,12 +882,12 @@ class TraceEngine:
         self.prefill(0, L)
         if n > 1:
             self.kv_copy(0, list(range(1, n)), L)
-        return self.decode(range(n), [int(head)] * n, max_new_tokens, eos, use_graph, None, sampling, logprobs=True, logits=logits)
+        return self.decode(range(n), [int(head)] * n, max_new_tokens, eos, use_graph, None, sampling, logprobs=True, logits=logits, constraints=constraints)
 
     def generate_questions(self, video: torch.Tensor, timestamps, prompts: Sequence[Sequence[int]], heads: Sequence[int], max_new_tokens: int,
                            eos: int = -1, sampling: Optional[SamplingParams] = None, use_graph: bool = True,
                            forced: Optional[Sequence[Sequence[int]]] = None, prefix_key=None, logprobs: bool = False,
-                           logits: Optional[LogitsParams] = None):
+                           logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None):
         """generate() for Q prompts about ONE video whose ids agree up to and including the <video> placeholder (the reference's per-question
         loops, trace/eval/videomme/evaluate.py:349-386): the tower, the slot pool and the prefill of the common prefix run once (slot 0), the
         prefix's KV rows are copied to the other Q - 1 slots, each prompt's rows after <video> are appended (one pass per group of equal
@@ -874,7 +918,7 @@ class TraceEngine:
                     slot += 1
         if prefix_key is not None:
             self.set_prefix_entry(prefix_key, P)
-        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits)
+        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits, constraints=constraints)
 
     # ---- two-stage pipeline over a stream of batches ---------------------------------------------------
     def make_streams(self, decode_cus: int = 0):
@@ -895,11 +939,12 @@ class TraceEngine:
         return enc, dec
 
     def generate_stream(self, batches: Iterable, max_new_tokens: int, eos: int = -1, use_graph: bool = True, streams=None,
-                        sampling: Optional[SamplingParams] = None, logprobs: bool = False, logits: Optional[LogitsParams] = None):
+                        sampling: Optional[SamplingParams] = None, logprobs: bool = False, logits: Optional[LogitsParams] = None,
+                        constraints: Optional[Constraints] = None):
         """generate() over a stream of batches as a two-stage pipeline: while batch k decodes (HBM-bound) on one stream, batch k+1
         runs its ViT + slot pool + prefill (MFMA-bound) on another, into the other half of the KV slots.  `batches` yields
         (videos, timestamps, input_ids, heads, forced-or-None); yields generate()'s result per batch, in order.  Every batch holds at
-        most max_batch // 2 videos.  sampling / logits: as decode(), the same params (and seed) for every batch.  Results are identical to generate() batch by batch: the stages share no buffers (KV banks,
+        most max_batch // 2 videos.  sampling / logits / constraints: as decode(), the same params (and seed) for every batch.  Results are identical to generate() batch by batch: the stages share no buffers (KV banks,
         prefill / ViT scratch vs decode scratch) and every kernel's reductions have a fixed order.
 
         The decode stage is issued from a worker thread: one decode batch is ~75 k kernel dispatches, far more than a HIP stream's
@@ -919,7 +964,7 @@ class TraceEngine:
                 dec_s.wait_event(ready)
                 # (logprobs: read inside this job, right after the ids — decode() returns them, nothing goes through engine state afterwards)
                 return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs,
-                                   logits=logits, shared_prefix=shared)
+                                   logits=logits, shared_prefix=shared, constraints=constraints)
 
         pending = None                                  # (bank, heads, forced, B, ready event, shared prefix): prefilled, waiting for its decode
         bank = 0
@@ -955,6 +1000,32 @@ class TraceEngine:
                     yield out
         finally:
             brackets(3)
+
+
+def _hist_tensors(hist, B, dev):
+    """one history per row -> (int32 [B, ld] device, ld, int32 [B] lengths device)"""
+    if len(hist) != B:
+        raise ValueError("one history per row")
+    ldh = max(1, max(len(h) for h in hist))
+    hh = torch.tensor([[int(t) for t in h] + [0] * (ldh - len(h)) for h in hist], dtype=torch.int32, device=dev)
+    return hh, ldh, torch.tensor([len(h) for h in hist], dtype=torch.int32, device=dev)
+
+
+def constraints_c(constraints: Constraints, n_vocab):
+    """(trace_constraints for the C ABI, the numpy arrays its pointers look into - keep them until the call has returned); ValueError first"""
+    check_constraints(constraints.stop_sequences, constraints.bad_words_ids, constraints.suppress_tokens, constraints.begin_suppress_tokens, n_vocab)
+
+    def csr(seqs):
+        off = np.cumsum([0] + [len(w) for w in seqs], dtype=np.int64).astype(np.int32)
+        return off, np.array([t for w in seqs for t in w], dtype=np.int32)
+    so, si = csr(constraints.stop_sequences)
+    bo, bi = csr(constraints.bad_words_ids)
+    su, bg = np.array(constraints.suppress_tokens, dtype=np.int32), np.array(constraints.begin_suppress_tokens, dtype=np.int32)
+    keep = (so, si, bo, bi, su, bg)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    k = _lib.TraceConstraintsC(C.sizeof(_lib.TraceConstraintsC), len(constraints.stop_sequences), len(constraints.bad_words_ids), len(su), len(bg),
+                               ptr(so), ptr(si), ptr(bo), ptr(bi), ptr(su), ptr(bg))
+    return k, keep
 
 
 # ---- kernel-level wrappers for unit tests / microbenchmarks -------------------------------------
@@ -1005,6 +1076,42 @@ class ops:
         _lib.check(lib.trace_op_logits_process(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, _ptr(hh), ldh, _ptr(hl), _ptr(st), int(eos),
                                                float(params.repetition_penalty), int(params.no_repeat_ngram_size), int(params.min_new_tokens),
                                                _ptr(out), _stream()))
+        return out
+
+    @staticmethod
+    def logits_process_ex(logits, heads, hist, params: Optional[LogitsParams], steps, eos: int, constraints: Optional[Constraints], V: int, Tv: int,
+                          Sv: int, element=None):
+        """trace_op_logits_process_ex: ops.logits_process (params None = all three off) with the ban rules of `constraints` (None = none) behind
+        the processors - bad words, suppress, begin-suppress, min_new_tokens over every stop sequence of one id: sampling.constrain_row_ref of
+        sampling.process_row_ref, bit for bit.  ValueError for ids outside [0, V+1+Tv+Sv) or lists beyond the device's bounds."""
+        lib = _lib.load(element or ops.element)
+        params = params if params is not None else LogitsParams()
+        lg = logits.contiguous()
+        B, ld = lg.shape
+        dev = lg.device
+        hd = heads if isinstance(heads, torch.Tensor) else torch.tensor([int(h) for h in heads], dtype=torch.int32, device=dev)
+        st = steps if isinstance(steps, torch.Tensor) else torch.tensor([int(x) for x in steps], dtype=torch.int32, device=dev)
+        hh, ldh, hl = _hist_tensors(hist, B, dev)
+        k, keep = (None, None) if constraints is None or constraints.off else constraints_c(constraints, V + 1 + Tv + Sv)
+        out = torch.empty_like(lg) if ld == V + 1 + Tv + Sv else torch.full_like(lg, float("-inf"))      # (the op writes columns [0, V+1+Tv+Sv))
+        _lib.check(lib.trace_op_logits_process_ex(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, _ptr(hh), ldh, _ptr(hl), _ptr(st), int(eos),
+                                                  float(params.repetition_penalty), int(params.no_repeat_ngram_size), int(params.min_new_tokens),
+                                                  None if k is None else C.byref(k), _ptr(out), _stream()))
+        del keep
+        return out
+
+    @staticmethod
+    def stop_match(hist, constraints: Constraints, element=None):
+        """trace_op_stop_match: one history per row (a sequence of id sequences, any lengths) -> int32 [B] (device): 1 where a stop sequence of
+        `constraints` equals the last ids of the row's history (sampling.stop_match_ref), else 0."""
+        lib = _lib.load(element or ops.element)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        B = len(hist)
+        hh, ldh, hl = _hist_tensors(hist, B, dev)
+        k, keep = constraints_c(constraints, None)
+        out = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(lib.trace_op_stop_match(_ptr(hh), ldh, _ptr(hl), B, C.byref(k), _ptr(out), _stream()))
+        del keep
         return out
 
     @staticmethod

@@ -239,3 +239,11 @@ class KeywordsStoppingCriteria:
 
     def __call__(self, output_ids, scores=None, **kwargs) -> bool:
         return all(self.call_for_batch(output_ids[i].unsqueeze(0), scores) for i in range(output_ids.shape[0]))
+
+
+def stop_sequences_from_keywords(criteria) -> list:
+    """The keyword ids of a KeywordsStoppingCriteria as lists: generate(stop_sequences=stop_sequences_from_keywords(c)) ends a row on the device when
+    its generated ids end in one of them - the id half of generate(stopping_criteria=[c]), without the host loop.  The criterion's other half, the
+    keyword found inside the decoded text of the last tokens, has no id-level counterpart and is not reproduced; and the criterion drops time and
+    score ids before it compares, while a stop sequence is matched against the row's ids as they are."""
+    return [[int(t) for t in (k.tolist() if hasattr(k, "tolist") else k)] for k in criteria.keyword_ids]

@@ -136,13 +136,15 @@ def load_tokenizer(model_path: str, cfg: TraceConfig, **kwargs):
 
 def apply_generation_config(model, model_path: str) -> None:
     """from_pretrained reads the checkpoint's generation_config.json (when present) into the model's generate() defaults; the sampling keys
-    this build acts on are do_sample / temperature / top_k / top_p and repetition_penalty / no_repeat_ngram_size / min_new_tokens."""
+    this build acts on are do_sample / temperature / top_k / top_p, repetition_penalty / no_repeat_ngram_size / min_new_tokens, and eos_token_id (an int
+    or a list of ids) / bad_words_ids / suppress_tokens / begin_suppress_tokens / stop_sequences."""
     fn = os.path.join(model_path, "generation_config.json")
     if not os.path.exists(fn):
         return
     with open(fn) as f:
         gc = json.load(f)
-    for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"):
+    for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "eos_token_id",
+              "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "stop_sequences"):
         if gc.get(k) is not None:
             setattr(model.generation_config, k, gc[k])
 

@@ -15,7 +15,7 @@ from .. import scoring
 from ..config import TraceConfig
 from ..constants import MMODAL_TOKEN_INDEX, NUM_FRAMES
 from ..prefix import split_questions
-from ..sampling import LogitsParams, SamplingParams, check_sampling
+from ..sampling import Constraints, LogitsParams, SamplingParams, check_constraints, check_sampling
 from .encoders import NumberTokenizer, ScoreTower, TimeTower
 
 
@@ -163,13 +163,18 @@ class TraceMistralForCausalLM:
     def generate(self, inputs=None, images_or_videos=None, times=None, scores=None, video_timestamps=None,
                  modal_list=None, heads=None, max_new_tokens: int = 128, do_sample: Optional[bool] = None,
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None, generation_config=None,
-                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, stopping_criteria=None,
+                 eos_token_id=None, pad_token_id: Optional[int] = None, stopping_criteria=None,
                  use_cache: bool = True, attention_mask=None, position_ids=None, output_logprobs: bool = False, **kwargs):
         """do_sample / temperature / top_k / top_p: explicit values, else `generation_config`'s, else this model's defaults (HF's: greedy,
         1.0, 50, 1.0, or the checkpoint's generation_config.json).  repetition_penalty / no_repeat_ngram_size / min_new_tokens: the same
         precedence; HF's processors in HF's order on the device, inside the decode step (trace_amd/csrc/logits.h).  Their history is the ids a row
         has generated so far, never the prompt (the reference hands HF inputs_embeds), as global vocabulary ids: a time or score digit emitted
-        earlier counts in a later span too.  Log-probabilities keep describing the raw, unprocessed distribution.  Sampling follows HF's warpers (temperature -> top_k -> top_p ->
+        earlier counts in a later span too.  Log-probabilities keep describing the raw, unprocessed distribution.
+        eos_token_id: an int or a list (HF's); the first id is the engine's eos, the others end a row the same way as stop sequences of one id.
+        bad_words_ids / suppress_tokens / begin_suppress_tokens (HF's NoBadWords / SuppressTokens / SuppressTokensAtBegin processors) and
+        stop_sequences (lists of global ids: a row ends once its generated ids end in one, the ids stay in the output): the same precedence, on
+        the device inside the decode step (trace_amd/csrc/constrain.h) - no host loop.  stopping_criteria= still runs the host loop;
+        mm_utils.stop_sequences_from_keywords(criterion) gives a KeywordsStoppingCriteria's ids for stop_sequences=.  Sampling follows HF's warpers (temperature -> top_k -> top_p ->
         multinomial) on the device (trace_amd/csrc/sample.h); the 64-bit seed is drawn from torch's default generator, so torch.manual_seed
         makes a call reproducible.  temperature == 0 or do_sample=False: greedy.
         output_logprobs=True: instead of the id tensor, an object with `.sequences` (exactly that tensor), `.logprobs` (float32 [B, n], zero
@@ -180,7 +185,10 @@ class TraceMistralForCausalLM:
         lgp = self._logits_params(kwargs.pop("repetition_penalty", None), kwargs.pop("no_repeat_ngram_size", None), kwargs.pop("min_new_tokens", None),
                                   generation_config)
         sampling = self._sampling_params(do_sample, temperature, top_k, top_p, _ProcessorsOff(generation_config, self.generation_config), kwargs)
+        eos, cons = self._eos_and_constraints(eos_token_id, kwargs, generation_config)
         lg = {} if lgp is None else {"logits": lgp}              # handed on only when armed
+        if cons is not None:
+            lg["constraints"] = cons
         if images_or_videos is None:
             raise NotImplementedError("text-only generation is outside the accelerated path")
         cfg, eng = self.config, self.engine
@@ -200,7 +208,6 @@ class TraceMistralForCausalLM:
             raise ValueError("video_timestamps is required on the TRACE path (time tokens per frame)")
         modals = list(modal_list or ["video"] * B)
         vids = [self._as_frames(x, modal) for x, modal in zip(images_or_videos, modals)]
-        eos = self._eos(eos_token_id)
         id_lists = [row.tolist() for row in ids]
         if B > eng.max_batch:
             raise ValueError(f"batch {B} exceeds the engine's max_batch {eng.max_batch}")
@@ -220,7 +227,7 @@ class TraceMistralForCausalLM:
                                                                             sampling=sampling, logprobs=output_logprobs, **lg)
         else:
             out, new_heads, *lps = self._generate_stepwise(vids, video_timestamps, id_lists, list(heads), max_new_tokens, eos,
-                                                           sampling, stopping_criteria, output_logprobs, lgp)
+                                                           sampling, stopping_criteria, output_logprobs, lgp, cons)
         for b in range(B):                       # the reference mutates `heads` in place (trace_mistral.py:342)
             heads[b] = int(new_heads[b])
         res, lp = self._padded(out, lps[0] if output_logprobs else None, eos if pad_token_id is None else pad_token_id)
@@ -231,7 +238,7 @@ class TraceMistralForCausalLM:
     @torch.no_grad()
     def generate_samples(self, inputs=None, images_or_videos=None, video_timestamps=None, n: int = 1, heads=None, max_new_tokens: int = 128,
                          temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None, generation_config=None,
-                         eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, modal_list=None, best_first: bool = True, **kwargs):
+                         eos_token_id=None, pad_token_id: Optional[int] = None, modal_list=None, best_first: bool = True, **kwargs):
         """n sampled continuations of ONE prompt, ranked: the tower, the slot pool and the prefill run once (TraceEngine.generate_samples), the n
         rows decode as one batch with per-token log-probabilities.  Sampling arguments as generate(do_sample=True) (the seed comes from
         torch's default generator the same way); greedy parameters are a ValueError.  Returns `.sequences` [n, len] (padded as generate()),
@@ -250,6 +257,7 @@ class TraceMistralForCausalLM:
         lgp = self._logits_params(kwargs.pop("repetition_penalty", None), kwargs.pop("no_repeat_ngram_size", None), kwargs.pop("min_new_tokens", None),
                                   generation_config)
         sampling = self._sampling_params(True, temperature, top_k, top_p, _ProcessorsOff(generation_config, self.generation_config), kwargs)
+        eos, cons = self._eos_and_constraints(eos_token_id, kwargs, generation_config)
         if sampling is None:
             raise ValueError("generate_samples needs temperature > 0: greedy rows would all be identical")
         eng = self.engine
@@ -257,9 +265,8 @@ class TraceMistralForCausalLM:
         eng.host_mode(False)
         self._live_kv = None
         x = self._as_frames(images_or_videos[0], (modal_list or ["video"])[0])
-        eos = self._eos(eos_token_id)
         out, new_heads, lps = eng.generate_samples(x, video_timestamps[0], ids[0].tolist(), head, n, max_new_tokens, eos=eos, sampling=sampling,
-                                                   **({} if lgp is None else {"logits": lgp}))
+                                                   **({} if lgp is None else {"logits": lgp}), **({} if cons is None else {"constraints": cons}))
         scores = np.array([np.sum(np.asarray(r, np.float32), dtype=np.float64) for r in lps], np.float64)
         order = rank_samples(scores) if best_first else list(range(n))
         seq, lp = self._padded([out[r] for r in order], [lps[r] for r in order], eos if pad_token_id is None else pad_token_id)
@@ -340,10 +347,27 @@ class TraceMistralForCausalLM:
         nf = getattr(self.config, "num_frames", NUM_FRAMES)
         return x.unsqueeze(0).expand(nf, -1, -1, -1) if x.dim() == 3 else x.expand(nf, -1, -1, -1)
 
-    def _eos(self, eos_token_id) -> int:
-        """the argument, else the config's; -1 = no eos"""
-        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
-        return -1 if eos is None else eos
+    def _eos_and_constraints(self, eos_token_id, kwargs, generation_config):
+        """(eos, Constraints or None) of a generate() call, with HF's precedence (_pick; eos_token_id falls back to the config's).  eos_token_id is an
+        int or a list: the first id is the engine's eos (-1 = none), the others become stop sequences of one id, duplicates dropped.
+        bad_words_ids / suppress_tokens / begin_suppress_tokens / stop_sequences are popped from kwargs; as HF does, a bad word that is exactly
+        [e] for an EOS id e is dropped.  ValueError outside the vocabulary or the device's bounds (sampling.check_constraints)."""
+        gc = generation_config
+        e = self._pick("eos_token_id", eos_token_id, gc, self.config.eos_token_id)
+        if isinstance(e, torch.Tensor):
+            e = e.tolist()
+        eos_ids = []
+        for t in ([] if e is None else e if isinstance(e, (list, tuple)) else [e]):
+            if int(t) >= 0 and int(t) not in eos_ids:
+                eos_ids.append(int(t))
+        seqs = lambda name: [[int(t) for t in (w.tolist() if isinstance(w, torch.Tensor) else w)] for w in self._pick(name, kwargs.pop(name, None), gc, [])]
+        flat = lambda name: [int(t) for t in self._pick(name, kwargs.pop(name, None), gc, [])]
+        stops = seqs("stop_sequences")
+        stops = [[t] for t in eos_ids[1:] if [t] not in stops] + stops
+        bad = [w for w in seqs("bad_words_ids") if not (len(w) == 1 and w[0] in eos_ids)]
+        cons = Constraints(stops, bad, flat("suppress_tokens"), flat("begin_suppress_tokens"))
+        check_constraints(cons.stop_sequences, cons.bad_words_ids, cons.suppress_tokens, cons.begin_suppress_tokens, self.config.total_vocab)
+        return (eos_ids[0] if eos_ids else -1), (None if cons.off else cons)
 
     def _padded(self, rows, lps, pad):
         """(ids int64 [B, n] padded with `pad` (0 when it is None or negative), log-probabilities float32 [B, n] zero padded, or None), on the device"""
@@ -392,7 +416,7 @@ class TraceMistralForCausalLM:
                            self._pick("min_new_tokens", min_new_tokens, gc, 0))
         return None if lgp.off else lgp
 
-    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, logprobs=False, lgp=None):
+    def _generate_stepwise(self, vids, timestamps, id_lists, heads, max_new, eos, sampling, stopping, logprobs=False, lgp=None, cons=None):
         """Stopping-criteria path: encode and prefill row by row, then TraceEngine.decode_stepwise with HF's StoppingCriteriaList as its callback.
         A row stops when ANY criterion fires for it; generate(inputs_embeds=...) hands the criteria the generated ids only (the reference calls
         super().generate with inputs_embeds, trace_mistral.py:301-312)."""
@@ -409,7 +433,7 @@ class TraceMistralForCausalLM:
                 r = sc(gen, None)
                 out |= (r.view(-1).bool().cpu() if isinstance(r, torch.Tensor) else torch.full((B,), bool(r)))
             return out.tolist()
-        return eng.decode_stepwise(range(B), heads, max_new, eos, sampling=sampling, logprobs=logprobs, logits=lgp, stopping=fired)
+        return eng.decode_stepwise(range(B), heads, max_new, eos, sampling=sampling, logprobs=logprobs, logits=lgp, stopping=fired, constraints=cons)
 
     # ---- forward (trace_mistral.py:114-264) ----
     @torch.no_grad()

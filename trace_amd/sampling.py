@@ -7,10 +7,13 @@ take (top_k > 1024, or top_k = 0 with top_p < 1), where it applies the same rule
 `token_logprob_ref` restates the per-token log-probability (sample.h token_logprob_row) the same way: the device's float bits.
 `LogitsParams` / `process_row_ref`: the logits processors of the decode step (repetition penalty, no-repeat n-grams, min_new_tokens:
 trace_amd/csrc/logits.h) and their float32 restatement, again bit for bit.
+`Constraints` / `constrain_row_ref` / `stop_match_ref` / `ends_stopped`: bad words, suppressed ids and stop sequences of the decode step
+(trace_amd/csrc/constrain.h) and their restatement; only -inf is stored, so the device is bit for bit by construction.
 `score_logprob_ref`: the log-probability of a GIVEN id as the scoring kernels (trace_amd/csrc/score.hip) form it from column-tile partial sums."""
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
@@ -326,6 +329,110 @@ def process_row_ref(row, hist, lo, hi, params: LogitsParams, step, eos):
     if int(step) < int(params.min_new_tokens) and lo <= int(eos) < hi:
         out[int(eos)] = -np.inf
     return out
+
+
+# ---- constraints (csrc/constrain.h) ----
+MAX_SEQS, MAX_SEQ_LEN, MAX_SUPPRESS = 64, 32, 1024          # constrain.h CONSTRAIN_MAX_SEQS / _SEQ_LEN / _SUPPRESS
+
+
+def _is_id(t) -> bool:
+    return isinstance(t, (int, np.integer)) and not isinstance(t, bool)
+
+
+def check_constraints(stop_sequences, bad_words_ids, suppress_tokens, begin_suppress_tokens, n_vocab=None) -> None:
+    """The device's bounds (at most 64 stop sequences and 64 bad words of 1..32 ids, at most 1024 ids per suppress list; nothing is truncated)
+    and HF's own checks: no empty sequence, every id a non-negative integer - inside [0, n_vocab) where the vocabulary V+1+Tv+Sv is given."""
+    def check_id(name, t):
+        if not _is_id(t) or t < 0 or (n_vocab is not None and t >= n_vocab):
+            raise ValueError(f"`{name}` holds {t!r}: every id has to be an integer in [0, {n_vocab if n_vocab is not None else 'vocabulary size'})")
+    for name, seqs in (("stop_sequences", stop_sequences), ("bad_words_ids", bad_words_ids)):
+        if len(seqs) > MAX_SEQS:
+            raise ValueError(f"`{name}` holds {len(seqs)} sequences, at most {MAX_SEQS} on the device")
+        for w in seqs:
+            if len(w) == 0:
+                raise ValueError(f"`{name}` holds an empty sequence")
+            if len(w) > MAX_SEQ_LEN:
+                raise ValueError(f"`{name}` holds a sequence of {len(w)} ids, at most {MAX_SEQ_LEN} on the device")
+            for t in w:
+                check_id(name, t)
+    for name, ids in (("suppress_tokens", suppress_tokens), ("begin_suppress_tokens", begin_suppress_tokens)):
+        if len(ids) > MAX_SUPPRESS:
+            raise ValueError(f"`{name}` holds {len(ids)} ids, at most {MAX_SUPPRESS} on the device")
+        for t in ids:
+            check_id(name, t)
+
+
+def _as_seqs(name, x):
+    if x is None:
+        return ()
+    if isinstance(x, (str, bytes)) or any(isinstance(w, (str, bytes)) or _is_id(w) for w in x):
+        raise ValueError(f"`{name}` has to be a list of lists of ids, but is {x!r}")
+    return tuple(tuple(w.tolist() if hasattr(w, "tolist") else w) for w in x)
+
+
+@dataclass(frozen=True)
+class Constraints:
+    """stop_sequences: id sequences that end a row like EOS once its generated ids end in one (the ids stay in the output); bad_words_ids: HF's
+    NoBadWordsLogitsProcessor; suppress_tokens / begin_suppress_tokens: HF's SuppressTokens(AtBegin)LogitsProcessor, the latter at the first
+    generated token only.  All ids are global vocabulary ids [text | <sync> | time | score]; the history the rules look at is the ids a row
+    has generated so far, never the prompt.  Stored as tuples (hashable, comparable)."""
+    stop_sequences: tuple = ()
+    bad_words_ids: tuple = ()
+    suppress_tokens: tuple = ()
+    begin_suppress_tokens: tuple = ()
+
+    def __post_init__(self):
+        object.__setattr__(self, "stop_sequences", _as_seqs("stop_sequences", self.stop_sequences))
+        object.__setattr__(self, "bad_words_ids", _as_seqs("bad_words_ids", self.bad_words_ids))
+        for name in ("suppress_tokens", "begin_suppress_tokens"):
+            v = getattr(self, name)
+            object.__setattr__(self, name, () if v is None else tuple(v.tolist() if hasattr(v, "tolist") else v))
+        check_constraints(self.stop_sequences, self.bad_words_ids, self.suppress_tokens, self.begin_suppress_tokens)
+
+    @property
+    def off(self) -> bool:
+        return not (self.stop_sequences or self.bad_words_ids or self.suppress_tokens or self.begin_suppress_tokens)
+
+
+def constrain_row_ref(row, hist, lo, hi, constraints: Constraints, step, min_new_tokens=0):
+    """The ban rules of constrain.h on one whole row (float32 [NV]; the processed row where logits processors run first, process_row_ref's):
+    a new float32 [NV], -inf outside [lo, hi).  hist: the ids the row has generated so far; step: the device step.
+      4. bad word w: len 1: y[w[0]] = -inf; longer: if the last len(w) - 1 ids of hist equal w[:-1]: y[w[-1]] = -inf;
+      5. suppress_tokens: y[t] = -inf at every step;   6. begin_suppress_tokens: at step 0 only;
+      3. (widened) step < min_new_tokens: y[w[0]] = -inf for every stop sequence of one id.
+    An id outside [lo, hi) touches nothing."""
+    x = np.asarray(row, np.float32)
+    h = [int(t) for t in hist]
+    out = np.full(len(x), -np.inf, np.float32)
+    out[lo:hi] = x[lo:hi]
+    banned = []
+    for w in constraints.bad_words_ids:
+        k = len(w)
+        if k == 1 or (len(h) >= k - 1 and h[len(h) - (k - 1):] == list(w[:-1])):
+            banned.append(w[-1])
+    banned += list(constraints.suppress_tokens)
+    if int(step) == 0:
+        banned += list(constraints.begin_suppress_tokens)
+    if int(step) < int(min_new_tokens):
+        banned += [w[0] for w in constraints.stop_sequences if len(w) == 1]
+    for t in banned:
+        if lo <= int(t) < hi:
+            out[int(t)] = -np.inf
+    return out
+
+
+def stop_match_ref(hist, constraints: Constraints) -> bool:
+    """the stop rule: some stop sequence w has len(hist) >= len(w) and equals the last len(w) ids of hist"""
+    h = [int(t) for t in hist]
+    return any(len(h) >= len(w) and h[len(h) - len(w):] == list(w) for w in constraints.stop_sequences)
+
+
+def ends_stopped(ids, eos, constraints: Optional[Constraints] = None) -> bool:
+    """'this row is finished': its recorded ids end in `eos` (>= 0) or in a stop sequence.  A row stops recording the moment either holds, so the
+    tail of what it has recorded says it for good."""
+    if len(ids) == 0:
+        return False
+    return (eos is not None and eos >= 0 and int(ids[-1]) == eos) or (constraints is not None and stop_match_ref(ids, constraints))
 
 
 def head_bounds(head: int, V: int, Tv: int, Sv: int):
