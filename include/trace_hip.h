@@ -34,7 +34,7 @@ typedef struct trace_config {
     float slot_eps, slot_rope_base;
     int32_t max_frames;      /* largest T per video                                    */
     int32_t max_ctx;         /* KV-cache length per sequence slot (prefill + new tokens) */
-    int32_t max_batch;       /* KV-cache sequence slots, <= 512; one decode batch takes at most 256 of them (64 on the fp8 path; the rest can be
+    int32_t max_batch;       /* KV-cache sequence slots, <= 512; one decode batch takes at most 256 of them (64 on the fp8 and w4 weight paths; the rest can be
                               * prefilled meanwhile: trace_amd.engine.TraceEngine.generate_stream) */
     int32_t max_new_tokens;  /* capacity of the on-device output id buffer               */
     int32_t projector_type;  /* 0 = spatial_slot (TRACE), 1 = stc_connector (legacy API) */
@@ -58,7 +58,8 @@ int trace_element_type(void);
 /* from_pretrained (trace/model/builder.py:113-114): create, stream tensors in by their reference state-dict
  * names (bf16; `on_device` says whether `data` is a device or host pointer), then finalize. */
 int trace_ctx_create(const trace_config* cfg, int device_id, trace_ctx** out);
-/* trace_ctx_create with options (trace_config is frozen at ABI version 4).  size = sizeof(trace_ctx_opts) of the caller.  kv_cache_fp8 = 1: the context
+/* trace_ctx_create with options (trace_config is frozen at ABI version 4).  size = sizeof(trace_ctx_opts) of the caller (8), or sizeof(trace_ctx_opts_w4)
+ * (12: the form below with llm_weights_w4 behind the two fields); a smaller size is TRACE_ERR_ARG.  kv_cache_fp8 = 1: the context
  * keeps its KV cache as e4m3 bytes with one fp32 scale per position and kv head (the "kv8" format, stated at the end of this header) — 264 bytes per
  * position and kv head instead of 512, i.e. about twice the sequences or context per card — plus one layer's 16-bit K / V^T of 8 slots that every prefill
  * stages through.  opts == NULL or a zero flag is trace_ctx_create.  Under kv_cache_fp8:
@@ -73,6 +74,21 @@ int trace_ctx_create(const trace_config* cfg, int device_id, trace_ctx** out);
 typedef struct trace_ctx_opts { int32_t size; int32_t kv_cache_fp8; } trace_ctx_opts;
 int trace_ctx_create_opts(const trace_config* cfg, int device_id, const trace_ctx_opts* opts, trace_ctx** out);
 int trace_ctx_kv_cache_type(trace_ctx* ctx);            /* 0 = element type, 1 = e4m3 + scales */
+/* The 12-byte form of the options: trace_ctx_create_opts reads llm_weights_w4 when the caller's size says the field is there (cast the pointer); the
+ * 8-byte struct above keeps working and means llm_weights_w4 = 0.  llm_weights_w4 = 1: the context keeps the four decoder projections of every layer
+ * (qkv, o, gate|up, down) in the "w4" format stated at the end of this header — 4-bit e2m1 codes with one power-of-two scale per 32 weights, 4.25 bits
+ * a weight — as its ONLY copy of them, in the decode tile layout, plus one layer's worth of 16-bit row-major scratch.  Embedding, heads, norms, ViT
+ * and slot pool stay 16-bit.  trace_ctx_load_tensor quantises a projection as it arrives; trace_ctx_device_bytes reports the saving.  Under w4:
+ *   - every prefill (trace_llm_prefill, _pair, _multi, _append, _shared, trace_llm_score_append) dequantises a layer's four tensors into the scratch
+ *     before the layer and runs the 16-bit GEMMs on it unchanged; the decode GEMVs widen the codes to bf16 in registers.  Both multiply by the same
+ *     matrix W~ (every w4 value is exactly a bf16 value), and activations are never quantised: a context of 16-bit weights loaded with W~ computes
+ *     the prefill's bits exactly, and the continuation promise of trace_llm_prefill_append holds as on 16-bit weights (trace_kv_copy,
+ *     trace_llm_prefill_shared and trace_decode_set_shared_prefix stay available);
+ *   - at most 64 sequences decode together (trace_decode_begin answers TRACE_ERR_ARG above), on the GEMV step (trace_op_decode_route_w4).
+ * TRACE_ERR_ARG, checked before any device call: llm_weights_w4 outside {0, 1}; with llm_weights_fp8 != 0; with kv_cache_fp8; in the fp16 library;
+ * hidden_size or intermediate_size not a multiple of 256. */
+typedef struct trace_ctx_opts_w4 { int32_t size; int32_t kv_cache_fp8; int32_t llm_weights_w4; } trace_ctx_opts_w4;
+int trace_ctx_llm_weights_type(trace_ctx* ctx);         /* 0 = element type, 1 / 2 = trace_config.llm_weights_fp8, 3 = w4 */
 int trace_ctx_destroy(trace_ctx* ctx);
 int trace_ctx_load_tensor(trace_ctx* ctx, const char* name, const void* data, int on_device, const int64_t* shape,
                           int ndim);
@@ -420,6 +436,10 @@ int trace_op_decode_route(int B, int fp8_scheme, int H, int I, int QKV, int32_t*
    (ks_in may be 0) + R [B,K] -> xout [B,K]; out = fp32 partial rows [trace_op_skinny_ks(N,K,4,B)][sk_rows][N] of RMSNorm(xout; w, eps) . W^T */
 int trace_op_skinny_fused_norm(const float* part_in, int ks_in, const void* R, void* xout, const void* w, float eps, const void* W, float* out,
                                int B, int N, int K, void* stream);
+/* trace_op_skinny_plan / trace_op_decode_route for w4 weights (kind 3: e2m1 codes + block exponents, bf16 activations; units of 256 k; epilogue 4
+   only), without launching: the same out[0..11) / out[0..8).  The GEMV takes K % 256 == 0, N % 16 == 0, B <= 64; the route H % 256 == 0, I % 256 == 0. */
+int trace_op_skinny_w4_plan(int N, int K, int B, int64_t* out);
+int trace_op_decode_route_w4(int B, int H, int I, int QKV, int32_t* out);
 int trace_op_sk_rows(void);                 /* row stride of every fp32 partial-row buffer = the largest decode batch (256) */
 /* Decode batches above 64 rows: out = X[M <= 128, K] . W[N, K]^T (row-major W) as fp32 k-chunk partial rows
    [trace_op_gemm_partial_ks(N, K)][trace_op_sk_rows()][N] for trace_op_add_rmsnorm (split-K MFMA GEMM, 128x128 tiles) */
@@ -540,6 +560,34 @@ int trace_op_kv8_pack(const void* k_rows, const void* v_rows, void* k8, void* v8
  * (the 16-bit cache's layout); positions from R on are not written.  Errors as above. */
 int trace_op_kv8_unpack(const void* k8, const void* v8, const float* ks, const float* vs, const int32_t* slots, void* k_out, void* vt_out, int R, int B,
                         int nkv, int num_slots, int max_ctx, void* stream);
+
+
+/* ---- The 4-bit weight format ("w4"), and its kernels over loose arrays ----------------------------------------------------------------------------
+ * For the four decoder projections W [N][K] (nn.Linear layout, bf16), K % 32 == 0.  A block is 32 consecutive k of one output row.
+ *     element  OCP e2m1: magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6} = codes 0..7, bit 3 = sign
+ *     scale    2^e, one e8m0 byte per block: byte = e + 127
+ *     e        the smallest integer with amax / 2^e <= 6 (amax = the block's largest magnitude), so nothing saturates; kept >= -120, so that every
+ *              quotient below is a normal fp32 number (bf16 denormals round to code 0).  An all-zero block: every code 0 and byte 0 (e = -127)
+ *     code     round to nearest, ties to the even code, of |v| / 2^e (exact: a power-of-two quotient); the sign bit is set only beside a non-zero
+ *              magnitude (no negative zeros)
+ *     W~[n][k] = e2m1(code) * 2^e — exactly a bf16 value.  Quantising W~ again gives W~ again (possibly under a smaller scale, where a block's largest
+ *              code rounded down to 3 or below).
+ * Powers of two because the conversion instruction (v_cvt_scalef32_pk_bf16_fp4) is only relied on for power-of-two scale operands.
+ * Logical arrays (trace_op_quant_rows_w4, trace_amd/w4.py quant):
+ *     codes [N][K / 2]   bytes: k = 2 j in the LOW nibble of byte j, k = 2 j + 1 in the high nibble
+ *     exps  [N][K / 32]  bytes
+ * Decode tile layout (trace_op_tile_pack_w4, trace_amd/w4.py tile_pack; N % 16 == 0, K % 256 == 0), U = K / 256 units per 16-row tile:
+ *     tcodes [N / 16][U][64 lanes][32] bytes: lane = g * 16 + r holds the 64 codes of row tile * 16 + r, k = unit * 256 + g * 64 .. + 64, in logical
+ *            byte and nibble order: dword q (0..7) of the 32 bytes is one 8-k matrix fragment, and the conversion instruction takes byte_sel's
+ *            low nibble to the low half of its result (tests/test_gpu_w4.py pointer probe)
+ *     texps  [N / 16][U][64 lanes][2]  bytes: the exponent bytes of the lane's two blocks (dwords 0-3, dwords 4-7)
+ * trace_op_dequant_w4: the tile layout -> row-major bf16 [N][K] = W~, exact.  trace_op_skinny_w4: X bf16 [B][K] . W~^T as fp32 k-chunk partial rows
+ * out [KS][trace_op_sk_rows()][N] (KS = out[0] of trace_op_skinny_w4_plan; rows >= B of every chunk are not written), fp32 accumulation of exact
+ * bf16 x bf16 products on the bf16 matrix instruction; the caller sums the chunks.  All four: bf16 library only (TRACE_ERR_ARG in the fp16 one). */
+int trace_op_quant_rows_w4(const void* W, void* codes, void* exps, int N, int K, void* stream);
+int trace_op_tile_pack_w4(const void* codes, const void* exps, void* tcodes, void* texps, int N, int K, void* stream);
+int trace_op_dequant_w4(const void* tcodes, const void* texps, void* out, int N, int K, void* stream);
+int trace_op_skinny_w4(const void* X, const void* tcodes, const void* texps, float* out, int B, int N, int K, void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,11 @@ class TraceCtxOptsC(C.Structure):
     _fields_ = [("size", C.c_int32), ("kv_cache_fp8", C.c_int32)]
 
 
+class TraceCtxOptsW4C(C.Structure):
+    """trace_ctx_opts_w4: the 12-byte form trace_ctx_create_opts also reads (cast to a TraceCtxOptsC pointer for the call)"""
+    _fields_ = [("size", C.c_int32), ("kv_cache_fp8", C.c_int32), ("llm_weights_w4", C.c_int32)]
+
+
 class TraceConstraintsC(C.Structure):
     _fields_ = [("size", C.c_int32), ("n_stop", C.c_int32), ("n_bad_words", C.c_int32), ("n_suppress", C.c_int32), ("n_begin_suppress", C.c_int32),
                 ("stop_offsets", C.c_void_p), ("stop_ids", C.c_void_p), ("bad_word_offsets", C.c_void_p), ("bad_word_ids", C.c_void_p),
@@ -47,6 +52,7 @@ SIGNATURES = {
     "trace_ctx_create": (I, [C.POINTER(TraceConfigC), I, C.POINTER(P)]),
     "trace_ctx_create_opts": (I, [C.POINTER(TraceConfigC), I, C.POINTER(TraceCtxOptsC), C.POINTER(P)]),
     "trace_ctx_kv_cache_type": (I, [P]),
+    "trace_ctx_llm_weights_type": (I, [P]),
     "trace_ctx_destroy": (I, [P]),
     "trace_ctx_load_tensor": (I, [P, C.c_char_p, P, I, C.POINTER(C.c_int64), I]),
     "trace_ctx_finalize": (I, [P]),
@@ -111,6 +117,8 @@ SIGNATURES = {
     "trace_op_skinny_ks": (I, [I, I, I, I]),
     "trace_op_skinny_plan": (I, [I, I, I, I, I, C.POINTER(C.c_int64)]),
     "trace_op_decode_route": (I, [I, I, I, I, I, C.POINTER(C.c_int32)]),
+    "trace_op_skinny_w4_plan": (I, [I, I, I, C.POINTER(C.c_int64)]),
+    "trace_op_decode_route_w4": (I, [I, I, I, I, C.POINTER(C.c_int32)]),
     "trace_op_sk_rows": (I, []),
     "trace_op_skinny_fused_norm": (I, [P, I, P, P, P, F, P, P, I, I, I, P]),
     "trace_op_gemm_partial_ks": (I, [I, I]),
@@ -136,9 +144,13 @@ SIGNATURES = {
     "trace_op_qkv_finish_kv8": (I, [P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "trace_op_kv8_pack": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "trace_op_kv8_unpack": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "trace_op_quant_rows_w4": (I, [P, P, P, I, I, P]),
+    "trace_op_tile_pack_w4": (I, [P, P, P, P, I, I, P]),
+    "trace_op_dequant_w4": (I, [P, P, P, I, I, P]),
+    "trace_op_skinny_w4": (I, [P, P, P, P, I, I, I, P]),
 }
 
-NOT_A_STATUS = {"trace_abi_version", "trace_element_type", "trace_ctx_kv_cache_type", "trace_op_skinny_ks", "trace_op_sk_rows", "trace_op_gemm_partial_ks", "trace_op_score_tile"}   # ints that are values
+NOT_A_STATUS = {"trace_abi_version", "trace_element_type", "trace_ctx_kv_cache_type", "trace_ctx_llm_weights_type", "trace_op_skinny_ks", "trace_op_sk_rows", "trace_op_gemm_partial_ks", "trace_op_score_tile"}   # ints that are values
 _libs = {}
 
 

@@ -937,7 +937,7 @@ __global__ __launch_bounds__(512) void head_logits_kernel(const bf16_t* __restri
 }  // namespace
 
 // The partition of every decode GEMV (skinny_lds here, skinny_fp8 in fp8.hip): KS k-chunks x row-groups of T tiles, WPT waves per tile.  K is counted
-// in units of 2 KB of weights per 16 rows: 64 k of bf16, 128 k of e4m3.  B enters through NB alone (its 16-row activation groups: 1, 2 or 4).
+// in units of 2 KB of weights per 16 rows: 64 k of bf16, 128 k of e4m3, 256 k of w4 codes (w4.hip).  B enters through NB alone (its 16-row activation groups: 1, 2 or 4).
 int skinny_num_cus() {
     static int n = 0;
     if (!n) {
@@ -948,7 +948,8 @@ int skinny_num_cus() {
     }
     return n;
 }
-static int skinny_unit(SkinnyKind kind) { return kind == SK_BF16 ? 64 : 128; }
+static int skinny_unit(SkinnyKind kind) { return kind == SK_BF16 ? 64 : kind == SK_W4A16 ? 256 : 128; }
+static int skinny_images(SkinnyKind kind) { return kind == SK_W4A16 ? 8 : kind == SK_W8A16 ? 4 : 2; }    // 1 KB activation images per unit and row group
 bool skinny_shape_ok(SkinnyKind kind, int N, int K, int epi, int B) {
     if (B < 1 || B > SKINNY_ROWS || N < 16 || K < skinny_unit(kind) || K % skinny_unit(kind)) return false;
     if (kind != SK_BF16) return epi == EPI_PARTIAL && N % 16 == 0;
@@ -961,8 +962,8 @@ static SkinnyPlan skinny_plan_nb(SkinnyKind kind, int N, int K, int epi, int NB)
     p.NT = epi == EPI_SWIGLU || (epi == EPI_PARTIAL && N >= 16384 && N % 32 == 0) ? 2 : 1;
     const int U = K / skinny_unit(kind);
     static const int cap1 = getenv("TRACE_SK_CAP") ? atoi(getenv("TRACE_SK_CAP")) : 64;    // tuning knob (microbenchmarks): bf16, one row group
-    // units of X that fit 128 KB of LDS: 2 KB a unit and row group as bf16 or e4m3 images, 4 KB as bf16 rows beside e4m3 weights
-    const int cap = kind == SK_BF16 && NB == 1 ? cap1 : (kind == SK_W8A16 ? 32 : 64) / NB;
+    // units of X that fit 128 KB of LDS: 2 KB a unit and row group as bf16 or e4m3 images, 4 KB as bf16 rows beside e4m3 weights, 8 KB beside w4 codes
+    const int cap = kind == SK_BF16 && NB == 1 ? cap1 : (128 / skinny_images(kind)) / NB;
     const int ks_min = (U + cap - 1) / cap;
     const int ks_max = epi == EPI_PARTIAL ? std::min(U, ks_min + 4) : ks_min;    // extra chunks are free only without the ticket merge
     p.ntiles = N / (16 * p.NT);
@@ -981,7 +982,7 @@ static SkinnyPlan skinny_plan_nb(SkinnyKind kind, int N, int K, int epi, int NB)
     // T*WPT <= 8 waves; the LDS reduction scratch (T*WPT*NT*NB KB) must fit beside the 128 KB of parked activations
     while (p.WPT * 2 * p.T <= 8 && p.WPT * 2 * p.T * p.NT * NB <= 28 && p.WPT * 2 <= p.chunk_units) p.WPT *= 2;
     p.threads = std::min(p.T, 8) * p.WPT * 64;          // T > 8: every wave takes two tasks in turn
-    p.lds_bytes = (size_t)p.chunk_units * (kind == SK_W8A16 ? 4 : 2) * NB * 1024 + (p.WPT > 1 ? (size_t)p.T * p.WPT * p.NT * NB * 1024 : 0);
+    p.lds_bytes = (size_t)p.chunk_units * skinny_images(kind) * NB * 1024 + (p.WPT > 1 ? (size_t)p.T * p.WPT * p.NT * NB * 1024 : 0);
     return p;
 }
 SkinnyPlan skinny_plan(SkinnyKind kind, int N, int K, int epi, int B) { return skinny_plan_nb(kind, N, K, epi, B > 32 ? 4 : B > 16 ? 2 : 1); }

@@ -38,6 +38,9 @@ struct LlmLayer {
     // decode GEMVs, one fp32 scale per output row
     uint8_t *wqkv8, *wo8, *wgu8, *wd8, *wqkv8_d, *wo8_d, *wgu8_d, *wd8_d;
     float *sqkv, *so, *sgu, *sd;
+    // w4 weight path (trace_ctx_opts_w4::llm_weights_w4; w4.hip): the ONLY copy of qkv, o, gate|up, down (in this order): e2m1 codes and exponent bytes
+    // in the decode tile layout; the 16-bit pointers above stay null
+    uint8_t *w4c[4], *w4e[4];
 };
 struct StcBlock { bf16_t *w1, *n1w, *n1b, *wdw, *n2w, *n2b, *fc1w, *fc1b, *fc2w, *fc2b, *w3, *n3w, *n3b, *wd, *ndw, *ndb; int cin, rd; };
 
@@ -123,6 +126,11 @@ struct trace_ctx {
     int fp8_wonly = 0;                 // llm_weights_fp8 == 2: the decode GEMVs keep bf16 activations (weight-only; the prefill GEMMs stay W8A8)
     uint8_t *pA8 = nullptr, *dA8 = nullptr, *dH8 = nullptr;      // quantised activations: prefill [2 max_ctx][max(H, I)], decode [64][I]; dH8 = the normed hidden rows
     float *psa = nullptr, *dsa = nullptr, *dsh = nullptr;        // their per-row scales
+    // w4 weights: one layer's 16-bit row-major qkv, o, gate|up, down that dequant_w4 fills before each prefill layer (and that a tensor lands in while it
+    // is loaded), and the logical codes / exponents of one loaded piece between the quantiser and the tile packer
+    int w4 = 0;
+    bf16_t* w4_row[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint8_t *w4_stage_c = nullptr, *w4_stage_e = nullptr;
     int step_in_call = 0;              // decode steps taken since trace_decode_begin at the time decode_step runs (host copy)
     long pos_sum = 0;                  // sum over the batch of the prefill lengths (host copy: algorithmic KV bytes of a decode step's attention)
     double kbytes_sum = 0.0;           // algorithmic bytes of the bracketed launches (profile == 2)
@@ -318,18 +326,26 @@ extern "C" int trace_op_gemm_route(int M, int N, int K, int lda, int ldw, int ld
 extern "C" int trace_abi_version(void) { return TRACE_ABI_VERSION; }
 extern "C" int trace_element_type(void) { return TRACE_ELEMENT_TYPE; }
 
-static int ctx_create(const trace_config* cfg, int device_id, int kv8, trace_ctx** out);
-extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ctx** out) { return ctx_create(cfg, device_id, 0, out); }
+static int ctx_create(const trace_config* cfg, int device_id, int kv8, int w4, trace_ctx** out);
+extern "C" int trace_ctx_create(const trace_config* cfg, int device_id, trace_ctx** out) { return ctx_create(cfg, device_id, 0, 0, out); }
 extern "C" int trace_ctx_create_opts(const trace_config* cfg, int device_id, const trace_ctx_opts* opts, trace_ctx** out) {
     if (!cfg || !out) return fail(TRACE_ERR_ARG, "null argument");
     if (opts && opts->size < (int32_t)sizeof(trace_ctx_opts)) return fail(TRACE_ERR_ARG, "trace_ctx_opts::size is smaller than this library's struct");
     const int kv8 = opts ? opts->kv_cache_fp8 : 0;
     if (kv8 != 0 && kv8 != 1) return fail(TRACE_ERR_ARG, "kv_cache_fp8 must be 0 or 1");
     if (kv8 && cfg->llm_weights_fp8) return fail(TRACE_ERR_ARG, "kv_cache_fp8 with llm_weights_fp8: the e4m3 KV cache runs on 16-bit weights only");
-    return ctx_create(cfg, device_id, kv8, out);
+    // the 12-byte form (trace_ctx_opts_w4) carries llm_weights_w4 behind the two fields of the 8-byte one
+    const int w4 = opts && opts->size >= (int32_t)sizeof(trace_ctx_opts_w4) ? reinterpret_cast<const trace_ctx_opts_w4*>(opts)->llm_weights_w4 : 0;
+    if (w4 != 0 && w4 != 1) return fail(TRACE_ERR_ARG, "llm_weights_w4 must be 0 or 1");
+    if (w4 && cfg->llm_weights_fp8) return fail(TRACE_ERR_ARG, "llm_weights_w4 with llm_weights_fp8: the decoder projections take one quantised format");
+    if (w4 && kv8) return fail(TRACE_ERR_ARG, "llm_weights_w4 with kv_cache_fp8: the e4m3 KV cache runs on 16-bit weights only");
+    if (w4 && TRACE_ELEMENT_TYPE != 0) return fail(TRACE_ERR_ARG, "llm_weights_w4 needs the bf16 library (the fp16 build has no w4 weight path)");
+    if (w4 && (cfg->hidden_size % 256 || cfg->intermediate_size % 256)) return fail(TRACE_ERR_ARG, "w4 weight path needs hidden / intermediate sizes that are multiples of 256");
+    return ctx_create(cfg, device_id, kv8, w4, out);
 }
 extern "C" int trace_ctx_kv_cache_type(trace_ctx* c) { return c ? c->kv8 : fail(TRACE_ERR_ARG, "null context"); }
-static int ctx_create(const trace_config* cfg, int device_id, int kv8, trace_ctx** out) {
+extern "C" int trace_ctx_llm_weights_type(trace_ctx* c) { return c ? (c->w4 ? 3 : c->fp8 ? 1 + c->fp8_wonly : 0) : fail(TRACE_ERR_ARG, "null context"); }
+static int ctx_create(const trace_config* cfg, int device_id, int kv8, int w4, trace_ctx** out) {
     if (!cfg || !out) return fail(TRACE_ERR_ARG, "null argument");
     g_err.clear();
     HIPCHK(hipSetDevice(device_id));
@@ -337,6 +353,7 @@ static int ctx_create(const trace_config* cfg, int device_id, int kv8, trace_ctx
     c->c = *cfg;
     c->dev = device_id;
     c->kv8 = kv8;
+    c->w4 = w4;
     c->H = cfg->hidden_size; c->I = cfg->intermediate_size; c->NL = cfg->num_layers;
     c->NQ = cfg->num_heads; c->NKV = cfg->num_kv_heads; c->HD = c->H / c->NQ;
     c->V = cfg->vocab_size; c->Tv = cfg->time_vocab; c->Sv = cfg->score_vocab;
@@ -401,7 +418,13 @@ static int ctx_create(const trace_config* cfg, int device_id, int kv8, trace_ctx
     A(c->embed, (size_t)c->V * H); A(c->final_norm, H); A(c->wheads, (size_t)c->NVpad * H);
     A(c->time_tab, (size_t)c->Tv * H); A(c->score_tab, (size_t)c->Sv * H); A(c->sync_row, H);
     c->llm.resize(c->NL);
+    const size_t w4_elems[4] = {(size_t)c->QKV * H, H * H, 2 * I * H, H * I};     // qkv, o, gate|up, down
     for (auto& l : c->llm) {
+        if (c->w4) {         // 4 bits a weight + a byte per 32: the only copy of the four projections
+            A(l.rms1, H); A(l.rms2, H);
+            for (int p = 0; p < 4; ++p) { A(l.w4c[p], w4_elems[p] / 2); A(l.w4e[p], w4_elems[p] / 32); }
+            continue;
+        }
         A(l.rms1, H); A(l.wqkv, (size_t)c->QKV * H); A(l.wo, H * H); A(l.rms2, H); A(l.wgu, 2 * I * H); A(l.wd, H * I);
         A(l.wqkv_d, (size_t)c->QKV * H); A(l.wo_d, H * H); A(l.wgu_d, 2 * I * H); A(l.wd_d, H * I);
         if (c->fp8) {
@@ -409,6 +432,11 @@ static int ctx_create(const trace_config* cfg, int device_id, int kv8, trace_ctx
             A(l.wqkv8_d, (size_t)c->QKV * H); A(l.wo8_d, H * H); A(l.wgu8_d, 2 * I * H); A(l.wd8_d, H * I);
             A(l.sqkv, (size_t)c->QKV); A(l.so, H); A(l.sgu, 2 * I); A(l.sd, H);
         }
+    }
+    if (c->w4) {
+        for (int p = 0; p < 4; ++p) A(c->w4_row[p], w4_elems[p]);
+        const size_t piece = std::max(std::max((size_t)c->QKV * H, H * H), H * I);        // the largest tensor a load call brings (gate and up come apart)
+        A(c->w4_stage_c, piece / 2); A(c->w4_stage_e, piece / 32);
     }
     A(c->slot_cos, (size_t)c->GG * vh / 2); A(c->slot_sin, (size_t)c->GG * vh / 2);
     A(c->rope_cos, (size_t)c->max_ctx * c->HD / 2); A(c->rope_sin, (size_t)c->max_ctx * c->HD / 2);
@@ -457,6 +485,7 @@ static int ctx_create(const trace_config* cfg, int device_id, int kv8, trace_ctx
         for (const auto& p : proj) {
             for (SkinnyKind kind : {SK_BF16, SK_W8A8, SK_W8A16})
                 if (kind == SK_BF16 || c->fp8) f = std::max(f, skinny_partial_floats(kind, p.N, p.K));
+            if (c->w4) f = std::max(f, skinny_partial_floats(SK_W4A16, p.N, p.K));
             if (p.wide_partial) f = std::max(f, (size_t)gemm_partial_ks(p.N, p.K) * SK_ROWS * p.N);
         }
         c->sk_ws_floats = std::max<size_t>(f, 64);
@@ -607,6 +636,26 @@ extern "C" int trace_ctx_load_tensor(trace_ctx* c, const char* name_, const void
         const size_t qrows = (size_t)c->NQ * c->HD, kvrows = (size_t)c->NKV * c->HD;
         if (k == "input_layernorm.weight") return flat(L.rms1, H);
         if (k == "post_attention_layernorm.weight") return flat(L.rms2, H);
+        if (c->w4) {
+            // a projection piece of `rows` rows lands in the layer scratch of its projection, is quantised row-wise into the staging arrays and packed into
+            // tiles tile0, tile0 + step, ... of the layer's only copy (gate / up: alternating tiles, the 16-row interleave of the 16-bit path)
+            auto piece = [&](int p, size_t rows, size_t K, size_t tile0, int step) -> int {
+                TRY(expect((int64_t)(rows * K)));
+                TRY(copy1d(c->w4_row[p], data, rows * K * E, on_device));
+                LCHK(launch_quant_rows_w4(c->w4_row[p], (long)K, c->w4_stage_c, c->w4_stage_e, (int)rows, (int)K, 0));
+                LCHK(launch_tile_pack_w4(c->w4_stage_c, c->w4_stage_e, L.w4c[p], L.w4e[p], (int)rows, (int)K, (int)tile0, step, 0));
+                HIPCHK(hipDeviceSynchronize());
+                return done();
+            };
+            if (k == "self_attn.q_proj.weight") return piece(0, qrows, H, 0, 1);
+            if (k == "self_attn.k_proj.weight") return piece(0, kvrows, H, qrows / 16, 1);
+            if (k == "self_attn.v_proj.weight") return piece(0, kvrows, H, (qrows + kvrows) / 16, 1);
+            if (k == "self_attn.o_proj.weight") return piece(1, H, H, 0, 1);
+            if (k == "mlp.gate_proj.weight") return piece(2, I, H, 0, 2);
+            if (k == "mlp.up_proj.weight") return piece(2, I, H, 1, 2);
+            if (k == "mlp.down_proj.weight") return piece(3, H, I, 0, 1);
+            return fail(TRACE_ERR_ARG, "unknown tensor " + name);
+        }
         if (k == "self_attn.q_proj.weight") return flat(L.wqkv, qrows * H);
         if (k == "self_attn.k_proj.weight") return flat(L.wqkv + qrows * H, kvrows * H);
         if (k == "self_attn.v_proj.weight") return flat(L.wqkv + (qrows + kvrows) * H, kvrows * H);
@@ -710,6 +759,7 @@ extern "C" int trace_ctx_finalize(trace_ctx* c) {
     }
     // decode copies of the LLM matrices in the GEMV tile layout (288 GB of HBM: +14.5 GB buys ~25% on the weight stream)
     for (auto& l : c->llm) {
+        if (c->w4) break;                                 // packed as the tensors arrived
         LCHK(launch_tile_pack(l.wqkv, c->H, l.wqkv_d, c->QKV, c->H, 0));
         LCHK(launch_tile_pack(l.wo, c->H, l.wo_d, c->H, c->H, 0));
         LCHK(launch_tile_pack(l.wgu, c->H, l.wgu_d, 2 * c->I, c->H, 0));
@@ -1156,7 +1206,12 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
     a.nq_rows = L; a.nkv_rows = past + L; a.batch = nb; a.heads = c->NQ; a.kv_heads = c->NKV;
     a.scale = 1.0f / sqrtf((float)HD); a.causal = 1;
     for (int l = 0; l < c->NL; ++l) {
-        const LlmLayer& W = c->llm[l];
+        LlmLayer W = c->llm[l];
+        if (c->w4) {          // this layer's four projections as 16-bit rows (exactly the weights the decode GEMVs widen); the GEMMs below run on them unchanged
+            const int wn[4] = {QKV, H, 2 * I, H}, wk[4] = {H, H, H, I};
+            for (int p = 0; p < 4; ++p) LCHK(launch_dequant_w4(W.w4c[p], W.w4e[p], c->w4_row[p], wk[p], wn[p], wk[p], s));
+            W.wqkv = c->w4_row[0]; W.wo = c->w4_row[1]; W.wgu = c->w4_row[2]; W.wd = c->w4_row[3];
+        }
         bf16_t* kc = c->kv8 ? c->kv_stage_k : c->kcache + (size_t)l * c->layer_stride;
         bf16_t* vc = c->kv8 ? c->kv_stage_v : c->vcache + (size_t)l * c->layer_stride;
         if (c->kv8 && past > 0)
@@ -1385,7 +1440,7 @@ static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* l
 }
 
 // Everything one decode step decides before it launches.  Pure: the tuning values come as an argument, nothing is kept between steps, and the only HIP
-// call behind it is the GEMV plan's CU count, asked once per process.  trace_op_decode_route shows it to host tests.  fp8_scheme: trace_config::llm_weights_fp8.
+// call behind it is the GEMV plan's CU count, asked once per process.  trace_op_decode_route shows it to host tests.  scheme: trace_config::llm_weights_fp8, or 3 for w4 weights.
 //   step (= prof[8]): 3 wide above SKINNY_ROWS and, on bf16 weights, from decode.wide_min_rows; 2 fused up to decode.fuse_norm_rows on bf16 weights where
 //     both fused-norm GEMVs take the shape; 1 skinny otherwise.
 //   qkv_finish: RoPE + cache append as a launch of its own instead of the attention's prologue (decode.unfused_qkv, wide: decode.wide_fuse_qkv).
@@ -1394,12 +1449,12 @@ static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* l
 //     ticket latency (measured, ctx 2100: B=1 16 splits 10.4 us, B=4 8 -> 13 us, B=16 2 -> 26 us, B=32 1 -> 45 us; B=32 with 16 splits: 79 us).
 //     attn.decode.nsplit > 0 forces the number (A/B).
 struct DecodeRoute { int step; SkinnyKind kind; bool qkv_finish; int ks_q, ks_o, ks_g, ks_d, nsplit; };
-static DecodeRoute decode_route(int B, int fp8_scheme, int H, int I, int QKV, const Tuning& t) {
+static DecodeRoute decode_route(int B, int scheme, int H, int I, int QKV, const Tuning& t) {
     DecodeRoute r{};
-    const bool fp8 = fp8_scheme != 0;
-    r.kind = !fp8 ? SK_BF16 : fp8_scheme == 2 ? SK_W8A16 : SK_W8A8;
-    if (B > SKINNY_ROWS || (B >= t.decode_wide_min_rows && !fp8)) r.step = 3;
-    else r.step = B <= t.decode_fuse_norm_rows && !fp8 && skinny_fused_norm_ok(QKV, H, B) && skinny_fused_norm_ok(2 * I, H, B) ? 2 : 1;
+    const bool quant = scheme != 0;                // quantised weights of either format (3 = w4: routed as the weight-only fp8 scheme is, on its own kind of GEMV)
+    r.kind = !quant ? SK_BF16 : scheme == 3 ? SK_W4A16 : scheme == 2 ? SK_W8A16 : SK_W8A8;
+    if (B > SKINNY_ROWS || (B >= t.decode_wide_min_rows && !quant)) r.step = 3;
+    else r.step = B <= t.decode_fuse_norm_rows && !quant && skinny_fused_norm_ok(QKV, H, B) && skinny_fused_norm_ok(2 * I, H, B) ? 2 : 1;
     r.qkv_finish = r.step == 3 ? !t.decode_wide_fuse_qkv : r.step == 1 && (t.decode_unfused_qkv == 1 || (t.decode_unfused_qkv == 0 && B >= 32));
     auto ks = [&](int N, int K) { return r.step == 3 ? gemm_partial_ks(N, K, t) : skinny_ks(r.kind, N, K, EPI_PARTIAL, B); };
     r.ks_q = ks(QKV, H); r.ks_o = ks(H, H); r.ks_g = r.step == 3 ? 0 : ks(2 * I, H); r.ks_d = ks(H, I);
@@ -1455,7 +1510,7 @@ static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s, const fl
 // ctx ~2100, where the KV stream (0.27 GB per token) is the larger part.
 static int decode_step_wide(trace_ctx* c, const DecodeRoute& r, float* logits_out, hipStream_t s) {
     const int H = c->H, I = c->I, QKV = c->QKV, B = c->B;
-    if (c->fp8) return fail(TRACE_ERR_STATE, "the fp8 weight path decodes at most 64 sequences together");
+    if (c->fp8 || c->w4) return fail(TRACE_ERR_STATE, "the fp8 and w4 weight paths decode at most 64 sequences together");
     const int wt = g_tune.decode_gemm_tiled;
     auto pgemm = [&](const bf16_t* A, int lda, const bf16_t* Wrow, const bf16_t* Wtile, int ldw, int N, int K, int ks) -> int {
         GemmArgs g{A, lda, (wt & 1) ? Wtile : Wrow, ldw, nullptr, 0, nullptr, nullptr, 0, B, N, K, nullptr, 0, nullptr, nullptr, 0, c->sk_ws, ks, (wt & 1) ? wt : 0};
@@ -1526,11 +1581,15 @@ static int decode_step_skinny(trace_ctx* c, const DecodeRoute& r, float* logits_
     // -> new residual, RMSNorm] -> gate|up -> [sum, SwiGLU] -> down -> [sum + residual, next layer's / the final RMSNorm].
     const bool wo = r.kind == SK_W8A16;              // weight-only decode GEMVs: bf16 activations straight from dH / dO / dACT, no quantiser launches
     const bool f8 = r.kind == SK_W8A8;
-    // One projection of the step, X [B, K] -> partial rows in sk_ws, on the step's kind of weights: bf16 tile copies (Wd), or the e4m3 tile copy (W8d, scales
-    // sw) with bf16 activations (weight-only) or with activations quantised row-wise first (quant_rows_fp8: [B, K] bf16 -> e4m3 + per-row scale).  The
-    // normed hidden rows dH arrive already quantised (dH8 / dsh) from add_rmsnorm; only the step's first norm needs the quantiser.  Partial rows, their
-    // consumers and the attention are the bf16 path's.
-    auto gemv = [&](const bf16_t* X, const bf16_t* Wd, const uint8_t* W8d, const float* sw, int N, int K) -> int {
+    // One projection of the step (p: 0 qkv, 1 o, 2 gate|up, 3 down), X [B, K] -> partial rows in sk_ws, on the step's kind of weights: the w4 tile copy (codes
+    // and exponent bytes) with bf16 activations, bf16 tile copies (Wd), or the e4m3 tile copy (W8d, scales sw) with bf16 activations (weight-only) or with
+    // activations quantised row-wise first (quant_rows_fp8: [B, K] bf16 -> e4m3 + per-row scale).  The normed hidden rows dH arrive already quantised
+    // (dH8 / dsh) from add_rmsnorm; only the step's first norm needs the quantiser.  Partial rows, their consumers and the attention are the bf16 path's.
+    auto gemv = [&](const bf16_t* X, const LlmLayer& W, int p, int N, int K) -> int {
+        if (r.kind == SK_W4A16) return launch_skinny_w4(X, K, W.w4c[p], W.w4e[p], B, N, K, c->sk_ws, c->sk_ws_floats, s);
+        const bf16_t* Wd = p == 0 ? W.wqkv_d : p == 1 ? W.wo_d : p == 2 ? W.wgu_d : W.wd_d;
+        const uint8_t* W8d = p == 0 ? W.wqkv8_d : p == 1 ? W.wo8_d : p == 2 ? W.wgu8_d : W.wd8_d;
+        const float* sw = p == 0 ? W.sqkv : p == 1 ? W.so : p == 2 ? W.sgu : W.sd;
         if (wo) return launch_skinny_w8(X, K, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
         if (!f8) return launch_skinny_gemm(X, K, Wd, K, nullptr, N, nullptr, 0, B, N, K, EPI_PARTIAL, 1, SKWS(c), s);
         if (X == c->dH) return launch_skinny_fp8(c->dH8, K, c->dsh, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
@@ -1543,19 +1602,19 @@ static int decode_step_skinny(trace_ctx* c, const DecodeRoute& r, float* logits_
         const LlmLayer& W = c->llm[l];
         // (fusing the RMSNorm into the GEMV itself was tried: re-scaling the same activations in every workgroup cost
         //  more than a row kernel — 65 us vs 52 + 6 us for the gate|up GEMV)
-        LCHK(gemv(c->dH, W.wqkv_d, W.wqkv8_d, W.sqkv, QKV, H));
+        LCHK(gemv(c->dH, W, 0, QKV, H));
         if (r.qkv_finish) LCHK(qkv_finish_layer(c, l, r.ks_q, s));
         LCHK(attn_decode_layer(c, l, r, c->sk_ws, s));
-        LCHK(gemv(c->dO, W.wo_d, W.wo8_d, W.so, H, H));
+        LCHK(gemv(c->dO, W, 1, H, H));
         LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
         {   // bracketed: the layer-0 gate|up GEMV (fp8: the bracket spans what the projection launches)
             StepBracket br(c, l, 1, s);
-            LCHK(gemv(c->dH, W.wgu_d, W.wgu8_d, W.sgu, 2 * I, H));
+            LCHK(gemv(c->dH, W, 2, 2 * I, H));
         }
         // (SwiGLU inside the gate|up GEMV at batch <= 16 — one K chunk, no combine kernel — measured 3.73 vs 3.5 ms per batch-1 step: its 224
         //  workgroups leave 32 CUs without a weight stream)
         LCHK(launch_swiglu_combine(c->sk_ws, r.ks_g, 2 * I, c->dACT, I, B, s));
-        LCHK(gemv(c->dACT, W.wd_d, W.wd8_d, W.sd, H, I));
+        LCHK(gemv(c->dACT, W, 3, H, I));
         const bf16_t* nw = l + 1 < c->NL ? c->llm[l + 1].rms1 : c->final_norm;
         LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
     }
@@ -1564,7 +1623,7 @@ static int decode_step_skinny(trace_ctx* c, const DecodeRoute& r, float* logits_
 
 // one decode step for the current batch: consumes dX (embedding of the last token), leaves the next one in dX
 static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
-    DecodeRoute r = decode_route(c->B, c->fp8 ? 1 + c->fp8_wonly : 0, c->H, c->I, c->QKV, g_tune);    // (fp8 contexts: at most 64 rows, checked at begin)
+    DecodeRoute r = decode_route(c->B, c->w4 ? 3 : c->fp8 ? 1 + c->fp8_wonly : 0, c->H, c->I, c->QKV, g_tune);    // (fp8 contexts: at most 64 rows, checked at begin)
     if (c->kv8) r.qkv_finish = true;                 // the e4m3 KV cache always appends with a launch of its own (qkv_finish_kv8), in every step body
     return r.step == 3 ? decode_step_wide(c, r, logits_out, s) : r.step == 2 ? decode_step_fused(c, r, logits_out, s) : decode_step_skinny(c, r, logits_out, s);
 }
@@ -1585,7 +1644,7 @@ extern "C" int trace_decode_set_shared_prefix(trace_ctx* c, int slot, int rows) 
 extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, const int32_t* heads, int max_new, int eos,
                                   const int32_t* forced, float* logits_out, void* stream) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
-    if (!slots || !heads || B < 1 || B > c->max_B || B > (c->fp8 ? SKINNY_ROWS : SK_ROWS)) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(c->fp8 ? SKINNY_ROWS : SK_ROWS) + " sequences decode together)");
+    if (!slots || !heads || B < 1 || B > c->max_B || B > (c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS)) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS) + " sequences decode together)");
     if (max_new < 1 || max_new > c->c.max_new_tokens) return fail(TRACE_ERR_ARG, "max_new exceeds capacity");
     hipStream_t s = (hipStream_t)stream;
     // the shared-prefix request is this call's alone: taken here, whatever the call then answers (one sequence shares with nobody)
@@ -1694,7 +1753,7 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
         // algorithmic bytes of the bracketed launch, by WHICH launch took the bracket (bracket_kind — not by the batch size: the wide step starts at
         // decode.wide_min_rows rows, below SKINNY_ROWS): the gate|up weights (fp8: the bracket also spans the activation quantiser), or the layer-0
         // attention's KV rows averaged over the bracketed steps
-        c->prof[4] = (float)(2.0 * c->I * c->H * (c->fp8 ? 1.0 : 2.0));
+        c->prof[4] = (float)(2.0 * c->I * c->H * (c->w4 ? 0.53125 : c->fp8 ? 1.0 : 2.0));
         if (c->bracket_kind == 3 && c->ksamples) c->prof[4] = (float)(c->kbytes_sum / c->ksamples);
         c->prof[8] = (float)c->bracket_kind;
     }
@@ -2187,6 +2246,22 @@ extern "C" int trace_op_decode_route(int B, int fp8_scheme, int H, int I, int QK
     std::copy(v, v + 8, out);
     return TRACE_OK;
 }
+// the same two for w4 weights (the older entry points keep refusing kind / scheme 3)
+extern "C" int trace_op_skinny_w4_plan(int N, int K, int B, int64_t* out) {
+    if (!out || !skinny_shape_ok(SK_W4A16, N, K, EPI_PARTIAL, B)) return fail(TRACE_ERR_ARG, "the w4 decode GEMV does not take this shape (K % 256, N % 16, B <= 64)");
+    const SkinnyPlan p = skinny_plan(SK_W4A16, N, K, EPI_PARTIAL, B);
+    const int64_t v[11] = {p.KS, p.chunk_units, p.T, p.WPT, p.ntiles, p.grid, p.threads, p.NT, p.NB, (int64_t)p.lds_bytes, (int64_t)skinny_partial_floats(SK_W4A16, N, K)};
+    std::copy(v, v + 11, out);
+    return TRACE_OK;
+}
+extern "C" int trace_op_decode_route_w4(int B, int H, int I, int QKV, int32_t* out) {
+    if (!out || B < 1 || B > SKINNY_ROWS) return fail(TRACE_ERR_ARG, "bad batch (w4 weights decode at most 64 sequences together)");
+    if (H < 256 || I < 256 || H % 256 || I % 256 || QKV < 16 || QKV % 16) return fail(TRACE_ERR_ARG, "bad geometry");
+    const DecodeRoute r = decode_route(B, 3, H, I, QKV, g_tune);
+    const int32_t v[8] = {r.step, (int32_t)r.kind, r.qkv_finish, r.ks_q, r.ks_o, r.ks_g, r.ks_d, r.nsplit};
+    std::copy(v, v + 8, out);
+    return TRACE_OK;
+}
 extern "C" int trace_op_sk_rows(void) { return SK_ROWS; }
 // gate|up of a wide decode step: X [M <= 128, K] . Wt (the 16-row interleaved gate|up matrix in the decode tile layout) -> SwiGLU -> out [M, N/2] bf16
 extern "C" int trace_op_gemm_swiglu_tiled(const void* X, const void* Wt, void* out, int M, int N, int K, int ring, void* stream) {
@@ -2237,6 +2312,35 @@ extern "C" int trace_op_skinny_fp8(const void* X8, const float* sx, const void* 
 }
 extern "C" int trace_op_skinny_w8(const void* X, const void* W8, const float* sw, float* out, int B, int N, int K, void* stream) {
     return op_skinny_e4m3(X, nullptr, W8, sw, out, B, N, K, (hipStream_t)stream);
+}
+
+// ---- w4 path hooks (tests/test_gpu_w4.py) ----
+#define W4_BF16_ONLY() do { if (TRACE_ELEMENT_TYPE != 0) return fail(TRACE_ERR_ARG, "the w4 kernels need the bf16 library"); } while (0)
+extern "C" int trace_op_quant_rows_w4(const void* W, void* codes, void* exps, int N, int K, void* stream) {
+    W4_BF16_ONLY();
+    if (!W || !codes || !exps) return fail(TRACE_ERR_ARG, "null argument");
+    LCHK(launch_quant_rows_w4((const bf16_t*)W, K, (uint8_t*)codes, (uint8_t*)exps, N, K, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_tile_pack_w4(const void* codes, const void* exps, void* tcodes, void* texps, int N, int K, void* stream) {
+    W4_BF16_ONLY();
+    if (!codes || !exps || !tcodes || !texps) return fail(TRACE_ERR_ARG, "null argument");
+    LCHK(launch_tile_pack_w4((const uint8_t*)codes, (const uint8_t*)exps, (uint8_t*)tcodes, (uint8_t*)texps, N, K, 0, 1, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_dequant_w4(const void* tcodes, const void* texps, void* out, int N, int K, void* stream) {
+    W4_BF16_ONLY();
+    if (!tcodes || !texps || !out) return fail(TRACE_ERR_ARG, "null argument");
+    LCHK(launch_dequant_w4((const uint8_t*)tcodes, (const uint8_t*)texps, (bf16_t*)out, K, N, K, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_skinny_w4(const void* X, const void* tcodes, const void* texps, float* out, int B, int N, int K, void* stream) {
+    W4_BF16_ONLY();
+    if (!X || !tcodes || !texps || !out) return fail(TRACE_ERR_ARG, "null argument");
+    if (!skinny_shape_ok(SK_W4A16, N, K, EPI_PARTIAL, B)) return fail(TRACE_ERR_ARG, "the w4 decode GEMV does not take this shape (K % 256, N % 16, B <= 64)");
+    const size_t floats = (size_t)skinny_ks(SK_W4A16, N, K, EPI_PARTIAL, B) * SK_ROWS * N;
+    LCHK(launch_skinny_w4((const bf16_t*)X, K, (const uint8_t*)tcodes, (const uint8_t*)texps, B, N, K, out, floats, (hipStream_t)stream));
+    return TRACE_OK;
 }
 
 // the fused-norm decode GEMV of small batches: part_in [ks_in][sk_rows][K] fp32 + R [B,K] -> xout [B,K] (new residual), out = fp32 partial rows

@@ -159,10 +159,11 @@ int launch_kv_copy(bf16_t* kcache, bf16_t* vtcache, long layer_stride, long slot
 
 // ---- decode (decode.hip) ----
 // The decode GEMVs by operand kind: bf16 weights and activations (launch_skinny_gemm*), e4m3 weights with e4m3 or with bf16 activations (fp8.hip).
-enum SkinnyKind { SK_BF16 = 0, SK_W8A8 = 1, SK_W8A16 = 2 };
+// SK_W4A16: w4 weights (e2m1 codes + a power-of-two scale per 32 k, w4.hip) with bf16 activations.  Unit rule: K % 256 == 0, N % 16 == 0, B <= 64, EPI_PARTIAL only.
+enum SkinnyKind { SK_BF16 = 0, SK_W8A8 = 1, SK_W8A16 = 2, SK_W4A16 = 3 };
 // How one GEMV is cut into workgroups (decode.hip skinny_plan_nb): KS k-chunks of chunk_units units, `grid` workgroups of `threads` threads that take T
 // tiles of 16 NT output rows with WPT waves a tile, NB 16-row activation groups, lds_bytes of dynamic LDS (2 activation images per unit and row group
-// for SK_BF16 / SK_W8A8, 4 for SK_W8A16, + the reduction scratch of WPT > 1).  The fp8 kinds take EPI_PARTIAL only.
+// for SK_BF16 / SK_W8A8, 4 for SK_W8A16, 8 for SK_W4A16, + the reduction scratch of WPT > 1).  The fp8 kinds take EPI_PARTIAL only.
 struct SkinnyPlan { int KS, chunk_units, T, WPT, ntiles, grid, threads, NT, NB; size_t lds_bytes; };
 bool skinny_shape_ok(SkinnyKind kind, int N, int K, int epi, int B);     // false: the kind's launcher answers TRACE_ERR_ARG
 SkinnyPlan skinny_plan(SkinnyKind kind, int N, int K, int epi, int B);
@@ -282,6 +283,18 @@ int launch_skinny_fp8(const uint8_t* X8, long ldx, const float* sx, const uint8_
 // [skinny_ks(SK_W8A16,N,K,EPI_PARTIAL,B)][SK_ROWS][N] = (X . W8^T) * sw[n]
 int launch_skinny_w8(const bf16_t* X, long ldx, const uint8_t* Wtiled, const float* sw, int B, int N, int K, float* ws, size_t ws_floats,
                      hipStream_t s);
+
+// ---- w4 weight path of the decoder (w4.hip; the format is stated in include/trace_hip.h) ----
+// W [N][K] bf16 (row stride ldw) -> logical codes [N][K/2] (k = 2j in the low nibble of byte j) + exponent bytes [N][K/32].  K % 32 == 0, ldw % 8 == 0.
+int launch_quant_rows_w4(const bf16_t* W, long ldw, uint8_t* codes, uint8_t* exps, int N, int K, hipStream_t s);
+// logical codes / exponents of N rows -> tiles tile0, tile0 + tile_step, ... of the decode copy: codes [N/16][K/256][64 lanes][32 B], exponents
+// [N/16][K/256][64 lanes][2]; lane (r = lane & 15, g = lane >> 4) of (tile, unit) holds row tile*16 + r, k = unit*256 + g*64 .. +64.  U = K / 256 of the
+// destination.  N % 16 == 0, K % 256 == 0.
+int launch_tile_pack_w4(const uint8_t* codes, const uint8_t* exps, uint8_t* tcodes, uint8_t* texps, int N, int K, int tile0, int tile_step, hipStream_t s);
+// the decode copy -> row-major 16-bit [N][K] (row stride ldo), exact: what the prefill GEMMs multiply by
+int launch_dequant_w4(const uint8_t* tcodes, const uint8_t* texps, bf16_t* out, long ldo, int N, int K, hipStream_t s);
+// decode GEMV on w4 weights: partial rows [skinny_ks(SK_W4A16,N,K,EPI_PARTIAL,B)][SK_ROWS][N] = X . W~^T in ws
+int launch_skinny_w4(const bf16_t* X, long ldx, const uint8_t* tcodes, const uint8_t* texps, int B, int N, int K, float* ws, size_t ws_floats, hipStream_t s);
 
 // ---- e4m3 KV cache (kv8.hip; the format is stated in include/trace_hip.h) ----
 // The four arrays of one layer: K8 [slot][kvh][ctx_pad][128] bytes, V8 [slot][kvh][ctx_pad/32][128][32] bytes (position-blocked V^T), ks / vs

@@ -41,8 +41,12 @@ class TraceEngine:
 
     def __init__(self, cfg: TraceConfig, device: int = 0, max_batch: int = 1, max_ctx: Optional[int] = None,
                  max_frames: Optional[int] = None, max_new_tokens: int = 1024, vit_batch_frames: Optional[int] = None,
-                 llm_fp8=False, dtype: torch.dtype = torch.bfloat16, kv_cache=None):
-        """kv_cache: None = the KV cache in the 16-bit element type; "fp8" = e4m3 bytes with one fp32 scale per position and kv head (trace_amd/kv8.py:
+                 llm_fp8=False, dtype: torch.dtype = torch.bfloat16, kv_cache=None, llm_w4=False):
+        """llm_w4: True = the four decoder projections of every layer in the 4-bit "w4" format (trace_amd/w4.py, include/trace_hip.h: e2m1 codes with a
+        power-of-two scale per 32 weights), quantised as the weights load and kept as the only copy; prefill dequantises a layer at a time, the decode
+        GEMVs widen the codes in registers.  Both multiply by the same matrix, so prefill_append / enable_prefix_cache() / the shared prefix keep their
+        bit-identity promise.  bf16 only; not with llm_fp8 or kv_cache; at most 64 sequences decode together.
+        kv_cache: None = the KV cache in the 16-bit element type; "fp8" = e4m3 bytes with one fp32 scale per position and kv head (trace_amd/kv8.py:
         264 bytes per position and kv head instead of 512).  Under "fp8" a prefill of whole prompts computes the bits of the 16-bit-cache engine, the
         decode steps attend the quantised rows, and prefill_append / enable_prefix_cache() continue from the QUANTISED prefix: their "bit-identical to
         an uncut prefill" promise is the 16-bit cache's — under "fp8" the guarantee is determinism.  Not with llm_fp8.
@@ -64,6 +68,17 @@ class TraceEngine:
             raise ValueError(f"kv_cache must be None or 'fp8', got {kv_cache!r}")
         if kv_cache and self.fp8_scheme:
             raise ValueError("kv_cache='fp8' with llm_fp8: fp8 weights over an fp8 KV cache is not supported")
+        if llm_w4 not in (False, True, None):
+            raise ValueError(f"llm_w4 must be False or True, got {llm_w4!r}")
+        self.llm_w4 = bool(llm_w4)
+        if self.llm_w4 and self.fp8_scheme:
+            raise ValueError("llm_w4 with llm_fp8: the decoder projections take one quantised format")
+        if self.llm_w4 and kv_cache:
+            raise ValueError("llm_w4 with kv_cache='fp8' is not supported")
+        if self.llm_w4 and dtype != torch.bfloat16:
+            raise ValueError("the w4 weight path exists in the bf16 library only")
+        if self.llm_w4 and (cfg.hidden_size % 256 or cfg.intermediate_size % 256):
+            raise ValueError("the w4 weight path needs hidden / intermediate sizes that are multiples of 256")
         self.kv_cache = kv_cache
         if not torch.cuda.is_available():
             raise _lib.TraceHipError("no HIP device visible: the TRACE hot path only runs on an MI355X (no CPU fallback)")
@@ -91,7 +106,10 @@ class TraceEngine:
             {None: 0, "w8a8": 1, "weight_only": 2}[self.fp8_scheme])
         self.llm_fp8 = self.fp8_scheme is not None
         h = C.c_void_p()
-        if kv_cache:
+        if self.llm_w4:
+            o = _lib.TraceCtxOptsW4C(C.sizeof(_lib.TraceCtxOptsW4C), 0, 1)
+            _lib.check(self.lib.trace_ctx_create_opts(C.byref(c), device, C.cast(C.byref(o), C.POINTER(_lib.TraceCtxOptsC)), C.byref(h)))
+        elif kv_cache:
             o = _lib.TraceCtxOptsC(C.sizeof(_lib.TraceCtxOptsC), 1)
             _lib.check(self.lib.trace_ctx_create_opts(C.byref(c), device, C.byref(o), C.byref(h)))
         else:
@@ -108,8 +126,8 @@ class TraceEngine:
 
     @property
     def decode_batch_max(self) -> int:
-        """sequences one decode batch can hold: the KV slots, at most 256 (64 on the fp8 weight path)"""
-        return min(self.max_batch, 64 if self.llm_fp8 else self.lib.trace_op_sk_rows())
+        """sequences one decode batch can hold: the KV slots, at most 256 (64 on the fp8 and w4 weight paths)"""
+        return min(self.max_batch, 64 if self.llm_fp8 or self.llm_w4 else self.lib.trace_op_sk_rows())
 
     @staticmethod
     def full_round_frames(cfg: TraceConfig) -> int:
@@ -1528,6 +1546,59 @@ class ops:
         _lib.check(lib.trace_op_kv8_unpack(_ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), _ptr(slots), _ptr(k_out), _ptr(vt_out), R, Bn, nkv, k8.shape[0],
                                            max_ctx, _stream()))
         return k_out, vt_out
+
+    # ---- w4 path pieces (the format: trace_amd/w4.py) ----
+    @staticmethod
+    def skinny_w4_plan(N, K, B) -> dict:
+        """trace_op_skinny_w4_plan: skinny_plan for the w4 decode GEMV (units of 256 k)"""
+        out = (C.c_int64 * 11)()
+        _lib.check(_lib.load(ops.element).trace_op_skinny_w4_plan(N, K, B, out))
+        return dict(zip(("KS", "chunk_units", "T", "WPT", "ntiles", "grid", "threads", "NT", "NB", "lds_bytes", "partial_floats"), out))
+
+    @staticmethod
+    def decode_route_w4(B, H, I, QKV) -> dict:
+        """trace_op_decode_route_w4: decode_route for a context on w4 weights"""
+        out = (C.c_int32 * 8)()
+        _lib.check(_lib.load(ops.element).trace_op_decode_route_w4(B, H, I, QKV, out))
+        return dict(zip(("step", "kind", "qkv_finish", "ks_q", "ks_o", "ks_g", "ks_d", "nsplit"), out))
+
+    @staticmethod
+    def quant_rows_w4(W):
+        """W bf16 [N, K] -> (uint8 codes [N, K / 2], uint8 exponent bytes [N, K / 32]) in the logical order"""
+        lib = _lib.load(ops.element)
+        N, K = W.shape
+        codes = torch.empty((N, K // 2), dtype=torch.uint8, device=W.device)
+        exps = torch.empty((N, K // 32), dtype=torch.uint8, device=W.device)
+        _lib.check(lib.trace_op_quant_rows_w4(_ptr(W), _ptr(codes), _ptr(exps), N, K, _stream()))
+        return codes, exps
+
+    @staticmethod
+    def tile_pack_w4(codes, exps):
+        """logical codes / exponents -> the decode tile copies (flat uint8 [N K / 2], [N K / 32])"""
+        lib = _lib.load(ops.element)
+        N, K = codes.shape[0], codes.shape[1] * 2
+        tc, te = torch.empty(N * K // 2, dtype=torch.uint8, device=codes.device), torch.empty(N * K // 32, dtype=torch.uint8, device=codes.device)
+        _lib.check(lib.trace_op_tile_pack_w4(_ptr(codes), _ptr(exps), _ptr(tc), _ptr(te), N, K, _stream()))
+        return tc, te
+
+    @staticmethod
+    def dequant_w4(tcodes, texps, N, K):
+        """the tile copies -> W~ bf16 [N, K], exact"""
+        lib = _lib.load(ops.element)
+        out = torch.empty((N, K), dtype=torch.bfloat16, device=tcodes.device)
+        _lib.check(lib.trace_op_dequant_w4(_ptr(tcodes), _ptr(texps), _ptr(out), N, K, _stream()))
+        return out
+
+    @staticmethod
+    def skinny_w4(X, tcodes, texps, N, out=None):
+        """the w4 decode GEMV: X bf16 [B, K] . W~^T as fp32 k-chunk partial rows [KS, sk_rows, N], written into `out` if one is given (rows >= B of a
+        chunk are not written); the product is out.sum(0)[:B]"""
+        lib = _lib.load(ops.element)
+        Bn, K = X.shape
+        if out is None:
+            out = torch.zeros((ops.skinny_w4_plan(N, K, Bn)["KS"], lib.trace_op_sk_rows(), N), dtype=torch.float32, device=X.device)
+        _lib.check(lib.trace_op_skinny_w4(_ptr(X), _ptr(tcodes), _ptr(texps), _ptr(out), Bn, N, K, _stream()))
+        return out
 
     # ---- fp8 (e4m3) path pieces ----
     @staticmethod

@@ -151,8 +151,11 @@ def apply_generation_config(model, model_path: str) -> None:
 
 def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", use_flash_attn=False, max_batch: int = 1, max_new_tokens: int = 1024, **kwargs):
-    if load_8bit or load_4bit:
-        raise NotImplementedError("bitsandbytes quantised loading is outside the MI355X path")
+    # load_4bit=True (trace/model/builder.py:41-48 there: bitsandbytes NF4) means THIS build's 4-bit format here: the decoder projections as e2m1 codes
+    # with a power-of-two scale per 32 weights (trace_amd/w4.py), quantised from the 16-bit checkpoint as it loads.  Not bitsandbytes' bits.
+    if load_8bit:
+        raise NotImplementedError("bitsandbytes 8-bit loading is outside the MI355X path: the 8-bit options here are kv_cache=\"fp8\" (the e4m3 KV "
+                                  "cache) and TraceEngine(llm_fp8=...) (e4m3 decoder weights); load_4bit=True loads 4-bit decoder weights")
     if model_base is not None or "lora" in model_name.lower():
         raise NotImplementedError("LoRA merge-at-load is outside the accelerated path; merge the adapter offline")
     from ..engine import TraceEngine      # fails loudly without the HIP library / a GPU
@@ -173,7 +176,8 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
     # torch_dtype=torch.float16 selects the fp16 library (libtrace_hip_f16.so)
     dtype = kwargs.get("torch_dtype") or torch.bfloat16
     eng = TraceEngine(cfg, device=dev_index, max_batch=max_batch, max_ctx=max_ctx, max_frames=max(T, 1),
-                      max_new_tokens=max_new_tokens, dtype=dtype, kv_cache=kwargs.get("kv_cache"))      # kv_cache="fp8": the e4m3 KV cache
+                      max_new_tokens=max_new_tokens, dtype=dtype, kv_cache=kwargs.get("kv_cache"),      # kv_cache="fp8": the e4m3 KV cache
+                      llm_w4=bool(load_4bit))
     if raw.get("synthetic_weights"):
         from .. import synth
         small = cfg.hidden_size * cfg.num_hidden_layers < 4096 * 8
