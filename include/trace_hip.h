@@ -230,6 +230,17 @@ int trace_decode_begin(trace_ctx* ctx, const int32_t* slots, int B, const int32_
                        const int32_t* forced, float* logits_out, void* stream);
 int trace_decode_steps(trace_ctx* ctx, int n, int use_graph, float* logits_out, void* stream);
 int trace_decode_read(trace_ctx* ctx, int32_t* out_ids, int32_t* out_len, int32_t* heads, void* stream);
+/* Retire rows of the running batch.  Shrink the batch begun by trace_decode_begin to n_keep rows: new row i is former row keep[i].  keep (HOST) is
+ * strictly increasing, within [0, B).  Everything a step reads or writes per row moves with the row: slot, position, head, done flag, length, the
+ * rows of recorded ids, forced ids and (when armed) log-probabilities, and the embedding the next step consumes.  The Philox row index of a row
+ * stays the index it had at trace_decode_begin, so a sampled row draws what it would have drawn in the full batch.  Results of dropped rows must
+ * have been read (trace_decode_read, trace_decode_read_logprobs) before the call; afterwards those calls return n_keep rows.  The step counter, the
+ * steps taken and max_new stay as they are; a shared prefix stays in force while two rows or more remain.  The next trace_decode_steps runs the step
+ * of the new batch size (a graph of its own, captured the first time that size is seen): on real weights its rounding is that batch size's, as it
+ * is for a batch begun at that size.  n_keep == B is a no-op that launches nothing.  Returns after the stream has run the gather.
+ * TRACE_ERR_STATE: no batch begun; host-select mode.  TRACE_ERR_ARG: n_keep < 1 or > B; an index outside [0, B); a list that is not strictly
+ * increasing.  After an error the batch is as it was. */
+int trace_decode_retire(trace_ctx* ctx, const int32_t* keep, int n_keep, void* stream);
 /* Host-driven token selection (do_sample=True in scripts/inference/inference.py:62, stopping criteria): with host
  * mode on (set before trace_decode_begin), begin/steps stop after the masked head logits; the host picks the ids and
  * trace_decode_feed applies them (output record, head switch, next-token embedding).  One eager step at a time. */

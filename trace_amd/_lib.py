@@ -81,6 +81,7 @@ SIGNATURES = {
     "trace_decode_begin": (I, [P, P, I, P, I, I, P, P, P]),
     "trace_decode_steps": (I, [P, I, I, P, P]),
     "trace_decode_read": (I, [P, P, P, P, P]),
+    "trace_decode_retire": (I, [P, P, I, P]),
     "trace_decode_host_mode": (I, [P, I]),
     "trace_decode_feed": (I, [P, P, I, P]),
     "trace_decode_set_sampling": (I, [P, F, I, F, C.c_uint64]),

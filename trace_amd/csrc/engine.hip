@@ -119,6 +119,9 @@ struct trace_ctx {
     float* part_val; int32_t* part_idx;
     float* hl_val; int32_t* hl_idx;        // trace_llm_head_logits' own partial buffers
     int32_t *d_slots, *d_pos, *d_heads, *d_done, *d_out_ids, *d_out_len, *d_step, *d_forced, *d_params;
+    int32_t* d_row_id = nullptr;       // [SK_ROWS] Philox row index of every row of the batch: identity at trace_decode_begin, gathered by trace_decode_retire
+    int32_t* d_retire = nullptr;       // trace_decode_retire's keep list [SK_ROWS] and scratch rows (allocated at the first retire)
+    int32_t h_pos0[SK_ROWS] = {0};     // host copy: the prefill length of every row of the batch (pos_sum after a retire)
     int32_t* d_heads_tmp;                // head id per row for trace_llm_head_logits
     int B = 0, max_new = 0, eos = -1, has_forced = 0, ntiles = 0, nsplit = 32;
     int slot_len[MAX_SLOTS] = {0};
@@ -498,7 +501,7 @@ static int ctx_create(const trace_config* cfg, int device_id, int kv8, int w4, t
     // trace_llm_head_logits: its own arg-max partials and three constant head-id rows (all 0 / all 1 / all 2), so that it shares nothing with a
     // decode batch in flight on another stream and needs no host copy or synchronisation per call
     A(c->hl_val, (size_t)SK_ROWS * c->ntiles); A(c->hl_idx, (size_t)SK_ROWS * c->ntiles);
-    A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4); A(c->d_sparams, 1); A(c->d_lgparams, 1);
+    A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_row_id, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4); A(c->d_sparams, 1); A(c->d_lgparams, 1);
     A(c->d_out_ids, (size_t)SK_ROWS * cfg->max_new_tokens); A(c->d_forced, (size_t)SK_ROWS * cfg->max_new_tokens);
 #undef A
     if (rc == TRACE_OK && hipHostMalloc((void**)&c->h_ring, Lm * 8 * trace_ctx::NSTAGE_H) != hipSuccess) rc = fail(TRACE_ERR_HIP, "hipHostMalloc");
@@ -1406,7 +1409,7 @@ extern "C" int trace_llm_head_logits(trace_ctx* c, const void* hidden, int R, in
 static StepState step_state(trace_ctx* c) {
     StepState st{};
     st.heads = c->d_heads; st.pos = c->d_pos; st.done = c->d_done; st.out_ids = c->d_out_ids; st.out_len = c->d_out_len;
-    st.step = c->d_step; st.forced = c->d_forced; st.params = c->d_params;
+    st.step = c->d_step; st.forced = c->d_forced; st.params = c->d_params; st.row_id = c->d_row_id;
     return st;
 }
 
@@ -1651,8 +1654,9 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     const int sh_slot = c->sh_want_slot, sh_rows = B > 1 ? c->sh_want_rows : 0;
     c->sh_want_slot = -1; c->sh_want_rows = 0;
     if (sh_rows > 0 && c->slot_len[sh_slot] < sh_rows) return fail(TRACE_ERR_STATE, "the shared slot holds fewer rows than the shared prefix");
-    int32_t pos[SK_ROWS], zero[SK_ROWS] = {0};
+    int32_t pos[SK_ROWS], zero[SK_ROWS] = {0}, iota[SK_ROWS];
     for (int b = 0; b < B; ++b) {
+        iota[b] = b;
         if (slots[b] < 0 || slots[b] >= c->max_B || c->slot_len[slots[b]] <= 0) return fail(TRACE_ERR_STATE, "slot not prefilled");
         if (c->slot_len[slots[b]] < sh_rows) return fail(TRACE_ERR_ARG, "a sequence is shorter than the shared prefix");
         if (heads[b] < 0 || heads[b] > 2) return fail(TRACE_ERR_ARG, "head must be 0, 1 or 2");
@@ -1666,8 +1670,9 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     c->B = B; c->max_new = max_new; c->eos = eos; c->has_forced = forced != nullptr;
     c->sh_slot = sh_rows > 0 ? sh_slot : -1; c->sh_rows = sh_rows;
     c->pos_sum = 0;
-    for (int b = 0; b < B; ++b) c->pos_sum += pos[b];
+    for (int b = 0; b < B; ++b) { c->pos_sum += pos[b]; c->h_pos0[b] = pos[b]; }
     HIPCHK(hipMemcpyAsync(c->d_slots, slots, B * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_row_id, iota, B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_pos, pos, B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_heads, heads, B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_done, zero, B * 4, hipMemcpyHostToDevice, s));
@@ -1757,6 +1762,35 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
         if (c->bracket_kind == 3 && c->ksamples) c->prof[4] = (float)(c->kbytes_sum / c->ksamples);
         c->prof[8] = (float)c->bracket_kind;
     }
+    return TRACE_OK;
+}
+
+// Shrink the running batch to the rows keep[0 .. n_keep): everything a step reads or writes per row moves with the row (retire.hip), the host copy
+// of the batch follows, and the next trace_decode_steps runs (captures, the first time) the step of the new batch size.
+extern "C" int trace_decode_retire(trace_ctx* c, const int32_t* keep, int n_keep, void* stream) {
+    if (!c || c->B < 1) return fail(TRACE_ERR_STATE, "trace_decode_begin not called");
+    if (c->host_mode) return fail(TRACE_ERR_STATE, "trace_decode_retire is not available in host-select mode");
+    const int B = c->B;
+    if (!keep || n_keep < 1 || n_keep > B) return fail(TRACE_ERR_ARG, "n_keep must lie in [1, " + std::to_string(B) + "] (the rows of the running batch)");
+    for (int i = 0; i < n_keep; ++i) {
+        if (keep[i] < 0 || keep[i] >= B) return fail(TRACE_ERR_ARG, "keep[" + std::to_string(i) + "] = " + std::to_string(keep[i]) + " is outside [0, " + std::to_string(B) + ")");
+        if (i && keep[i] <= keep[i - 1]) return fail(TRACE_ERR_ARG, "the keep list must be strictly increasing");
+    }
+    if (n_keep == B) return TRACE_OK;                // every row, in order: nothing moves, nothing is launched
+    hipStream_t s = (hipStream_t)stream;
+    const size_t row_ints = retire_row_ints(c->c.max_new_tokens, c->H);
+    if (!c->d_retire) TRY(dalloc(c, &c->d_retire, SK_ROWS + SK_ROWS * row_ints));
+    RetireArgs a{};
+    a.small[0] = c->d_slots; a.small[1] = c->d_pos; a.small[2] = c->d_heads; a.small[3] = c->d_done; a.small[4] = c->d_out_len; a.small[5] = c->d_row_id;
+    a.wide[0] = c->d_out_ids; a.wide[1] = c->d_forced; a.wide[2] = c->armed.logprobs ? reinterpret_cast<int32_t*>(c->d_logprobs) : nullptr;
+    a.x = c->dX; a.H = c->H; a.max_new = c->max_new;
+    HIPCHK(hipMemcpyAsync(c->d_retire, keep, (size_t)n_keep * 4, hipMemcpyHostToDevice, s));
+    LCHK(launch_retire(a, c->d_retire, n_keep, B, c->d_retire + SK_ROWS, s));
+    HIPCHK(hipStreamSynchronize(s));                 // the caller's keep list must outlive the async copy
+    c->pos_sum = 0;
+    for (int i = 0; i < n_keep; ++i) { c->h_pos0[i] = c->h_pos0[keep[i]]; c->pos_sum += c->h_pos0[i]; }      // (keep[i] >= i: read before overwritten)
+    c->B = n_keep;
+    if (n_keep == 1) { c->sh_slot = -1; c->sh_rows = 0; }      // one sequence shares with nobody (as at trace_decode_begin): its own slot holds the same rows
     return TRACE_OK;
 }
 

@@ -223,7 +223,20 @@ struct StepState {
     int32_t* step;        // [1] device step counter
     const int32_t* forced;// [B, max_new] teacher-forcing ids; negative entry = feed the arg-max
     const int32_t* params;// device [3]: max_new, eos, record_feed (device-resident so a captured graph stays valid)
+    const int32_t* row_id;// [B] the Philox row index of each row (the index it had at trace_decode_begin: trace_decode_retire moves it with the row); null = b
 };
+// Retiring rows of a decode batch (retire.hip): every per-row array of the step, gathered to its first n_keep rows through a scratch copy.
+constexpr int RETIRE_SMALL = 6;
+struct RetireArgs {
+    int32_t* small[RETIRE_SMALL];   // [B] each: slots, pos, heads, done, out_len, row_id
+    int32_t* wide[3];               // [B][max_new] each: out_ids, forced, the log-probabilities' bits (null where not armed)
+    bf16_t* x;                      // [B][H] the next step's input embedding
+    int H, max_new;
+};
+// ints of one scratch row: 8 for the small arrays, three max_new-rows padded to 16 bytes, the embedding row
+__host__ __device__ constexpr size_t retire_row_ints(int max_new, int H) { return 8 + 3 * (size_t)((max_new + 3) & ~3) + (size_t)(H >> 1); }
+// new row i <- former row keep[i] (device int32 [n_keep], strictly increasing within [0, B): the caller checks); scratch: n_keep * retire_row_ints ints, 16-byte aligned
+int launch_retire(const RetireArgs& a, const int32_t* keep, int n_keep, int B, int32_t* scratch, hipStream_t s);
 // The one launcher of select_next_kernel, by form.  SELECT_TILES: the arg-max over launch_head_logits' partials (logits and sp null).  SELECT_SAMPLE:
 // a draw by sample.h's sampler from rows `logits` [B][NV] fp32 (masked, raw or processed) under the device params *sp.  SELECT_ROW: the arg-max
 // over the head's range of such rows, the lowest id among equal maxima as the partials have it (sp null).

@@ -48,7 +48,8 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
         __shared__ SampleLds L;
         int lo, hi;
         head_bounds(st.heads[b], V, Tv, Sv, lo, hi);
-        idx = lo + sample_row(logits + (size_t)b * (V + 1 + Tv + Sv) + lo, hi - lo, *sp, (uint32_t)step, (uint32_t)b, L);
+        idx = lo + sample_row(logits + (size_t)b * (V + 1 + Tv + Sv) + lo, hi - lo, *sp, (uint32_t)step,
+                               (uint32_t)(st.row_id ? st.row_id[b] : b), L);      // (a row keeps the index it had at trace_decode_begin: trace_decode_retire)
     } else {
     if constexpr (MODE == SELECT_ROW) {
         int lo, hi;

@@ -13,6 +13,7 @@ from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
 from .prefix import APPEND_GROUP_MAX, SHARE_PREFIX_MIN_BATCH, group_by_length, shared_prefix_len, split_questions
+from .retire import RETIRE_FRACTION, RetireBook, retire_plan
 from .sampling import Constraints, LogitsParams, SamplingParams, argmax_rows, check_constraints, ends_stopped, sample_rows_host
 from . import scoring
 
@@ -38,6 +39,12 @@ class TraceEngine:
     # Batches of at least this many videos prefill the prompt rows they have in common before <video> once and share them (encode_prefill; the
     # break-even: prefix.SHARE_PREFIX_MIN_BATCH).  An instance may set its own.
     share_prefix_min_batch = SHARE_PREFIX_MIN_BATCH
+    # Decode steps between two looks at the recorded ids under retire_finished=True (decode): a retire happens at such a boundary only.  An instance may
+    # set its own.  With the flag off the loop steps 32 at a time whatever this says.
+    retire_chunk = 32
+    # ... and a retire happens there once at least 1 / retire_fraction of the running rows have finished (retire.retire_plan, where the reason for the
+    # value stands).  An instance may set its own.
+    retire_fraction = RETIRE_FRACTION
 
     def __init__(self, cfg: TraceConfig, device: int = 0, max_batch: int = 1, max_ctx: Optional[int] = None,
                  max_frames: Optional[int] = None, max_new_tokens: int = 1024, vit_batch_frames: Optional[int] = None,
@@ -120,7 +127,12 @@ class TraceEngine:
         self._max_new = 0
         self._stage_ev = None          # stage_timing(): [(kind, event, event)] while on
         self._stage_videos = 0
-        self.stats = {"vit_frames": 0, "prefill_rows": 0, "score_rows": 0}      # frames the tower has run / rows prefilled / rows scored so far (what prefix reuse saves is read off these)
+        # frames the tower has run / rows prefilled / rows scored so far (what prefix reuse saves is read off these) / rows x steps of the decode_steps
+        # calls so far (what retiring finished rows saves is read off that one)
+        self.stats = {"vit_frames": 0, "prefill_rows": 0, "score_rows": 0, "decode_row_steps": 0}
+        self._rows: List[int] = []            # original index (at decode_begin) of every row of the running decode batch
+        self._rows_history: List[List[int]] = []      # _rows after decode_begin and after every retire of the running batch
+        self.retires = 0                      # retire_rows calls that shrank a batch, so far
         self._prefix = None            # (key, rows): KV slot 0 holds `rows` prefilled prompt rows described by `key` (set_prefix_entry); see _drop_prefix
         self._dbg = None               # debugging hook: callable(tag, index, tensor-or-None) called between the stages (tools/pipeline_stress.py)
 
@@ -528,6 +540,8 @@ class TraceEngine:
         if shared_prefix is not None:
             _lib.check(self.lib.trace_decode_set_shared_prefix(self.h, int(shared_prefix[0]), int(shared_prefix[1]) & ~31))
         self._B, self._max_new = B, max_new
+        self._rows = list(range(B))
+        self._rows_history = [list(self._rows)]
         f = None
         if forced is not None:
             flat = []
@@ -544,7 +558,22 @@ class TraceEngine:
         if want_logits:
             lg = torch.empty((self._B, self.cfg.total_vocab), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.trace_decode_steps(self.h, n, 1 if use_graph else 0, _ptr(lg), _stream()))
+        self.stats["decode_row_steps"] += self._B * n
         return lg
+
+    def retire_rows(self, keep: Sequence[int]):
+        """Shrink the running decode batch to the rows at positions `keep` (strictly increasing, within the current batch; trace_decode_retire):
+        everything a step holds per row moves with the row, and a sampled row goes on drawing with the Philox row index it began with.  Read the
+        results of the rows that leave first (decode_read, decode_read_logprobs): afterwards those return len(keep) rows.  self._rows keeps the
+        original index of every live row.  All rows in order = nothing happens.  Not in host-select mode."""
+        keep = [int(k) for k in keep]
+        _lib.check(self.lib.trace_decode_retire(self.h, _i32(keep), len(keep), _stream()))
+        shrunk = len(keep) != self._B
+        self._rows = [self._rows[k] for k in keep]
+        self._B = len(keep)
+        if shrunk:
+            self.retires += 1
+            self._rows_history.append(list(self._rows))
 
     def decode_read(self):
         B, mn = self._B, self._max_new
@@ -753,8 +782,14 @@ class TraceEngine:
 
     def decode(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
                forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-               logits: Optional[LogitsParams] = None, shared_prefix=None, constraints: Optional[Constraints] = None):
+               logits: Optional[LogitsParams] = None, shared_prefix=None, constraints: Optional[Constraints] = None, retire_finished: bool = False):
         """Stage 2 of generate(): the decode loop over prefilled KV slots, on the current stream -> (ids per sequence, final heads).
+        retire_finished: every retire_chunk steps the rows whose recorded ids end in EOS or a stop sequence leave the running batch (retire_rows, when
+        retire.retire_plan says it pays), so the later steps attend and project the live rows only; the result has every row, in its original order,
+        shaped as with the flag off.  A row's ids, length and log-probabilities are a function of its own logits: on a decoder whose logits do not
+        depend on rounding they are the flag-off ones exactly, sampled draws included; on real weights a row that decodes on in a smaller batch sees
+        that batch size's rounding.  The returned head of a retired row is the one it had when it left.  Off (the default):
+        today's loop, launches and graphs.  ValueError with sampling parameters outside the device sampler's domain (they run the host loop).
         constraints: bad words / suppressed ids / stop sequences (Constraints; None or all off = today's launches and graphs), inside the decode
         step like `logits` (set_constraints); not together with forced ids.
         shared_prefix: what encode_prefill returned for these slots (decode_begin: the attention reads the shared rows from one slot; same results).
@@ -773,6 +808,9 @@ class TraceEngine:
             check_constraints(constraints.stop_sequences, constraints.bad_words_ids, constraints.suppress_tokens, constraints.begin_suppress_tokens,
                               self.cfg.total_vocab)
         if sampling is not None and not sampling.greedy and not sampling.on_device:
+            if retire_finished:
+                raise ValueError("retire_finished=True needs the device decode loop: these sampling parameters lie outside the device sampler's "
+                                 "domain and run one host-selected step at a time")
             return self.decode_stepwise(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits, shared_prefix=shared_prefix,
                                         constraints=constraints)
         on_dev = sampling is not None and not sampling.greedy
@@ -785,7 +823,8 @@ class TraceEngine:
         try:
             if bound:
                 self.set_constraints(constraints)
-            return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs, shared_prefix, constraints if bound else None)
+            return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs, shared_prefix, constraints if bound else None,
+                                retire_finished)
         finally:
             if bound:
                 self.set_constraints(None)
@@ -798,7 +837,8 @@ class TraceEngine:
 
     def decode_stepwise(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1,
                         forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-                        logits: Optional[LogitsParams] = None, stopping=None, shared_prefix=None, constraints: Optional[Constraints] = None):
+                        logits: Optional[LogitsParams] = None, stopping=None, shared_prefix=None, constraints: Optional[Constraints] = None,
+                        retire_finished: bool = False):
         """decode() one eager step at a time with the token picked on the host: the one loop in host-select mode (sampling parameters outside the
         device sampler's domain, stopping criteria).  Every rule is the device step's.  The row the pick reads is the processed one
         (logits_process: the history is the ids recorded so far) when `logits` is armed, else the raw one; sampled rows go through sample(),
@@ -809,7 +849,10 @@ class TraceEngine:
         one bool per row, asked after every step but the last while some row is unfinished; a row it fired for keeps the ids (and log-probabilities) it held then,
         while its returned head is the whole run's: the device goes on feeding it, as it does a row past its EOS.  The greedy pick is taken on the
         device (sampling.argmax_rows: B ids come back); the recorded ids are read back after every step, since both finished rules look at them.  The
-        loop ends when every row is finished or max_new_tokens ids were fed.  Returns what decode() returns."""
+        loop ends when every row is finished or max_new_tokens ids were fed.  Returns what decode() returns.
+        retire_finished=True is a ValueError: host-select mode has no step graph and trace_decode_retire does not serve it."""
+        if retire_finished:
+            raise ValueError("retire_finished=True needs the device decode loop; decode_stepwise runs in host-select mode")
         B, cfg = len(slots), self.cfg
         greedy = sampling is None or sampling.greedy
         armed = logits is not None and not logits.off
@@ -856,37 +899,46 @@ class TraceEngine:
         finally:
             self.host_mode(False)
 
-    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False, shared_prefix=None, constraints=None):
+    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False, shared_prefix=None, constraints=None, retire_finished=False):
         self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, shared_prefix=shared_prefix)
+        read_lps = lambda ids: self.decode_read_logprobs([len(x) for x in ids]) if logprobs else None
+        book = RetireBook(len(slots), logprobs) if retire_finished else None
         if max_new_tokens > 1:
             if eos < 0 and not (constraints is not None and constraints.stop_sequences):
-                self.decode_steps(max_new_tokens - 1, use_graph)
+                self.decode_steps(max_new_tokens - 1, use_graph)        # (no row can finish: nothing to look at between the steps, nothing to retire)
             else:
-                done, chunk = 0, 32
+                done, chunk = 0, max(1, int(self.retire_chunk)) if retire_finished else 32
                 while done < max_new_tokens - 1:
                     n = min(chunk, max_new_tokens - 1 - done)
                     self.decode_steps(n, use_graph)
                     done += n
-                    ids, _ = self.decode_read()
-                    if all(ends_stopped(x, eos, constraints) for x in ids):
+                    ids, hd = self.decode_read()
+                    finished = [ends_stopped(x, eos, constraints) for x in ids]
+                    if all(finished):
                         break
+                    if book is not None and done < max_new_tokens - 1 and retire_plan(len(ids), finished.count(False), self.retire_fraction):
+                        keep = book.keep_list(finished)
+                        book.retire(keep, ids, hd, read_lps(ids))
+                        self.retire_rows(keep)
         ids, hd = self.decode_read()
-        return (ids, hd, self.decode_read_logprobs([len(x) for x in ids])) if logprobs else (ids, hd)
+        if book is not None:
+            return book.result(ids, hd, read_lps(ids))
+        return (ids, hd, read_lps(ids)) if logprobs else (ids, hd)
 
     def generate(self, videos: Sequence[torch.Tensor], timestamps: Sequence, input_ids: Sequence[Sequence[int]],
                  heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
                  forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-                 logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None):
+                 logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None, retire_finished: bool = False):
         B = len(videos)
         if B > self.decode_batch_max:
             raise ValueError(f"batch {B} exceeds the engine's decode batch {self.decode_batch_max}")
         shared = self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
         return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits, shared_prefix=shared,
-                           constraints=constraints)
+                           constraints=constraints, retire_finished=retire_finished)
 
     def generate_samples(self, video: torch.Tensor, timestamps, prompt_ids: Sequence[int], head: int, n: int, max_new_tokens: int, eos: int = -1,
                          sampling: Optional[SamplingParams] = None, use_graph: bool = True, logits: Optional[LogitsParams] = None,
-                         constraints: Optional[Constraints] = None):
+                         constraints: Optional[Constraints] = None, retire_finished: bool = False):
         """n sampled continuations of ONE prompt from one tower pass and one prefill: the prompt is encoded and prefilled into KV slot 0, its rows
         are copied to slots 1 .. n - 1 (kv_copy), and slots 0 .. n - 1 decode as one batch with log-probabilities on.  Row r draws with Philox
         row index r, as any decode batch does, so the result equals generate() of the prompt repeated n times with the same SamplingParams:
@@ -900,12 +952,13 @@ class TraceEngine:
         self.prefill(0, L)
         if n > 1:
             self.kv_copy(0, list(range(1, n)), L)
-        return self.decode(range(n), [int(head)] * n, max_new_tokens, eos, use_graph, None, sampling, logprobs=True, logits=logits, constraints=constraints)
+        return self.decode(range(n), [int(head)] * n, max_new_tokens, eos, use_graph, None, sampling, logprobs=True, logits=logits, constraints=constraints,
+                           retire_finished=retire_finished)
 
     def generate_questions(self, video: torch.Tensor, timestamps, prompts: Sequence[Sequence[int]], heads: Sequence[int], max_new_tokens: int,
                            eos: int = -1, sampling: Optional[SamplingParams] = None, use_graph: bool = True,
                            forced: Optional[Sequence[Sequence[int]]] = None, prefix_key=None, logprobs: bool = False,
-                           logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None):
+                           logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None, retire_finished: bool = False):
         """generate() for Q prompts about ONE video whose ids agree up to and including the <video> placeholder (the reference's per-question
         loops, trace/eval/videomme/evaluate.py:349-386): the tower, the slot pool and the prefill of the common prefix run once (slot 0), the
         prefix's KV rows are copied to the other Q - 1 slots, each prompt's rows after <video> are appended (one pass per group of equal
@@ -936,7 +989,8 @@ class TraceEngine:
                     slot += 1
         if prefix_key is not None:
             self.set_prefix_entry(prefix_key, P)
-        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits, constraints=constraints)
+        return self.decode(slot_of, heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits, constraints=constraints,
+                           retire_finished=retire_finished)
 
     # ---- two-stage pipeline over a stream of batches ---------------------------------------------------
     def make_streams(self, decode_cus: int = 0):
@@ -958,11 +1012,11 @@ class TraceEngine:
 
     def generate_stream(self, batches: Iterable, max_new_tokens: int, eos: int = -1, use_graph: bool = True, streams=None,
                         sampling: Optional[SamplingParams] = None, logprobs: bool = False, logits: Optional[LogitsParams] = None,
-                        constraints: Optional[Constraints] = None):
+                        constraints: Optional[Constraints] = None, retire_finished: bool = False):
         """generate() over a stream of batches as a two-stage pipeline: while batch k decodes (HBM-bound) on one stream, batch k+1
         runs its ViT + slot pool + prefill (MFMA-bound) on another, into the other half of the KV slots.  `batches` yields
         (videos, timestamps, input_ids, heads, forced-or-None); yields generate()'s result per batch, in order.  Every batch holds at
-        most max_batch // 2 videos.  sampling / logits / constraints: as decode(), the same params (and seed) for every batch.  Results are identical to generate() batch by batch: the stages share no buffers (KV banks,
+        most max_batch // 2 videos.  sampling / logits / constraints: as decode(), the same params (and seed) for every batch; retire_finished: as decode(), for every batch.  Results are identical to generate() batch by batch: the stages share no buffers (KV banks,
         prefill / ViT scratch vs decode scratch) and every kernel's reductions have a fixed order.
 
         The decode stage is issued from a worker thread: one decode batch is ~75 k kernel dispatches, far more than a HIP stream's
@@ -982,7 +1036,7 @@ class TraceEngine:
                 dec_s.wait_event(ready)
                 # (logprobs: read inside this job, right after the ids — decode() returns them, nothing goes through engine state afterwards)
                 return self.decode(range(bank * half, bank * half + B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs,
-                                   logits=logits, shared_prefix=shared, constraints=constraints)
+                                   logits=logits, shared_prefix=shared, constraints=constraints, retire_finished=retire_finished)
 
         pending = None                                  # (bank, heads, forced, B, ready event, shared prefix): prefilled, waiting for its decode
         bank = 0

@@ -164,8 +164,13 @@ class TraceMistralForCausalLM:
                  modal_list=None, heads=None, max_new_tokens: int = 128, do_sample: Optional[bool] = None,
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None, generation_config=None,
                  eos_token_id=None, pad_token_id: Optional[int] = None, stopping_criteria=None,
-                 use_cache: bool = True, attention_mask=None, position_ids=None, output_logprobs: bool = False, **kwargs):
-        """do_sample / temperature / top_k / top_p: explicit values, else `generation_config`'s, else this model's defaults (HF's: greedy,
+                 use_cache: bool = True, attention_mask=None, position_ids=None, output_logprobs: bool = False, retire_finished: bool = False,
+                 **kwargs):
+        """retire_finished=True: rows that have ended (EOS, a stop sequence) leave the running decode batch at chunk boundaries, so a batch of short
+        and long answers stops paying for the short ones (TraceEngine.decode); the returned tensor has the same shape and rows.  Identical ids where
+        the logits do not depend on rounding; on real weights a row that decodes on in a smaller batch sees that batch size's rounding
+        (INTEGRATION.md 2a).  ValueError with stopping_criteria= and on the legacy STC path (both run the host loop).
+        do_sample / temperature / top_k / top_p: explicit values, else `generation_config`'s, else this model's defaults (HF's: greedy,
         1.0, 50, 1.0, or the checkpoint's generation_config.json).  repetition_penalty / no_repeat_ngram_size / min_new_tokens: the same
         precedence; HF's processors in HF's order on the device, inside the decode step (trace_amd/csrc/logits.h).  Their history is the ids a row
         has generated so far, never the prompt (the reference hands HF inputs_embeds), as global vocabulary ids: a time or score digit emitted
@@ -189,6 +194,8 @@ class TraceMistralForCausalLM:
         lg = {} if lgp is None else {"logits": lgp}              # handed on only when armed
         if cons is not None:
             lg["constraints"] = cons
+        if retire_finished:
+            lg["retire_finished"] = True                        # handed on only when on
         if images_or_videos is None:
             raise NotImplementedError("text-only generation is outside the accelerated path")
         cfg, eng = self.config, self.engine
@@ -211,6 +218,8 @@ class TraceMistralForCausalLM:
         id_lists = [row.tolist() for row in ids]
         if B > eng.max_batch:
             raise ValueError(f"batch {B} exceeds the engine's max_batch {eng.max_batch}")
+        if retire_finished and (legacy_stc or stopping_criteria):
+            raise ValueError("retire_finished=True needs the device decode loop: not with stopping_criteria= or on the legacy STC path")
         if legacy_stc:
             # legacy trace.infer() flow (trace/__init__.py:23-75): STC connector, no time tokens, text head only
             for b in range(B):
@@ -238,12 +247,14 @@ class TraceMistralForCausalLM:
     @torch.no_grad()
     def generate_samples(self, inputs=None, images_or_videos=None, video_timestamps=None, n: int = 1, heads=None, max_new_tokens: int = 128,
                          temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None, generation_config=None,
-                         eos_token_id=None, pad_token_id: Optional[int] = None, modal_list=None, best_first: bool = True, **kwargs):
+                         eos_token_id=None, pad_token_id: Optional[int] = None, modal_list=None, best_first: bool = True, retire_finished: bool = False,
+                         **kwargs):
         """n sampled continuations of ONE prompt, ranked: the tower, the slot pool and the prefill run once (TraceEngine.generate_samples), the n
         rows decode as one batch with per-token log-probabilities.  Sampling arguments as generate(do_sample=True) (the seed comes from
         torch's default generator the same way); greedy parameters are a ValueError.  Returns `.sequences` [n, len] (padded as generate()),
         `.logprobs` float32 [n, len] (zero padded), `.scores` float64 [n] (each row's sum, accumulated in float64 from the float32 entries),
-        `.order` (the decode-row index of each returned row) and `.heads`.  best_first: rows sorted by descending score, ties to the lower
+        `.order` (the decode-row index of each returned row) and `.heads`.  retire_finished: as generate() (a row keeps its Philox row index when others
+        leave: the draws are the full batch's).  best_first: rows sorted by descending score, ties to the lower
         decode row; otherwise decode order."""
         if images_or_videos is None or video_timestamps is None:
             raise ValueError("generate_samples takes one video with its timestamps")
@@ -266,7 +277,8 @@ class TraceMistralForCausalLM:
         self._live_kv = None
         x = self._as_frames(images_or_videos[0], (modal_list or ["video"])[0])
         out, new_heads, lps = eng.generate_samples(x, video_timestamps[0], ids[0].tolist(), head, n, max_new_tokens, eos=eos, sampling=sampling,
-                                                   **({} if lgp is None else {"logits": lgp}), **({} if cons is None else {"constraints": cons}))
+                                                   **({} if lgp is None else {"logits": lgp}), **({} if cons is None else {"constraints": cons}),
+                                                   **({"retire_finished": True} if retire_finished else {}))
         scores = np.array([np.sum(np.asarray(r, np.float32), dtype=np.float64) for r in lps], np.float64)
         order = rank_samples(scores) if best_first else list(range(n))
         seq, lp = self._padded([out[r] for r in order], [lps[r] for r in order], eos if pad_token_id is None else pad_token_id)
