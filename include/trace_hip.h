@@ -468,11 +468,21 @@ int trace_op_gemm_fp8(const void* A8, const float* sa, const void* W8, const flo
 int trace_op_skinny_fp8(const void* X8, const float* sx, const void* W8, const float* sw, float* out, int B, int N, int K, void* stream);
 /* the weight-only decode GEMV: X bf16 [B,K] . (e4m3 W8 [N,K] widened to bf16)^T * sw[n] -> fp32 out [B,N] */
 int trace_op_skinny_w8(const void* X, const void* W8, const float* sw, float* out, int B, int N, int K, void* stream);
-/* out[b][j] = bf16(silu(sum_ks gate) * sum_ks up) from partial rows [KS][64][N2] of the 16-row interleaved gate|up GEMV */
+/* out[b][j] = bf16(silu(sum_ks gate) * sum_ks up) from partial rows [KS][trace_op_sk_rows()][N2] of the 16-row interleaved gate|up GEMV */
 int trace_op_swiglu_combine(const float* part, int KS, int N2, void* out, int B, void* stream);
 /* x = bf16(sum_ks part[ks][b][:]) + R[b][:] -> xout;  y = RMSNorm(x) * w   (decode residual add + norm, N <= 4096) */
 int trace_op_add_rmsnorm(const float* part, int KS, const void* R, void* xout, const void* w, void* y, int B, int N,
                          float eps, void* stream);
+/* The same kernel as the decode step calls it: row strides ldr / ldx / ldy (elements, multiples of 4), xout may be R (in place, the engine's form),
+   KS chunks read of part [>= KS][trace_op_sk_rows()][N], and y8 [B][N] e4m3 bytes + sy [B] fp32 = the rule of trace_op_quant_rows_fp8 applied to
+   y (both NULL: not written; one NULL: TRACE_ERR_ARG).  TRACE_ERR_ARG before any launch: N % 4, N > 4096, B outside 1..trace_op_sk_rows(), KS < 1,
+   a stride that is no multiple of 4 or below N, and y8 / sy in the fp16 library (it has no fp8 weight path). */
+int trace_op_add_rmsnorm_ex(const float* part, int KS, const void* R, int ldr, void* xout, int ldx, const void* w, void* y, int ldy, void* y8,
+                            float* sy, int B, int N, float eps, void* stream);
+/* The down GEMV of 1..4 rows with SwiGLU folded in: part_gu [ks_gu][sk_rows][2 K] fp32 (partial rows of the 16-row interleaved gate|up GEMV) ->
+   out = fp32 partial rows [trace_op_skinny_ks(N,K,4,B)][sk_rows][N] of el(silu(sum gate) * sum up) . W^T (W row-major [N][K]; packed internally).
+   TRACE_ERR_ARG: B outside 1..4, K % 64, N % 16, N < 16, ks_gu < 1, a null argument. */
+int trace_op_skinny_fused_swiglu(const float* part_gu, int ks_gu, const void* W, float* out, int B, int N, int K, void* stream);
 /* kcache [B, nkv, max_ctx, 128] row-major; vtcache [B, nkv, 128, max_ctx] = V transposed (the engine's cache layout,
    max_ctx % 32 == 0); pos[b] = newest position, already in both caches; q [B, nq*128] rotated; ws B*nq*nsplit*130 floats.
    The kernel fetches whole 32-position blocks: positions pos[b] + 1 .. the next multiple of 32 are READ (their scores are masked

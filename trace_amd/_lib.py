@@ -132,6 +132,8 @@ SIGNATURES = {
     "trace_op_skinny_w8": (I, [P, P, P, P, I, I, I, P]),
     "trace_op_swiglu_combine": (I, [P, I, I, P, I, P]),
     "trace_op_add_rmsnorm": (I, [P, I, P, P, P, P, I, I, F, P]),
+    "trace_op_add_rmsnorm_ex": (I, [P, I, P, I, P, I, P, P, I, P, P, I, I, F, P]),
+    "trace_op_skinny_fused_swiglu": (I, [P, I, P, P, I, I, I, P]),
     "trace_op_sample": (I, [P, I, I, P, I, I, I, F, I, F, C.c_uint64, P, P, P]),
     "trace_op_token_logprob": (I, [P, I, I, P, I, I, I, P, P, P]),
     "trace_op_logits_process": (I, [P, I, I, P, I, I, I, P, I, P, P, I, F, I, I, P, P]),

@@ -28,6 +28,15 @@ __device__ __forceinline__ uint4 ldg_nt(const bf16_t* p) {
 }
 union Frag { uint4 u; bf16x8_t v; };
 
+// silu(g) * u of the decode step's two SwiGLU row kernels (swiglu_combine_kernel and the SwiGLU prologue): g / (1 + exp(-g)) * u, the expression of
+// every SwiGLU epilogue here — except where exp(-g) overflows fp32 (g < -88.7): the quotient would be -0 although silu(g) = g e^g (-2e-37 at -89)
+// is still a bf16 number.  There e^g is taken as e^(g + 64) e^-64, so that no factor is subnormal.  No other gate's bits change.
+__device__ __forceinline__ float silu_mul(float g, float u) {
+    const float e = __expf(-g);
+    if (__builtin_expect(__builtin_isinf(e), 0)) return g * __expf(g + 64.f) * 1.6038109e-28f * u;
+    return g / (1.f + e) * u;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // skinny_lds: decode GEMV with the ACTIVATIONS STATIONARY IN LDS.
 // History: the first version gave every workgroup 16 weight rows and all of K, and read X (B x K bf16, L2-resident)
@@ -204,8 +213,8 @@ __global__ __launch_bounds__(512) void skinny_lds_kernel(const bf16_t* __restric
                 float o[8];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    o[e] = g0[e] / (1.f + __expf(-g0[e])) * u0[e];
-                    o[4 + e] = g1[e] / (1.f + __expf(-g1[e])) * u1[e];
+                    o[e] = silu_mul(g0[e], u0[e]);
+                    o[4 + e] = silu_mul(g1[e], u1[e]);
                 }
                 const u32x4_t y = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7])};
                 // fragment order, as in the RMSNorm prologue: combo (unit, half) -> 1 KB image, lane (r = b, g): X[b][unit*64 + g*16 + half*8 .. +8]
@@ -401,7 +410,7 @@ __global__ __launch_bounds__(256) void swiglu_combine_kernel(const float* __rest
     }
     float o[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = gt[e] / (1.f + __expf(-gt[e])) * up[e];
+    for (int e = 0; e < 4; ++e) o[e] = silu_mul(gt[e], up[e]);
     *reinterpret_cast<uint2*>(out + (size_t)b * ldo + j4 * 4) = make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
 }
 
@@ -471,7 +480,7 @@ __global__ __launch_bounds__(1024) void add_rmsnorm_kernel(const float* __restri
     }
     if (y8) {
         // fp8 weight path: the next GEMV's activations, quantised here exactly as fp8.hip's quant_rows_fp8 would from y (per-row amax of
-        // the bf16-rounded values, q = rne(y * 448 / amax)) — saves that launch
+        // the bf16-rounded values, q = rne(y * 448 / amax), rows below 2^-100 scaled by 2^64 before the reciprocal) — saves that launch
         float am = on ? fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) : 0.f;
         am = wave_max(am);
         if ((tid & 63) == 0) s_amax[tid >> 6] = am;
@@ -479,12 +488,13 @@ __global__ __launch_bounds__(1024) void add_rmsnorm_kernel(const float* __restri
         am = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) am = fmaxf(am, s_amax[i]);
-        const float inv = am > 0.f ? 448.f / am : 1.f;
+        const float pre = (am > 0.f && am < 0x1p-100f) ? 0x1p64f : 1.f;
+        const float inv = am > 0.f ? 448.f / (am * pre) : 1.f;
         if (tid == 0) sy[b] = am > 0.f ? am / 448.f : 1.f;
         if (on) {
             float f[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf(v[e] * inv, -448.f), 448.f);
+            for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf(v[e] * pre * inv, -448.f), 448.f);
             int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
             w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
             *reinterpret_cast<int*>(y8 + (size_t)b * N + c * 4) = w;

@@ -2409,6 +2409,35 @@ extern "C" int trace_op_add_rmsnorm(const float* part, int KS, const void* R, vo
                             (hipStream_t)stream));
     return TRACE_OK;
 }
+// the same launcher with everything the decode step passes it: row strides, xout == R, the e4m3 copy of y (y8 / sy) and an explicit chunk count
+extern "C" int trace_op_add_rmsnorm_ex(const float* part, int KS, const void* R, int ldr, void* xout, int ldx, const void* w, void* y, int ldy, void* y8,
+                                       float* sy, int B, int N, float eps, void* stream) {
+    if (!part || !R || !xout || !w || !y) return fail(TRACE_ERR_ARG, "null argument");
+    if ((y8 == nullptr) != (sy == nullptr)) return fail(TRACE_ERR_ARG, "y8 and sy go together");
+    if (y8 && TRACE_ELEMENT_TYPE != 0) return fail(TRACE_ERR_ARG, "y8 / sy need the bf16 library (the fp16 build has no fp8 weight path)");
+    if (N < 4 || ldr < N || ldx < N || ldy < N) return fail(TRACE_ERR_ARG, "row strides below N");
+    LCHK(launch_add_rmsnorm(part, KS, (const bf16_t*)R, ldr, (bf16_t*)xout, ldx, (const bf16_t*)w, (bf16_t*)y, ldy, B, N, eps, (hipStream_t)stream,
+                            (uint8_t*)y8, sy));
+    return TRACE_OK;
+}
+// the SwiGLU-prologue decode GEMV of small batches: part_gu [ks_gu][sk_rows][2 K] fp32 -> out = fp32 partial rows [trace_op_skinny_ks(N,K,4,B)][sk_rows][N] of
+// el(silu(sum gate) * sum up) . W^T (W row-major here; packed internally)
+extern "C" int trace_op_skinny_fused_swiglu(const float* part_gu, int ks_gu, const void* W, float* out, int B, int N, int K, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!part_gu || !W || !out) return fail(TRACE_ERR_ARG, "null argument");
+    if (B < 1 || B > 4 || ks_gu < 1 || !skinny_shape_ok(SK_BF16, N, K, EPI_PARTIAL, B)) return fail(TRACE_ERR_ARG, "shape not supported by the fused-SwiGLU GEMV");
+    bf16_t* wt = nullptr; float* ws = nullptr;
+    const size_t wsf = skinny_ws_floats(N, K, EPI_PARTIAL);
+    HIPCHK(hipMalloc((void**)&wt, (size_t)N * K * 2));
+    if (hipMalloc((void**)&ws, wsf * 4) != hipSuccess) { hipFree(wt); return fail(TRACE_ERR_HIP, "workspace allocation failed"); }
+    int rc = launch_tile_pack((const bf16_t*)W, K, wt, N, K, s);
+    if (rc == TRACE_OK) rc = launch_skinny_gemm_fused_swiglu(part_gu, ks_gu, wt, B, N, K, ws, wsf, s);
+    if (rc == TRACE_OK && hipMemcpyAsync(out, ws, (size_t)skinny_ks(SK_BF16, N, K, EPI_PARTIAL, B) * SK_ROWS * N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = TRACE_ERR_HIP;
+    hipStreamSynchronize(s);
+    hipFree(wt); hipFree(ws);
+    if (rc != TRACE_OK) return fail(rc, "fused-SwiGLU GEMV failed");
+    return TRACE_OK;
+}
 // kcache [B, nkv, max_ctx, 128]; vtcache [B, nkv, 128, max_ctx] (V transposed; max_ctx % 32 == 0); pos[b] = index of the
 // newest token (ctx = pos+1), already in the caches; q [B, nq*128] ready (rotated).  ws: B*nq*nsplit*130 floats.
 // The identity slots and the ticket counters of the decode-attention hooks hold SK_ROWS rows x OP_ATTN_MAX_KV kv heads: a launch is refused unless it fits them.

@@ -26,7 +26,9 @@ __device__ __forceinline__ uint32_t cvt4_fp8(float a, float b, float c, float d)
 }
 
 // X [rows][K] bf16 (row stride ldx) -> X8 [rows][K] e4m3 bytes (row stride ld8) + sx[row] = amax / 448 (1 for an all-zero row).
-// q = rne(x * (448 / amax)), |x * inv| <= 448 by construction (clamped against the last-ulp case).  One workgroup per row; the
+// q = rne(x * (448 / amax)), |x * inv| <= 448 by construction (clamped against the last-ulp case).  A row with 0 < amax < 448 / FLT_MAX
+// (1.3e-36) would make the reciprocal infinite and its zeros NaN, which the clamp turns into -448: rows below 2^-100 are scaled by 2^64 first
+// (exact; x * 1.f leaves every other row's bits alone), so zeros stay zeros and sx stays amax / 448.  One workgroup per row; the
 // row stays in registers between the amax pass and the conversion (K <= 16384).
 __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __restrict__ X, long ldx, uint8_t* __restrict__ X8, long ld8,
                                                              float* __restrict__ sx, int K) {
@@ -53,7 +55,8 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
     __syncthreads();
     amax = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
     const float scale = amax > 0.f ? amax / FP8_MAX : 1.f;
-    const float inv = amax > 0.f ? FP8_MAX / amax : 1.f;
+    const float pre = (amax > 0.f && amax < 0x1p-100f) ? 0x1p64f : 1.f;
+    const float inv = amax > 0.f ? FP8_MAX / (amax * pre) : 1.f;
     if (tid == 0) sx[row] = scale;
     uint8_t* qr = X8 + (size_t)row * ld8;
 #pragma unroll
@@ -64,8 +67,8 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
             float f[8];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                f[2 * e] = fminf(fmaxf(bflo(u[e]) * inv, -FP8_MAX), FP8_MAX);
-                f[2 * e + 1] = fminf(fmaxf(bfhi(u[e]) * inv, -FP8_MAX), FP8_MAX);
+                f[2 * e] = fminf(fmaxf(bflo(u[e]) * pre * inv, -FP8_MAX), FP8_MAX);
+                f[2 * e + 1] = fminf(fmaxf(bfhi(u[e]) * pre * inv, -FP8_MAX), FP8_MAX);
             }
             *reinterpret_cast<uint2*>(qr + (size_t)c * 8) = make_uint2(cvt4_fp8(f[0], f[1], f[2], f[3]), cvt4_fp8(f[4], f[5], f[6], f[7]));
         }

@@ -1448,12 +1448,13 @@ class ops:
         return out
 
     @staticmethod
-    def skinny_fused_norm(part_in, R, w, eps, W):
-        """(xout, out-partials): xout = bf16(sum_k part_in[k, :B]) + R; partial rows [ks, sk_rows, N] of RMSNorm(xout; w) . W^T  (B <= 4)"""
+    def skinny_fused_norm(part_in, R, w, eps, W, KS=None):
+        """(xout, out-partials): xout = bf16(sum_k part_in[k, :B]) + R; partial rows [ks, sk_rows, N] of RMSNorm(xout; w) . W^T  (B <= 4).
+        KS: chunks of part_in to read (default: all the tensor holds)"""
         lib = _lib.load(ops.element)
         Bn, K = R.shape
         N = W.shape[0]
-        ks_in = 0 if part_in is None else part_in.shape[0]
+        ks_in = 0 if part_in is None else (part_in.shape[0] if KS is None else int(KS))
         xout = torch.empty_like(R)
         out = torch.zeros((lib.trace_op_skinny_ks(N, K, EPI_PARTIAL, Bn), lib.trace_op_sk_rows(), N), dtype=torch.float32, device=R.device)
         _lib.check(lib.trace_op_skinny_fused_norm(_ptr(part_in), ks_in, _ptr(R), _ptr(xout), _ptr(w), eps, _ptr(W), _ptr(out), Bn, N, K, _stream()))
@@ -1493,6 +1494,46 @@ class ops:
         x, y = torch.empty_like(R), torch.empty_like(R)
         _lib.check(lib.trace_op_add_rmsnorm(_ptr(part), part.shape[0], _ptr(R), _ptr(x), _ptr(w), _ptr(y), Bn, N, eps, _stream()))
         return x, y
+
+    @staticmethod
+    def add_rmsnorm_ex(part, R, w, eps, KS=None, xout=None, y=None, fp8=False):
+        """trace_op_add_rmsnorm_ex.  part fp32 [>= KS, sk_rows, N] (KS=None: every chunk of the tensor); R, `xout`, `y` [B, N], strided views allowed
+        (unit column stride; a view's row stride is what the kernel gets); xout=None / y=None: fresh contiguous tensors; xout may be R (in place, the
+        engine's form).  fp8: also the e4m3 bytes and row scales of y.  Returns (xout, y) or (xout, y, y8, sy)."""
+        lib = _lib.load(ops.element)
+        ops._rows2d(R, "R")
+        Bn, N = R.shape
+        x = torch.empty((Bn, N), dtype=R.dtype, device=R.device) if xout is None else ops._rows2d(xout, "xout")
+        yy = torch.empty((Bn, N), dtype=R.dtype, device=R.device) if y is None else ops._rows2d(y, "y")
+        if tuple(x.shape) != (Bn, N) or tuple(yy.shape) != (Bn, N):
+            raise ValueError("xout / y: the shape of R")
+        if part.dim() != 3 or part.dtype != torch.float32 or not part.is_contiguous() or part.shape[1] != lib.trace_op_sk_rows() or part.shape[2] != N:
+            raise ValueError("part: contiguous fp32 [chunks, sk_rows, N]")
+        ks = part.shape[0] if KS is None else int(KS)
+        if ks > part.shape[0]:
+            raise ValueError("KS: more chunks than the tensor holds")
+        y8 = torch.empty((Bn, N), dtype=torch.uint8, device=R.device) if fp8 else None
+        sy = torch.empty((Bn,), dtype=torch.float32, device=R.device) if fp8 else None
+        _lib.check(lib.trace_op_add_rmsnorm_ex(_ptr(part), ks, _ptr(R), R.stride(0), _ptr(x), x.stride(0), _ptr(w), _ptr(yy), yy.stride(0), _ptr(y8), _ptr(sy),
+                                               Bn, N, float(eps), _stream()))
+        return (x, yy, y8, sy) if fp8 else (x, yy)
+
+    @staticmethod
+    def skinny_fused_swiglu(part_gu, W, Bn, KS=None):
+        """trace_op_skinny_fused_swiglu: part_gu fp32 [>= KS, sk_rows, 2 K] (16-row interleaved gate|up partial rows), W [N, K] row-major -> the fp32
+        partial rows [ks, sk_rows, N] of el(silu(sum gate) * sum up) . W^T  (Bn <= 4)"""
+        lib = _lib.load(ops.element)
+        N, K = W.shape
+        if part_gu.dim() != 3 or part_gu.dtype != torch.float32 or not part_gu.is_contiguous() or part_gu.shape[1] != lib.trace_op_sk_rows() \
+                or part_gu.shape[2] != 2 * K:
+            raise ValueError("part_gu: contiguous fp32 [chunks, sk_rows, 2 K]")
+        ks_gu = part_gu.shape[0] if KS is None else int(KS)
+        if ks_gu > part_gu.shape[0]:
+            raise ValueError("KS: more chunks than the tensor holds")
+        ks = lib.trace_op_skinny_ks(N, K, EPI_PARTIAL, Bn) if (1 <= Bn <= 64 and N >= 16 and N % 16 == 0 and K >= 64 and K % 64 == 0) else 1
+        out = torch.zeros((ks, lib.trace_op_sk_rows(), N), dtype=torch.float32, device=W.device)
+        _lib.check(lib.trace_op_skinny_fused_swiglu(_ptr(part_gu), ks_gu, _ptr(W.contiguous()), _ptr(out), Bn, N, K, _stream()))
+        return out
 
     @staticmethod
     def attn_decode(q, kcache, vcache, pos, nsplit, scale, vtcache=None):
