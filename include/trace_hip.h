@@ -582,6 +582,33 @@ int trace_op_kv8_pack(const void* k_rows, const void* v_rows, void* k8, void* v8
 int trace_op_kv8_unpack(const void* k8, const void* v8, const float* ks, const float* vs, const int32_t* slots, void* k_out, void* vt_out, int R, int B,
                         int nkv, int num_slots, int max_ctx, void* stream);
 
+/* ---- the prefill's cache-write kernels, each alone (tests/test_gpu_prefill_glue_probes.py) ----
+ * Pass-throughs of the launchers the prefill calls, with every stride and offset they take.  Each also takes the ELEMENT COUNT of every array the launch
+ * will touch and answers TRACE_ERR_ARG, before any launch, when a read or a store would leave one of them, when a pointer is not 16-byte aligned or a
+ * stride is no multiple of 8 elements.
+ *
+ * trace_op_rope_kv: qkv rows [q heads | k heads | v heads] of hd elements, row stride ld >= (nq + 2 nkv) hd.  Row r has
+ *   sq = seq_len > 0 ? r / seq_len : 0,  pos = pos_arr ? pos_arr[r] : pos0 + r - sq seq_len,  slot = slot_arr ? slot_arr[r] : slot0 + sq
+ * (slot_arr / pos_arr: device int32 [arr_len >= R], either may be NULL).  q heads are rotated in place (rotate-half: the partner of d is d + hd/2;
+ * o1 = x1 c - x2 s, o2 = x2 c + x1 s with c, s = cos_t / sin_t [table_rows][hd/2] fp32 at row pos, rounded once); k head h is rotated and stored at
+ * kcache[slot slot_stride + h kv_head_stride + pos hd]; with vcache != NULL v head h is copied to the same offset of vcache; nothing else is written.
+ * Refused: hd % 16, ld % 8 or below the row width, R / nq / nkv < 1, qkv_elems below (R - 1) ld + width, a position outside 0 .. table_rows - 1, a negative
+ * slot, a cache row that ends past kcache_elems (vcache_elems), a position past kv_head_stride with nkv > 1, two rows that go to one cache row. */
+int trace_op_rope_kv(void* qkv, int64_t qkv_elems, int ld, void* kcache, int64_t kcache_elems, void* vcache, int64_t vcache_elems, int64_t slot_stride,
+                     int64_t kv_head_stride, const int32_t* slot_arr, const int32_t* pos_arr, int64_t arr_len, int slot0, int pos0, int R, int nq, int nkv, int hd,
+                     const float* cos_t, const float* sin_t, int table_rows, int seq_len, void* stream);
+/* trace_op_transpose_v: dst[b dst_bs + h dst_hs + d dst_rs + p0 + r] = src[b src_bs + h src_hs + r src_rs + d] for r < n, d < hd; positions p0 + n .. the end
+ * of that 64-position block become zero, positions below p0 and from that block's end on keep what they hold.  perm = 1 (p0 = 0 only): within every 16
+ * positions the stored order is [0-3, 8-11, 4-7, 12-15].  Refused: hd outside {64, 128}, perm outside {0, 1}, perm with p0 != 0, dst_rs % 64,
+ * p0 + n > dst_rs, n < 1, p0 < 0, src_rs < hd, heads / batch outside 1..65535, a source or destination the counts cannot hold. */
+int trace_op_transpose_v(const void* src, int64_t src_elems, int64_t src_bs, int64_t src_hs, int src_rs, void* dst, int64_t dst_elems, int64_t dst_bs,
+                         int64_t dst_hs, int dst_rs, int n, int hd, int heads, int batch, int perm, int p0, void* stream);
+/* trace_op_gather_rows: out[r][0 .. H) = tabs[kind[r]][row[r]][0 .. H) for r < L.  tabs: HOST array of six device pointers (NULL = unused), tab_rows: HOST
+ * array of their row counts; kind / row: device int32.  Refused: H % 8, L < 1, kind_len or row_len below L, out_elems below L H, a kind outside 0..5, a row
+ * outside 0 .. tab_rows[kind] - 1 (so every kind used names a table). */
+int trace_op_gather_rows(const void* const* tabs, const int64_t* tab_rows, const int32_t* kind, int64_t kind_len, const int32_t* row, int64_t row_len, void* out,
+                         int64_t out_elems, int L, int H, void* stream);
+
 
 /* ---- The 4-bit weight format ("w4"), and its kernels over loose arrays ----------------------------------------------------------------------------
  * For the four decoder projections W [N][K] (nn.Linear layout, bf16), K % 32 == 0.  A block is 32 consecutive k of one output row.

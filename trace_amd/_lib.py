@@ -147,6 +147,9 @@ SIGNATURES = {
     "trace_op_qkv_finish_kv8": (I, [P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "trace_op_kv8_pack": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "trace_op_kv8_unpack": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "trace_op_rope_kv": (I, [P, C.c_int64, I, P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int64, P, P, C.c_int64, I, I, I, I, I, I, P, P, I, I, P]),
+    "trace_op_transpose_v": (I, [P, C.c_int64, C.c_int64, C.c_int64, I, P, C.c_int64, C.c_int64, C.c_int64, I, I, I, I, I, I, I, P]),
+    "trace_op_gather_rows": (I, [C.POINTER(P), C.POINTER(C.c_int64), P, C.c_int64, P, C.c_int64, P, C.c_int64, I, I, P]),
     "trace_op_quant_rows_w4": (I, [P, P, P, I, I, P]),
     "trace_op_tile_pack_w4": (I, [P, P, P, P, I, I, P]),
     "trace_op_dequant_w4": (I, [P, P, P, I, I, P]),

@@ -2599,3 +2599,93 @@ extern "C" int trace_op_kv8_unpack(const void* k8, const void* v8, const float* 
                            (long)nkv * max_ctx * 128, (long)max_ctx * 128, max_ctx, R, B, nkv, s));
     return TRACE_OK;
 }
+
+// ---- prefill cache-write hooks (llm.hip rope_kv / gather_rows, attn.hip transpose_v; tests/test_gpu_prefill_glue_probes.py) ----
+// Thin pass-throughs of the three launchers: every stride and offset is the caller's.  Each takes the ELEMENT COUNT of every array the launch touches and
+// answers TRACE_ERR_ARG, before any launch, when a read or a store would leave one of them.
+static bool op_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static int op_read_i32(const int32_t* dev, long n, std::vector<int32_t>& host, hipStream_t s) {
+    host.resize((size_t)n);
+    HIPCHK(hipMemcpyAsync(host.data(), dev, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return TRACE_OK;
+}
+extern "C" int trace_op_rope_kv(void* qkv, int64_t qkv_elems, int ld, void* kcache, int64_t kcache_elems, void* vcache, int64_t vcache_elems,
+                                int64_t slot_stride, int64_t kv_head_stride, const int32_t* slot_arr, const int32_t* pos_arr, int64_t arr_len, int slot0, int pos0,
+                                int R, int nq, int nkv, int hd, const float* cos_t, const float* sin_t, int table_rows, int seq_len, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!qkv || !kcache || !cos_t || !sin_t) return fail(TRACE_ERR_ARG, "null argument");
+    if (R < 1 || nq < 1 || nkv < 1 || hd < 16 || hd % 16 || seq_len < 0 || table_rows < 1) return fail(TRACE_ERR_ARG, "bad R / heads / hd / seq_len / table_rows");
+    const long width = (long)(nq + 2 * nkv) * hd;
+    if (ld % 8 || ld < width) return fail(TRACE_ERR_ARG, "ld: a multiple of 8, at least (nq + 2 nkv) hd");
+    if (qkv_elems < (long)(R - 1) * ld + width) return fail(TRACE_ERR_ARG, "qkv holds fewer than R rows");
+    if (slot_stride < 0 || kv_head_stride < 0 || slot_stride % 8 || kv_head_stride % 8) return fail(TRACE_ERR_ARG, "cache strides: non-negative multiples of 8 elements");
+    if (!op_aligned16(qkv) || !op_aligned16(kcache) || !op_aligned16(vcache) || !op_aligned16(cos_t) || !op_aligned16(sin_t))
+        return fail(TRACE_ERR_ARG, "pointers must be 16-byte aligned");
+    if ((slot_arr || pos_arr) && arr_len < R) return fail(TRACE_ERR_ARG, "slot_arr / pos_arr hold fewer than R entries");
+    std::vector<int32_t> hs, hp;
+    if (slot_arr) TRY(op_read_i32(slot_arr, R, hs, s));
+    if (pos_arr) TRY(op_read_i32(pos_arr, R, hp, s));
+    std::vector<int64_t> seen;
+    seen.reserve((size_t)R);
+    for (int r = 0; r < R; ++r) {                       // the kernel's own rule for a row's slot and position
+        const int sq = seq_len > 0 ? r / seq_len : 0;
+        const long pos = pos_arr ? (long)hp[r] : (long)pos0 + r - (long)sq * seq_len;
+        const long slot = slot_arr ? (long)hs[r] : (long)slot0 + sq;
+        if (pos < 0 || pos >= table_rows) return fail(TRACE_ERR_ARG, "position outside the RoPE tables");
+        if (slot < 0) return fail(TRACE_ERR_ARG, "slot out of range");
+        if ((pos + 1) * hd > kv_head_stride && nkv > 1) return fail(TRACE_ERR_ARG, "position past the kv head's rows");
+        const long end = slot * slot_stride + (long)(nkv - 1) * kv_head_stride + (pos + 1) * hd;
+        if (end > kcache_elems) return fail(TRACE_ERR_ARG, "slot / position past the K cache");
+        if (vcache && end > vcache_elems) return fail(TRACE_ERR_ARG, "slot / position past the V cache");
+        seen.push_back(slot * slot_stride + pos * hd);
+    }
+    if ((long)nkv * kv_head_stride > slot_stride && (slot_arr || (seq_len > 0 && R > seq_len))) return fail(TRACE_ERR_ARG, "kv heads overlap the next slot");
+    std::sort(seen.begin(), seen.end());
+    for (size_t i = 1; i < seen.size(); ++i)
+        if (seen[i] - seen[i - 1] < hd) return fail(TRACE_ERR_ARG, "two rows go to one cache row");
+    LCHK(launch_rope_kv((bf16_t*)qkv, ld, (bf16_t*)kcache, (bf16_t*)vcache, (long)slot_stride, (long)kv_head_stride, slot_arr, pos_arr, slot0, pos0, R, nq, nkv,
+                        hd, cos_t, sin_t, seq_len, s));
+    return TRACE_OK;
+}
+extern "C" int trace_op_transpose_v(const void* src, int64_t src_elems, int64_t src_bs, int64_t src_hs, int src_rs, void* dst, int64_t dst_elems, int64_t dst_bs,
+                                    int64_t dst_hs, int dst_rs, int n, int hd, int heads, int batch, int perm, int p0, void* stream) {
+    if (!src || !dst) return fail(TRACE_ERR_ARG, "null argument");
+    if (hd != 64 && hd != 128) return fail(TRACE_ERR_ARG, "hd must be 64 or 128");
+    if (perm != 0 && perm != 1) return fail(TRACE_ERR_ARG, "perm: 0 or 1");
+    if (perm && p0) return fail(TRACE_ERR_ARG, "perm = 1 takes p0 = 0 only");
+    if (n < 1 || p0 < 0 || heads < 1 || heads > 65535 || batch < 1 || batch > 65535) return fail(TRACE_ERR_ARG, "bad n / p0 / heads / batch");
+    if (dst_rs < 64 || dst_rs % 64 || (long)p0 + n > dst_rs) return fail(TRACE_ERR_ARG, "dst_rs: a multiple of 64, at least p0 + n");
+    if (src_rs < hd || src_rs % 8 || src_hs < 0 || src_hs % 8 || src_bs < 0 || src_bs % 8) return fail(TRACE_ERR_ARG, "source strides: multiples of 8, src_rs >= hd");
+    if (dst_hs < 0 || dst_hs % 8 || dst_bs < 0 || dst_bs % 8) return fail(TRACE_ERR_ARG, "destination strides: non-negative multiples of 8");
+    if (!op_aligned16(src) || !op_aligned16(dst)) return fail(TRACE_ERR_ARG, "pointers must be 16-byte aligned");
+    if (src_elems < (long)(batch - 1) * src_bs + (long)(heads - 1) * src_hs + (long)(n - 1) * src_rs + hd) return fail(TRACE_ERR_ARG, "the source holds fewer than n rows");
+    const long last = round_up(p0 + n, 64);             // stores end with the zero fill of the last 64-position block
+    if (dst_elems < (long)(batch - 1) * dst_bs + (long)(heads - 1) * dst_hs + (long)(hd - 1) * dst_rs + last) return fail(TRACE_ERR_ARG, "the destination is too small");
+    LCHK(launch_transpose_v((const bf16_t*)src, (long)src_bs, (long)src_hs, src_rs, (bf16_t*)dst, (long)dst_bs, (long)dst_hs, dst_rs, n, hd, heads, batch,
+                            (hipStream_t)stream, perm, p0));
+    return TRACE_OK;
+}
+extern "C" int trace_op_gather_rows(const void* const* tabs, const int64_t* tab_rows, const int32_t* kind, int64_t kind_len, const int32_t* row, int64_t row_len,
+                                    void* out, int64_t out_elems, int L, int H, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!tabs || !tab_rows || !kind || !row || !out) return fail(TRACE_ERR_ARG, "null argument");
+    if (L < 1 || H < 8 || H % 8) return fail(TRACE_ERR_ARG, "bad L / H (H a multiple of 8)");
+    if (kind_len < L || row_len < L) return fail(TRACE_ERR_ARG, "kind / row hold fewer than L entries");
+    if (out_elems < (long)L * H) return fail(TRACE_ERR_ARG, "out holds fewer than L rows");
+    if (!op_aligned16(out)) return fail(TRACE_ERR_ARG, "pointers must be 16-byte aligned");
+    GatherTabs t{};
+    for (int k = 0; k < 6; ++k) {
+        if (!op_aligned16(tabs[k]) || tab_rows[k] < 0 || (!tabs[k] && tab_rows[k])) return fail(TRACE_ERR_ARG, "bad table");
+        t.t[k] = (const bf16_t*)tabs[k];
+    }
+    std::vector<int32_t> hk, hr;
+    TRY(op_read_i32(kind, L, hk, s));
+    TRY(op_read_i32(row, L, hr, s));
+    for (int r = 0; r < L; ++r) {
+        if (hk[r] < 0 || hk[r] > 5) return fail(TRACE_ERR_ARG, "kind outside 0..5");
+        if (hr[r] < 0 || hr[r] >= tab_rows[hk[r]]) return fail(TRACE_ERR_ARG, "row outside its table");
+    }
+    LCHK(launch_gather_rows(t, kind, row, (bf16_t*)out, L, H, s));
+    return TRACE_OK;
+}

@@ -1338,6 +1338,68 @@ class ops:
         _lib.check(lib.trace_op_rmsnorm_ex(_ptr(x), x.stride(0), _ptr(y), y.stride(0), _ptr(w), x.shape[0], x.shape[1], float(eps), _stream()))
         return y
 
+    # ---- the prefill's cache-write kernels (trace_hip.h: "the prefill's cache-write kernels, each alone") ----
+    # Every array is a contiguous tensor whose numel() is the element count the library checks against and whose data_ptr() is the base the kernel gets:
+    # an offset into a larger buffer is a slice of its flat view (buf.view(-1)[off:]).  Strides and offsets go through as given.
+    @staticmethod
+    def _flat(t, name, dtype=None):
+        if t is None:
+            return None
+        if not t.is_contiguous() or (dtype is not None and t.dtype != dtype):
+            raise ValueError(f"{name}: a contiguous tensor" + (f" of {dtype}" if dtype is not None else ""))
+        return t
+
+    @staticmethod
+    def rope_kv(qkv, ld, kcache, slot_stride, kv_head_stride, R, nq, nkv, hd, cos_t, sin_t, slot0=0, pos0=0, seq_len=0, slot_arr=None, pos_arr=None,
+                vcache=None, table_rows=None):
+        """trace_op_rope_kv, in place on qkv / kcache / vcache.  cos_t, sin_t: fp32 [table_rows, hd / 2] (table_rows=None: the rows the tensors hold);
+        slot_arr / pos_arr: int32 device tensors."""
+        lib = _lib.load(ops.element)
+        el = ops.dtype()
+        for t, name in ((qkv, "qkv"), (kcache, "kcache"), (vcache, "vcache")):
+            ops._flat(t, name, el)
+        for t, name in ((cos_t, "cos_t"), (sin_t, "sin_t")):
+            ops._flat(t, name, torch.float32)
+        for t, name in ((slot_arr, "slot_arr"), (pos_arr, "pos_arr")):
+            ops._flat(t, name, torch.int32)
+        if cos_t.numel() != sin_t.numel() or (slot_arr is not None and pos_arr is not None and slot_arr.numel() != pos_arr.numel()):
+            raise ValueError("cos_t / sin_t, slot_arr / pos_arr: equal sizes")
+        rows = cos_t.numel() // max(hd // 2, 1) if table_rows is None else int(table_rows)
+        if rows * (hd // 2) > cos_t.numel():
+            raise ValueError("table_rows: more rows than the tables hold")
+        arr = slot_arr if slot_arr is not None else pos_arr
+        _lib.check(lib.trace_op_rope_kv(_ptr(qkv), qkv.numel(), int(ld), _ptr(kcache), kcache.numel(), _ptr(vcache), 0 if vcache is None else vcache.numel(),
+                                        int(slot_stride), int(kv_head_stride), _ptr(slot_arr), _ptr(pos_arr), 0 if arr is None else arr.numel(), int(slot0),
+                                        int(pos0), int(R), int(nq), int(nkv), int(hd), _ptr(cos_t), _ptr(sin_t), rows, int(seq_len), _stream()))
+
+    @staticmethod
+    def transpose_v(src, src_bs, src_hs, src_rs, dst, dst_bs, dst_hs, dst_rs, n, hd, heads, batch, perm=0, p0=0):
+        """trace_op_transpose_v, in place on dst"""
+        lib = _lib.load(ops.element)
+        ops._flat(src, "src", ops.dtype())
+        ops._flat(dst, "dst", ops.dtype())
+        _lib.check(lib.trace_op_transpose_v(_ptr(src), src.numel(), int(src_bs), int(src_hs), int(src_rs), _ptr(dst), dst.numel(), int(dst_bs), int(dst_hs),
+                                            int(dst_rs), int(n), int(hd), int(heads), int(batch), int(perm), int(p0), _stream()))
+
+    @staticmethod
+    def gather_rows(tabs, kind, row, out, L, H, tab_rows=None):
+        """trace_op_gather_rows, in place on out.  tabs: six tensors [rows, H] or None; tab_rows=None: the rows each tensor holds; kind / row: int32 device
+        tensors."""
+        lib = _lib.load(ops.element)
+        if len(tabs) != 6:
+            raise ValueError("tabs: six tables (None = unused)")
+        for t in tabs:
+            ops._flat(t, "table", ops.dtype())
+        ops._flat(out, "out", ops.dtype())
+        ops._flat(kind, "kind", torch.int32)
+        ops._flat(row, "row", torch.int32)
+        counts = [0 if t is None else t.numel() // max(int(H), 1) for t in tabs] if tab_rows is None else [int(x) for x in tab_rows]
+        if any(c * int(H) > (0 if t is None else t.numel()) for c, t in zip(counts, tabs)):
+            raise ValueError("tab_rows: more rows than a table holds")
+        ptrs = (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in tabs])
+        _lib.check(lib.trace_op_gather_rows(ptrs, (C.c_int64 * 6)(*counts), _ptr(kind), kind.numel(), _ptr(row), row.numel(), _ptr(out), out.numel(), int(L),
+                                            int(H), _stream()))
+
     @staticmethod
     def slot_pool(feats, ln_w, ln_b, slots, cos_t, sin_t, eps):
         """trace_op_slot_pool: feats [T, n, D] — a view with unit channel stride, any frame / row strides that are multiples of 8 elements — ln_w / ln_b
