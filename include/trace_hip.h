@@ -241,6 +241,23 @@ int trace_decode_read(trace_ctx* ctx, int32_t* out_ids, int32_t* out_len, int32_
  * TRACE_ERR_STATE: no batch begun; host-select mode.  TRACE_ERR_ARG: n_keep < 1 or > B; an index outside [0, B); a list that is not strictly
  * increasing.  After an error the batch is as it was. */
 int trace_decode_retire(trace_ctx* ctx, const int32_t* keep, int n_keep, void* stream);
+/* Admit rows into the running batch.  Append n prefilled sequences (KV slots `slots`, HOST) behind the B rows of the batch begun by
+ * trace_decode_begin: the batch becomes B + n rows, the new ones last (retire first, then admit: rows never land in holes).  For the new rows the call
+ * does what trace_decode_begin does for a batch (position = the slot's prefill length, heads[i], done = 0, length 0, zeroed ids and, when armed,
+ * log-probabilities, forced ids = forced [n][max_new] HOST or none) and then computes THEIR token 0 from the prefill hidden state, on those rows alone:
+ * the rows already running, and the step counter they share, do not move.  A row keeps a step count of its own from there: its recorded ids, length,
+ * forced ids, log-probabilities, max_new, min_new_tokens, begin_suppress_tokens, stop match and Philox counter are those of a row begun at its step 0.
+ * row_ids[i] (HOST, >= 0) is the row's Philox row index: a sampled row draws what row row_ids[i] of a batch begun together draws.  max_new, eos,
+ * sampling, processors, constraints and log-probabilities are the running batch's.  After an admission trace_decode_steps' bound is per row: a call is
+ * refused only when no row has n steps of its own left; a row past its max_new is stepped on without recording or advancing (it rewrites the last
+ * cache row its own slot allows).  The next trace_decode_steps runs the step of the new batch size.  Returns after the stream has run the copies.
+ * TRACE_ERR_STATE: no batch running; host-select mode; a shared prefix is live (trace_decode_set_shared_prefix); a slot not prefilled.
+ * TRACE_ERR_ARG: B + n above the cap of trace_decode_begin; a slot the batch holds, or twice in the list; prefill + max_new > max_ctx; a head outside
+ * 0..2; a negative row index; forced ids while processors or constraints are armed.  After one of these errors, all of them found by the argument
+ * and state checks before anything is queued, the batch is as it was.  A copy or launch that fails after them (a HIP error) leaves B and the B
+ * running rows' state and the shared counter untouched, but rows [B, B + n) of the per-row arrays and the spare counter pair are already written:
+ * harmless for the running rows, not "as it was". */
+int trace_decode_admit(trace_ctx* ctx, const int32_t* slots, int n, const int32_t* heads, const int32_t* row_ids, const int32_t* forced, void* stream);
 /* Host-driven token selection (do_sample=True in scripts/inference/inference.py:62, stopping criteria): with host
  * mode on (set before trace_decode_begin), begin/steps stop after the masked head logits; the host picks the ids and
  * trace_decode_feed applies them (output record, head switch, next-token embedding).  One eager step at a time. */
@@ -368,6 +385,8 @@ int trace_set_profile(trace_ctx* ctx, int on);
 /* Debugging aid: device addresses of the K cache, the V^T cache and the prefill's last-position hidden rows, with strides[8] = layer, slot, kv-head
  * strides (elements), ctx_pad, layers, kv heads, head_dim, hidden (tools/pipeline_stress.py checksums them between the pipeline's stages). */
 int trace_debug_buffers(trace_ctx* ctx, void** kcache, void** vcache, void** xlast, int64_t* strides);
+/* The batch sizes a captured decode step exists for (any tail mode), ascending, into sizes[0 .. cap) (HOST, may be NULL); returns their number. */
+int trace_debug_step_graphs(trace_ctx* ctx, int32_t* sizes, int cap);
 /* The same for a kv_cache_fp8 context: device addresses of K8, V8 (bytes), ks, vs (fp32), strides[8] = layer, slot, kv-head strides of the payload in
  * BYTES (those of the scales are these / 128), ctx_pad, layers, kv heads, head_dim, hidden.  TRACE_ERR_STATE on a 16-bit-cache context. */
 int trace_debug_kv8_buffers(trace_ctx* ctx, void** k8, void** v8, void** ks, void** vs, int64_t* strides);

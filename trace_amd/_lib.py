@@ -82,6 +82,7 @@ SIGNATURES = {
     "trace_decode_steps": (I, [P, I, I, P, P]),
     "trace_decode_read": (I, [P, P, P, P, P]),
     "trace_decode_retire": (I, [P, P, I, P]),
+    "trace_decode_admit": (I, [P, P, I, P, P, P, P]),
     "trace_decode_host_mode": (I, [P, I]),
     "trace_decode_feed": (I, [P, P, I, P]),
     "trace_decode_set_sampling": (I, [P, F, I, F, C.c_uint64]),
@@ -93,6 +94,7 @@ SIGNATURES = {
     "trace_stream_destroy": (I, [P, P]),
     "trace_set_gemm_cus": (I, [P, I]),
     "trace_set_profile": (I, [P, I]),
+    "trace_debug_step_graphs": (I, [P, P, I]),
     "trace_debug_buffers": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64)]),
     "trace_debug_kv8_buffers": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64)]),
     "trace_get_profile": (I, [P, P, I]),

@@ -120,6 +120,11 @@ struct trace_ctx {
     float* hl_val; int32_t* hl_idx;        // trace_llm_head_logits' own partial buffers
     int32_t *d_slots, *d_pos, *d_heads, *d_done, *d_out_ids, *d_out_len, *d_step, *d_forced, *d_params;
     int32_t* d_row_id = nullptr;       // [SK_ROWS] Philox row index of every row of the batch: identity at trace_decode_begin, gathered by trace_decode_retire
+    int32_t* d_step0 = nullptr;        // [SK_ROWS] the value of d_step[0] at which each row's own step 0 happened: zeros at trace_decode_begin, set by trace_decode_admit,
+                                       // gathered by trace_decode_retire.  Always passed (never null): a step graph captured before an admission reads the same array after it
+    int32_t h_step0[SK_ROWS] = {0};    // host copy of d_step0 (trace_decode_steps' per-row bound)
+    int32_t h_slots[SK_ROWS] = {0};    // host copy of d_slots (trace_decode_admit refuses a slot the batch holds)
+    int admitted = 0;                  // rows admitted since trace_decode_begin
     int32_t* d_retire = nullptr;       // trace_decode_retire's keep list [SK_ROWS] and scratch rows (allocated at the first retire)
     int32_t h_pos0[SK_ROWS] = {0};     // host copy: the prefill length of every row of the batch (pos_sum after a retire)
     int32_t* d_heads_tmp;                // head id per row for trace_llm_head_logits
@@ -501,7 +506,7 @@ static int ctx_create(const trace_config* cfg, int device_id, int kv8, int w4, t
     // trace_llm_head_logits: its own arg-max partials and three constant head-id rows (all 0 / all 1 / all 2), so that it shares nothing with a
     // decode batch in flight on another stream and needs no host copy or synchronisation per call
     A(c->hl_val, (size_t)SK_ROWS * c->ntiles); A(c->hl_idx, (size_t)SK_ROWS * c->ntiles);
-    A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_row_id, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4); A(c->d_sparams, 1); A(c->d_lgparams, 1);
+    A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_row_id, SK_ROWS); A(c->d_step0, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4); A(c->d_sparams, 1); A(c->d_lgparams, 1);
     A(c->d_out_ids, (size_t)SK_ROWS * cfg->max_new_tokens); A(c->d_forced, (size_t)SK_ROWS * cfg->max_new_tokens);
 #undef A
     if (rc == TRACE_OK && hipHostMalloc((void**)&c->h_ring, Lm * 8 * trace_ctx::NSTAGE_H) != hipSuccess) rc = fail(TRACE_ERR_HIP, "hipHostMalloc");
@@ -1406,39 +1411,50 @@ extern "C" int trace_llm_head_logits(trace_ctx* c, const void* hidden, int R, in
 }
 
 // ------------------------------------------------------------------------------------------------ decode
-static StepState step_state(trace_ctx* c) {
+// The rows a tail launch works on.  The batch: rows [0, B), the shared counter d_step[0..1], every row's origin d_step0.  The rows an admission
+// appends (trace_decode_admit): rows [r0, r0 + n) as a batch of their own, with the spare counter pair d_step[2..3] (which the admission zeroes
+// first) and no origin, so the selection they run is their step 0 while the shared counter and the rows in front of r0 are not touched.
+struct TailRows { int r0, n; };
+static StepState step_state(trace_ctx* c, TailRows t = {0, 0}) {
     StepState st{};
-    st.heads = c->d_heads; st.pos = c->d_pos; st.done = c->d_done; st.out_ids = c->d_out_ids; st.out_len = c->d_out_len;
-    st.step = c->d_step; st.forced = c->d_forced; st.params = c->d_params; st.row_id = c->d_row_id;
+    const size_t r0 = (size_t)t.r0;
+    st.heads = c->d_heads + r0; st.pos = c->d_pos + r0; st.done = c->d_done + r0; st.out_ids = c->d_out_ids + r0 * c->max_new; st.out_len = c->d_out_len + r0;
+    st.step = t.r0 ? c->d_step + 2 : c->d_step; st.forced = c->d_forced + r0 * c->max_new; st.params = c->d_params; st.row_id = c->d_row_id + r0;
+    st.step0 = t.r0 ? nullptr : c->d_step0;
     return st;
 }
 
-static int head_only(trace_ctx* c, const bf16_t* xn, float* logits_out, hipStream_t s) {
-    LCHK(launch_head_logits(xn, c->H, c->wheads, c->H, c->d_heads, c->V, c->Tv, c->Sv, c->part_val, c->part_idx, logits_out,
-                            c->B, s));
+static int head_only(trace_ctx* c, const bf16_t* xn, float* logits_out, hipStream_t s, TailRows t) {
+    LCHK(launch_head_logits(xn, c->H, c->wheads, c->H, c->d_heads + t.r0, c->V, c->Tv, c->Sv, c->part_val + (size_t)t.r0 * c->ntiles,
+                            c->part_idx + (size_t)t.r0 * c->ntiles, logits_out, t.n, s));
     return TRACE_OK;
 }
 // the selection in one of its forms; `rows`: the masked logits SELECT_SAMPLE / SELECT_ROW read (null for SELECT_TILES, which reads the tile partials)
-static int select_only(trace_ctx* c, int form, const float* rows, int advance, hipStream_t s) {
-    LCHK(launch_select(form, c->part_val, c->part_idx, rows, form == SELECT_SAMPLE ? c->d_sparams : nullptr, step_state(c), c->embed, c->time_tab,
-                       c->score_tab, c->sync_row, c->dX, c->H, c->B, c->H, c->V, c->Tv, c->Sv, advance, s, c->armed.stop ? c->d_ctab : nullptr));
+static int select_only(trace_ctx* c, int form, const float* rows, int advance, hipStream_t s, TailRows t = {0, 0}) {
+    if (!t.n) t.n = c->B;
+    LCHK(launch_select(form, c->part_val + (size_t)t.r0 * c->ntiles, c->part_idx + (size_t)t.r0 * c->ntiles, rows, form == SELECT_SAMPLE ? c->d_sparams : nullptr,
+                       step_state(c, t), c->embed, c->time_tab, c->score_tab, c->sync_row, c->dX + (size_t)t.r0 * c->H, c->H, t.n, c->H, c->V, c->Tv, c->Sv,
+                       advance, s, c->armed.stop ? c->d_ctab : nullptr));
     return TRACE_OK;
 }
-static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* logits_out, hipStream_t s) {
+// xn / logits_out: the first of the t.n rows
+static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* logits_out, hipStream_t s, TailRows t = {0, 0}) {
     const TailMode m = c->armed;
+    if (!t.n) t.n = c->B;
+    const size_t lg0 = (size_t)t.r0 * c->NV;
     // 1. the head: tile partials, and the raw masked rows into the caller's logits_out, else d_slog when anything armed will read them, else nowhere
-    float* raw = !logits_out && m.index() ? c->d_slog : logits_out;
-    TRY(head_only(c, xn, raw, s));
+    float* raw = !logits_out && m.index() ? c->d_slog + lg0 : logits_out;
+    TRY(head_only(c, xn, raw, s, t));
     // 2. host-select mode ends here: the host picks the token and calls trace_decode_feed
     if (c->host_mode) return TRACE_OK;
     // 3. logits processors and the ban rules of the constraints: the raw rows -> d_plog (raw stays as it is for step 5)
-    if (m.process) LCHK(launch_step_logits_process(raw, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_lgparams, c->d_plog, s, c->d_ctab));
+    if (m.process) LCHK(launch_step_logits_process(raw, step_state(c, t), t.n, c->V, c->Tv, c->Sv, c->d_lgparams, c->d_plog + lg0, s, c->d_ctab));
     // 4. the selection: a draw from the rows, the arg-max over a processed row, or the arg-max over the tile partials (they describe the raw row);
     //    with stop sequences armed, the instantiation that matches them against the recorded ids
     const int form = m.sample ? SELECT_SAMPLE : m.process ? SELECT_ROW : SELECT_TILES;
-    TRY(select_only(c, form, form == SELECT_TILES ? nullptr : m.process ? c->d_plog : raw, advance, s));
+    TRY(select_only(c, form, form == SELECT_TILES ? nullptr : m.process ? c->d_plog + lg0 : raw, advance, s, t));
     // 5. the log-probability of the token just recorded (it reads out_ids / out_len / the advanced step counter), on the raw rows
-    if (m.logprobs) LCHK(launch_step_logprob(raw, step_state(c), c->B, c->V, c->Tv, c->Sv, c->d_logprobs, s));
+    if (m.logprobs) LCHK(launch_step_logprob(raw, step_state(c, t), t.n, c->V, c->Tv, c->Sv, c->d_logprobs + (size_t)t.r0 * c->max_new, s));
     return TRACE_OK;
 }
 
@@ -1678,6 +1694,9 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     HIPCHK(hipMemcpyAsync(c->d_done, zero, B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_out_len, zero, B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_step, zero, 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_step0, zero, B * 4, hipMemcpyHostToDevice, s));
+    for (int b = 0; b < B; ++b) { c->h_step0[b] = 0; c->h_slots[b] = slots[b]; }
+    c->admitted = 0;
     HIPCHK(hipMemsetAsync(c->d_out_ids, 0, (size_t)B * max_new * 4, s));
     const int32_t prm[3] = {max_new, eos, c->host_mode};
     HIPCHK(hipMemcpyAsync(c->d_params, prm, 12, hipMemcpyHostToDevice, s));
@@ -1704,9 +1723,24 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
     if (logits_out && (n != 1 || use_graph)) return fail(TRACE_ERR_ARG, "logits_out needs n == 1 and eager mode");
     if (c->host_mode && (n != 1 || use_graph)) return fail(TRACE_ERR_ARG, "host-select mode runs one eager step at a time");
     // every step appends one KV row at pos[b]++; decode_begin checked pos + max_new <= max_ctx once, so the total is bounded here
-    if (c->steps_done + n > c->max_new - 1)
-        return fail(TRACE_ERR_STATE, "decode steps exceed max_new - 1 since trace_decode_begin (" + std::to_string(c->steps_done) + " taken, " +
-                                     std::to_string(n) + " requested, max_new " + std::to_string(c->max_new) + ")");
+    if (!c->admitted) {
+        if (c->steps_done + n > c->max_new - 1)
+            return fail(TRACE_ERR_STATE, "decode steps exceed max_new - 1 since trace_decode_begin (" + std::to_string(c->steps_done) + " taken, " +
+                                         std::to_string(n) + " requested, max_new " + std::to_string(c->max_new) + ")");
+    } else {
+        // After an admission the bound is per row: row b has taken steps_done - h_step0[b] steps of its own, and the call is refused only when no row
+        // has room for all n.  A row whose own max_new is reached inside the call goes on being stepped with the batch; select_next_kernel's guard on
+        // `local` stops its recording and its pos[b] += 1.  From the step's code (decode_step_*: append the fed token's K / V at row pos[b] of the slot,
+        // attend rows [0, pos[b]], then select, which advances pos[b]): the row began at pos0 without an advance (its step 0), its local steps
+        // 1 .. max_new - 1 appended at pos0 .. pos0 + max_new - 2 and left pos[b] = pos0 + max_new - 1; every later step (local >= max_new) appends at
+        // that same row pos0 + max_new - 1 and attends pos0 + max_new rows.  The admission (like trace_decode_begin) checked pos0 + max_new <= max_ctx,
+        // so pos0 + max_new - 1 <= max_ctx - 1: inside the row's own slot and inside the RoPE tables, whatever the number of such steps.
+        int most = 0;                                 // the most steps any row of the batch may still take
+        for (int b = 0; b < c->B; ++b) most = std::max(most, c->max_new - 1 - (c->steps_done - c->h_step0[b]));
+        if (n > most)
+            return fail(TRACE_ERR_STATE, "decode steps exceed max_new - 1 for every row of the batch (" + std::to_string(n) + " requested, at most " +
+                                         std::to_string(most) + " left to any row, max_new " + std::to_string(c->max_new) + ")");
+    }
     const int steps_before = c->steps_done;
     c->steps_done += n;
     hipStream_t s = (hipStream_t)stream;
@@ -1781,17 +1815,82 @@ extern "C" int trace_decode_retire(trace_ctx* c, const int32_t* keep, int n_keep
     const size_t row_ints = retire_row_ints(c->c.max_new_tokens, c->H);
     if (!c->d_retire) TRY(dalloc(c, &c->d_retire, SK_ROWS + SK_ROWS * row_ints));
     RetireArgs a{};
-    a.small[0] = c->d_slots; a.small[1] = c->d_pos; a.small[2] = c->d_heads; a.small[3] = c->d_done; a.small[4] = c->d_out_len; a.small[5] = c->d_row_id;
+    a.small[0] = c->d_slots; a.small[1] = c->d_pos; a.small[2] = c->d_heads; a.small[3] = c->d_done; a.small[4] = c->d_out_len; a.small[5] = c->d_row_id; a.small[6] = c->d_step0;
     a.wide[0] = c->d_out_ids; a.wide[1] = c->d_forced; a.wide[2] = c->armed.logprobs ? reinterpret_cast<int32_t*>(c->d_logprobs) : nullptr;
     a.x = c->dX; a.H = c->H; a.max_new = c->max_new;
     HIPCHK(hipMemcpyAsync(c->d_retire, keep, (size_t)n_keep * 4, hipMemcpyHostToDevice, s));
     LCHK(launch_retire(a, c->d_retire, n_keep, B, c->d_retire + SK_ROWS, s));
     HIPCHK(hipStreamSynchronize(s));                 // the caller's keep list must outlive the async copy
     c->pos_sum = 0;
-    for (int i = 0; i < n_keep; ++i) { c->h_pos0[i] = c->h_pos0[keep[i]]; c->pos_sum += c->h_pos0[i]; }      // (keep[i] >= i: read before overwritten)
+    for (int i = 0; i < n_keep; ++i) { c->h_pos0[i] = c->h_pos0[keep[i]]; c->h_step0[i] = c->h_step0[keep[i]]; c->h_slots[i] = c->h_slots[keep[i]]; c->pos_sum += c->h_pos0[i]; }      // (keep[i] >= i: read before overwritten)
     c->B = n_keep;
     if (n_keep == 1) { c->sh_slot = -1; c->sh_rows = 0; }      // one sequence shares with nobody (as at trace_decode_begin): its own slot holds the same rows
     return TRACE_OK;
+}
+
+// Append n prefilled sequences behind the B rows of the running batch (retire first, then admit: rows never land in holes).  What trace_decode_begin
+// does for a batch is done for rows [B, B + n) alone; then the head and the selection of their own step 0 run on those rows only, no position advance.
+// The counter, and why no launch can see it half-advanced: the selection's check-in (select.h) lets the last of a launch's workgroups advance the
+// counter it was given.  The admission's launches get the spare pair d_step[2..3] (TailRows), zeroed by a stream-ordered copy before them, and a null
+// origin: their `local` is 0, they check in n times to the spare pair, and nothing of theirs reads or writes d_step[0..1] or a row in front of B.  The
+// shared counter therefore still holds what the last step of the batch left, steps_done + 1 (trace_decode_begin's selection took it from 0 to 1, every
+// step adds 1), and the origin of the new rows is written by the host from that number, steps_done: the next common step reads counter steps_done + 1,
+// their local step 1.  Everything is queued on the caller's stream, in order, between two steps; the next step's graph or launches see B + n rows
+// whose check-in count is B + n, so its last workgroup, and no earlier one, advances the shared counter.
+extern "C" int trace_decode_admit(trace_ctx* c, const int32_t* slots, int n, const int32_t* heads, const int32_t* row_ids, const int32_t* forced,
+                                  void* stream) {
+    if (!c || c->B < 1) return fail(TRACE_ERR_STATE, "trace_decode_admit: no decode batch is running (trace_decode_begin not called)");
+    if (c->host_mode) return fail(TRACE_ERR_STATE, "trace_decode_admit is not available in host-select mode");
+    if (c->sh_rows > 0) return fail(TRACE_ERR_STATE, "trace_decode_admit: the running batch attends a shared prefix; admitted rows would have to hold the same rows");
+    if (!slots || !heads || !row_ids || n < 1) return fail(TRACE_ERR_ARG, "trace_decode_admit: bad slots / heads / row_ids / n");
+    const int B = c->B, cap = std::min(c->max_B, c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS), max_new = c->max_new;
+    if (n > cap - B) return fail(TRACE_ERR_ARG, "trace_decode_admit: " + std::to_string(B) + " running + " + std::to_string(n) + " admitted rows exceed the cap (at most " + std::to_string(cap) + " sequences decode together)");
+    int32_t pos[SK_ROWS], zero[SK_ROWS] = {0}, org[SK_ROWS];
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= c->max_B || c->slot_len[slots[i]] <= 0) return fail(TRACE_ERR_STATE, "trace_decode_admit: slot not prefilled");
+        for (int b = 0; b < B; ++b) if (c->h_slots[b] == slots[i]) return fail(TRACE_ERR_ARG, "trace_decode_admit: slot " + std::to_string(slots[i]) + " is already in the running batch");
+        for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(TRACE_ERR_ARG, "trace_decode_admit: duplicate slot");
+        if (heads[i] < 0 || heads[i] > 2) return fail(TRACE_ERR_ARG, "trace_decode_admit: head must be 0, 1 or 2");
+        if (row_ids[i] < 0) return fail(TRACE_ERR_ARG, "trace_decode_admit: row_ids must not be negative");
+        pos[i] = c->slot_len[slots[i]];
+        if (pos[i] + max_new > c->max_ctx) return fail(TRACE_ERR_ARG, "trace_decode_admit: prefill + max_new_tokens exceeds max_ctx");
+        org[i] = c->steps_done;
+    }
+    if (forced && (c->armed.process || c->armed.stop))
+        return fail(TRACE_ERR_ARG, "trace_decode_admit: forced ids with logits processors / constraints armed: the history is the recorded ids, not the fed ones");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t wide0 = (size_t)B * max_new, wide_n = (size_t)n * max_new;
+    HIPCHK(hipMemcpyAsync(c->d_slots + B, slots, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_row_id + B, row_ids, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_pos + B, pos, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_heads + B, heads, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_done + B, zero, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_out_len + B, zero, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_step0 + B, org, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_step + 2, zero, 8, hipMemcpyHostToDevice, s));          // the spare counter pair of the admission's own selection
+    HIPCHK(hipMemsetAsync(c->d_out_ids + wide0, 0, wide_n * 4, s));
+    if (c->armed.logprobs) HIPCHK(hipMemsetAsync(c->d_logprobs + wide0, 0, wide_n * 4, s));
+    if (forced) HIPCHK(hipMemcpyAsync(c->d_forced + wide0, forced, wide_n * 4, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemsetAsync(c->d_forced + wide0, 0xff, wide_n * 4, s));
+    for (int i = 0; i < n; ++i)
+        HIPCHK(hipMemcpyAsync(c->dH + (size_t)(B + i) * c->H, c->xlast + (size_t)slots[i] * c->H, (size_t)c->H * 2, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));     // host arrays above must outlive the async copies
+    TRY(head_and_select(c, c->dH + (size_t)B * c->H, 0, nullptr, s, TailRows{B, n}));
+    for (int i = 0; i < n; ++i) { c->h_pos0[B + i] = pos[i]; c->h_step0[B + i] = org[i]; c->h_slots[B + i] = slots[i]; c->pos_sum += pos[i]; }
+    c->B = B + n; c->admitted += n;
+    if (forced) c->has_forced = 1;
+    return TRACE_OK;
+}
+
+extern "C" int trace_debug_step_graphs(trace_ctx* c, int32_t* sizes, int cap) {
+    if (!c) return 0;
+    int n = 0;
+    for (int B = 1; B <= SK_ROWS; ++B) {
+        bool any = false;
+        for (int m = 0; m < 16 && !any; ++m) any = c->graphs[m][B][0].exec || c->graphs[m][B][1].exec;
+        if (any) { if (sizes && n < cap) sizes[n] = B; ++n; }
+    }
+    return n;
 }
 
 extern "C" int trace_decode_read(trace_ctx* c, int32_t* out_ids, int32_t* out_len, int32_t* heads, void* stream) {

@@ -224,11 +224,12 @@ struct StepState {
     const int32_t* forced;// [B, max_new] teacher-forcing ids; negative entry = feed the arg-max
     const int32_t* params;// device [3]: max_new, eos, record_feed (device-resident so a captured graph stays valid)
     const int32_t* row_id;// [B] the Philox row index of each row (the index it had at trace_decode_begin: trace_decode_retire moves it with the row); null = b
+    const int32_t* step0; // [B] the value of *step at which the row's own step 0 happened (0 for a row of trace_decode_begin; trace_decode_admit); null = 0
 };
 // Retiring rows of a decode batch (retire.hip): every per-row array of the step, gathered to its first n_keep rows through a scratch copy.
-constexpr int RETIRE_SMALL = 6;
+constexpr int RETIRE_SMALL = 7;
 struct RetireArgs {
-    int32_t* small[RETIRE_SMALL];   // [B] each: slots, pos, heads, done, out_len, row_id
+    int32_t* small[RETIRE_SMALL];   // [B] each: slots, pos, heads, done, out_len, row_id, step0
     int32_t* wide[3];               // [B][max_new] each: out_ids, forced, the log-probabilities' bits (null where not armed)
     bf16_t* x;                      // [B][H] the next step's input embedding
     int H, max_new;

@@ -2,7 +2,7 @@
 // An in-place gather would race — row i is at once the destination of keep[i] and the source of some j < i, in another workgroup — so the rows go
 // through a scratch copy: phase 0 reads array row keep[i] into scratch row i, phase 1 (the next launch on the stream) writes scratch row i to array
 // row i.  The arrays keep their addresses, which the captured step graphs hold.  One workgroup per (kept row, segment):
-//   segment 0: the six one-int-per-row arrays (slots, pos, heads, done, out_len, row_id);
+//   segment 0: the seven one-int-per-row arrays (slots, pos, heads, done, out_len, row_id, step0);
 //   segments 1-3: the rows at stride max_new (out_ids, forced, log-probabilities where armed), 16 bytes per lane when max_new % 4 == 0 (every row
 //     then starts on a 16-byte boundary), 4 bytes per lane otherwise;
 //   segment 4: the row of the next step's input embedding (H 16-bit elements, H % 8 == 0), 16 bytes per lane.

@@ -21,14 +21,15 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float
 
 // The log-probability of one token per row (sample.h token_logprob_row), one workgroup per row, in two forms that share every line of arithmetic:
 //   loose rows (heads != null): row b's token is ids[b], its head heads[b]; out[b].  An id outside the head's range gives -inf.
-//   decode step (heads == null): launched after select_next_kernel, which has recorded this step's token and advanced the counter: the step is
-//     *step - 1, the token out_ids[b][step]; the head it was drawn from is the one whose id range holds it (the three ranges are disjoint).
+//   decode step (heads == null): launched after select_next_kernel, which has recorded this step's token and advanced the counter: the row's step is
+//     *step - 1 - step0[b], the token out_ids[b][step]; the head it was drawn from is the one whose id range holds it (the three ranges are disjoint).
 //     Only rows select_next recorded a token for in this step (out_len[b] == step + 1) write out[b][step]; rows that finished earlier and
 //     steps at or past max_new leave `out` untouched.
 __global__ __launch_bounds__(SAMPLE_THREADS) void token_logprob_kernel(const float* __restrict__ logits, int ld, const int32_t* __restrict__ heads,
                                                                        int V, int Tv, int Sv, const int32_t* __restrict__ ids,
                                                                        float* __restrict__ out, const int32_t* __restrict__ step_ctr,
-                                                                       const int32_t* __restrict__ out_len, const int32_t* __restrict__ params) {
+                                                                       const int32_t* __restrict__ out_len, const int32_t* __restrict__ params,
+                                                                       const int32_t* __restrict__ step0) {
     __shared__ float fbuf[SAMPLE_THREADS];
     __shared__ float wmax[4];
     const int b = blockIdx.x;
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void token_logprob_kernel(const flo
         head = heads[b];
         o = (size_t)b;
     } else {
-        const int step = step_ctr[0] - 1, max_new = params[0];
+        const int step = step_ctr[0] - 1 - (step0 ? step0[b] : 0), max_new = params[0];     // the row's own step (StepState::step0)
         if (step < 0 || step >= max_new || out_len[b] != step + 1) return;       // (uniform over the workgroup)
         id = ids[(size_t)b * max_new + step];
         head = id <= V ? 0 : (id < V + 1 + Tv ? 1 : 2);
@@ -62,13 +63,13 @@ int launch_sample_rows(const float* logits, int ld, int B, const int32_t* heads,
 
 int launch_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out, hipStream_t s) {
     if (B < 1 || B > 65535 || ld < V + 1 + Tv + Sv || V < 1 || Tv < 1 || Sv < 1 || !heads) return TRACE_ERR_ARG;
-    hipLaunchKernelGGL(token_logprob_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, logits, ld, heads, V, Tv, Sv, ids, out, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(token_logprob_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, logits, ld, heads, V, Tv, Sv, ids, out, nullptr, nullptr, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
 
 int launch_step_logprob(const float* logits, const StepState& st, int B, int V, int Tv, int Sv, float* out_logprobs, hipStream_t s) {
     if (B < 1 || B > SK_ROWS || !logits || !out_logprobs) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(token_logprob_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, logits, V + 1 + Tv + Sv, nullptr, V, Tv, Sv, st.out_ids, out_logprobs,
-                       st.step, st.out_len, st.params);
+                       st.step, st.out_len, st.params, st.step0);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

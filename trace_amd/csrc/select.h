@@ -9,7 +9,9 @@
 namespace {
 
 // one workgroup per sequence.  `step` is shared: every workgroup reads it first, then checks in; the last one to
-// check in advances it (so no workgroup can observe the next step's value).
+// check in advances it (so no workgroup can observe the next step's value).  `local` = step - st.step0[b] is the row's own step (a row admitted into a
+// running batch, trace_decode_admit, began later than the counter): the index into out_ids / forced, out_len, the max_new guards, the Philox counter
+// and the stop match's length are the row's; only the check-in works on the shared value.
 // SELECT_TILES: the arg-max over head_logits_kernel's tile partials (greedy).  SELECT_SAMPLE: the token is drawn by sample_row (sample.h)
 // from the masked logits in `logits` [B, V+1+Tv+Sv] (head_logits_kernel's rows, or logits_process_kernel's) under the device-resident params
 // *sp, with the step counter and the row index as the Philox counter.  SELECT_ROW: the arg-max over the row's head range [lo, hi) of `logits`
@@ -33,6 +35,7 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int b = blockIdx.x;
     const int step = __hip_atomic_load(st.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int local = step - (st.step0 ? st.step0[b] : 0);     // the row's own step: everything below that belongs to the row uses it, the check-in alone the shared value
     const int max_new = st.params[0], eos = st.params[1], record_feed = st.params[2];
     __syncthreads();
     if (tid == 0) {
@@ -48,7 +51,7 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
         __shared__ SampleLds L;
         int lo, hi;
         head_bounds(st.heads[b], V, Tv, Sv, lo, hi);
-        idx = lo + sample_row(logits + (size_t)b * (V + 1 + Tv + Sv) + lo, hi - lo, *sp, (uint32_t)step,
+        idx = lo + sample_row(logits + (size_t)b * (V + 1 + Tv + Sv) + lo, hi - lo, *sp, (uint32_t)local,
                                (uint32_t)(st.row_id ? st.row_id[b] : b), L);      // (a row keeps the index it had at trace_decode_begin: trace_decode_retire)
     } else {
     if constexpr (MODE == SELECT_ROW) {
@@ -86,18 +89,18 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
         for (int w = 1; w < 4; ++w)
             if (sv[w] > v || (sv[w] == v && si[w] < idx)) { v = sv[w]; idx = si[w]; }
         int tok = idx;
-        if (advance && step < max_new) st.pos[b] += 1;     // (the host bounds the step count too: engine.hip trace_decode_steps)
+        if (advance && local < max_new) st.pos[b] += 1;     // (the host bounds the step count too: engine.hip trace_decode_steps)
         int feed = tok;
-        if (step < max_new) {
-            const int f = st.forced[(size_t)b * max_new + step];
+        if (local < max_new) {
+            const int f = st.forced[(size_t)b * max_new + local];
             if (f >= 0) feed = f;
         }
         if (record_feed) tok = feed;          // host-driven sampling: the emitted token is the one fed back
         const bool was_done = st.done[b] != 0;
-        if constexpr (STOP) s_len = !was_done && step < max_new ? step + 1 : 0;
-        if (!was_done && step < max_new) {
-            st.out_ids[(size_t)b * max_new + step] = tok;
-            st.out_len[b] = step + 1;
+        if constexpr (STOP) s_len = !was_done && local < max_new ? local + 1 : 0;
+        if (!was_done && local < max_new) {
+            st.out_ids[(size_t)b * max_new + local] = tok;
+            st.out_len[b] = local + 1;
             if (eos >= 0 && tok == eos) st.done[b] = 1;
         }
         // head switch (trace_mistral.py:86-88): V -> time(1), V+1 -> score(2), V+Tv+1 -> text(0)

@@ -13,6 +13,7 @@ from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
 from .prefix import APPEND_GROUP_MAX, SHARE_PREFIX_MIN_BATCH, group_by_length, shared_prefix_len, split_questions
+from .admit import ADMIT_FRACTION, QueueBook, admit_plan
 from .retire import RETIRE_FRACTION, RetireBook, retire_plan
 from .sampling import Constraints, LogitsParams, SamplingParams, argmax_rows, check_constraints, ends_stopped, sample_rows_host
 from . import scoring
@@ -45,6 +46,8 @@ class TraceEngine:
     # ... and a retire happens there once at least 1 / retire_fraction of the running rows have finished (retire.retire_plan, where the reason for the
     # value stands).  An instance may set its own.
     retire_fraction = RETIRE_FRACTION
+    # ... and generate_queue admits waiting requests there once the room is at least 1 / admit_fraction of the cap (admit.admit_plan)
+    admit_fraction = ADMIT_FRACTION
 
     def __init__(self, cfg: TraceConfig, device: int = 0, max_batch: int = 1, max_ctx: Optional[int] = None,
                  max_frames: Optional[int] = None, max_new_tokens: int = 1024, vit_batch_frames: Optional[int] = None,
@@ -133,6 +136,7 @@ class TraceEngine:
         self._rows: List[int] = []            # original index (at decode_begin) of every row of the running decode batch
         self._rows_history: List[List[int]] = []      # _rows after decode_begin and after every retire of the running batch
         self.retires = 0                      # retire_rows calls that shrank a batch, so far
+        self.admits = 0                       # admit_rows calls that grew a batch, so far
         self._prefix = None            # (key, rows): KV slot 0 holds `rows` prefilled prompt rows described by `key` (set_prefix_entry); see _drop_prefix
         self._dbg = None               # debugging hook: callable(tag, index, tensor-or-None) called between the stages (tools/pipeline_stress.py)
 
@@ -575,6 +579,33 @@ class TraceEngine:
             self.retires += 1
             self._rows_history.append(list(self._rows))
 
+    def admit_rows(self, slots: Sequence[int], heads: Sequence[int], row_ids: Optional[Sequence[int]] = None,
+                   forced: Optional[Sequence[Sequence[int]]] = None):
+        """Append prefilled KV slots behind the rows of the running decode batch (trace_decode_admit): the new rows get what decode_begin gives a
+        batch, their token 0 is selected on them alone, and from there each counts steps of its own: ids, length, forced ids, log-probabilities,
+        min_new_tokens, begin_suppress_tokens, the stop match and the sampler's counter are those of a row begun at its step 0.  row_ids: the Philox
+        row index of each new row (default: the position it lands at), so a sampled row can draw what that row of a batch begun together draws.
+        self._rows names the new rows by the next unused original indices.  Retire first, then admit.  Not in host-select mode, not under a shared
+        prefix, not with forced ids while processors or constraints are armed."""
+        slots, heads = [int(s) for s in slots], [int(h) for h in heads]
+        n, mn = len(slots), self._max_new
+        if len(heads) != n or (row_ids is not None and len(row_ids) != n) or (forced is not None and len(forced) != n):
+            raise ValueError("one head, row index and forced row per admitted slot")
+        rid = [int(r) for r in row_ids] if row_ids is not None else list(range(self._B, self._B + n))
+        f = None
+        if forced is not None:
+            flat = []
+            for row in forced:
+                row = list(row)[:mn]
+                flat += row + [0] * (mn - len(row))
+            f = _i32(flat)
+        _lib.check(self.lib.trace_decode_admit(self.h, _i32(slots), n, _i32(heads), _i32(rid), f, _stream()))
+        nxt = 1 + max([max(h) for h in self._rows_history if h] + [-1])
+        self._rows = self._rows + list(range(nxt, nxt + n))
+        self._B += n
+        self.admits += 1
+        self._rows_history.append(list(self._rows))
+
     def decode_read(self):
         B, mn = self._B, self._max_new
         ids = (C.c_int32 * (B * mn))()
@@ -714,14 +745,15 @@ class TraceEngine:
         return groups
 
     def encode_prefill(self, videos: Sequence[torch.Tensor], timestamps: Sequence, input_ids: Sequence[Sequence[int]], slot0: int = 0,
-                       record_stages: bool = False):
+                       record_stages: bool = False, share_prefix: bool = True):
         """Stage 1 of generate() for a batch: CLIP tower (over the batch's frame stream) -> slot pool + time rows -> splice -> prefill
         into KV slots slot0 .. slot0 + B - 1.  Runs on the current stream; touches no decode state, so it may run on another stream
         while an earlier batch (other slots) is being decoded (generate_stream).
         A batch of share_prefix_min_batch videos or more whose prompts agree before <video> (one question for every video: the evaluation loops)
         prefills those P rows once, into the batch's first slot, and every run continues from a copy of them (trace_llm_prefill_shared): the same
         bits in every slot as whole prefills leave (16-bit KV cache and 16-bit weights only: a continuation is not bit-identical under the others).
-        Returns (first slot, P) then — what decode(shared_prefix=) takes — and None otherwise."""
+        Returns (first slot, P) then — what decode(shared_prefix=) takes — and None otherwise.  share_prefix=False: whole prefills whatever the
+        prompts (generate_queue: rows admitted later could not hold the same shared rows)."""
         B = len(videos)
         if slot0 < 0 or slot0 + B > self.max_batch:
             raise ValueError(f"slots {slot0}..{slot0 + B - 1} exceed the engine's {self.max_batch} KV slots")
@@ -733,7 +765,7 @@ class TraceEngine:
         held: List[torch.Tensor] = []                 # spliced embeds of slots held_slot0 .. (equal lengths)
         held_slot0 = 0
         P = 0                                         # prompt rows shared by the batch
-        if 2 <= B and B >= self.share_prefix_min_batch and not self.kv_cache and not self.llm_fp8:
+        if share_prefix and 2 <= B and B >= self.share_prefix_min_batch and not self.kv_cache and not self.llm_fp8:
             P = shared_prefix_len(input_ids)
         if P:
             def prefix():
@@ -935,6 +967,150 @@ class TraceEngine:
         shared = self.encode_prefill(videos, timestamps, input_ids, 0, record_stages=True)
         return self.decode(range(B), heads, max_new_tokens, eos, use_graph, forced, sampling, logprobs=logprobs, logits=logits, shared_prefix=shared,
                            constraints=constraints, retire_finished=retire_finished)
+
+    def generate_queue(self, requests: Iterable, max_new_tokens: int, eos: int = -1, *, max_rows: Optional[int] = None,
+                       sampling: Optional[SamplingParams] = None, logprobs: bool = False, logits: Optional[LogitsParams] = None,
+                       constraints: Optional[Constraints] = None, use_graph: bool = True):
+        """Continuous batching: requests (video, timestamps, input_ids, head[, forced ids]) flow through one running decode batch of at most
+        max_rows rows (default and bound: decode_batch_max) -> one (ids, head[, logprobs]) per request, in request order.  The first max_rows
+        requests are encoded, prefilled (whole prefills: no shared prefix) and begun as a batch; every retire_chunk steps the recorded ids are read,
+        the rows that ended (EOS, a stop sequence, or max_new_tokens ids) leave (retire_rows, by retire.retire_plan), and once admit.admit_plan says
+        the room is worth it the next requests are encoded and prefilled into the KV slots the retired rows freed and appended to the batch
+        (admit_rows); the boundary then looks again, so a row whose token 0 already ends it leaves before it has ridden a chunk.  When every row of
+        the batch has ended at once, the next requests begin a batch of their own.  KV slot and batch position are independent: the book holds the
+        map and the free slots.  Everything runs on the current stream; the admitted rows' encode and prefill do not
+        overlap the decode (generate_stream's banks do that for whole batches).
+        A row's ids, length and log-probabilities are a function of its own logits, its own step count and (sampled) its Philox row index, which is its
+        request index counted from the first request of the batch it joined: on a decoder whose logits do not depend on rounding they are those of
+        generate() of the request alone, exactly; on real weights a row sees the rounding of the batch sizes it is decoded in.
+        max_new_tokens, eos, sampling, logits and constraints hold for every request.  ValueError, before any work, for sampling parameters outside
+        the device sampler's domain.  ValueError for a request that carries forced ids while logits= / constraints= are armed: before any work when
+        `requests` is a list or a tuple (every request is looked at first); an iterator is looked at as it is pulled, so there the error comes when
+        the bad request is reached — the requests before it have been decoded by then, their results are lost with the call, and the batch that
+        was running is dropped (the next decode_begin starts afresh; the armed modes are taken down as after any call)."""
+        def prefill_into(slots, reqs):
+            i = 0
+            while i < len(slots):                     # runs of neighbouring slots go through encode_prefill together (it pairs equal-length prompts)
+                j = i + 1
+                while j < len(slots) and slots[j] == slots[j - 1] + 1:
+                    j += 1
+                self.encode_prefill([r[0] for r in reqs[i:j]], [r[1] for r in reqs[i:j]], [list(r[2]) for r in reqs[i:j]], slots[i],
+                                    record_stages=True, share_prefix=False)
+                i = j
+            return slots
+
+        return self._queue(requests, prefill_into, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph)
+
+    def decode_queue(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, *, max_rows: Optional[int] = None,
+                     forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
+                     logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None, use_graph: bool = True):
+        """generate_queue's decode side alone, over KV slots that are prefilled already (what decode() is to generate()): request r decodes slot
+        slots[r] from head heads[r]; at most max_rows of them run together -> one (ids, head[, logprobs]) per slot, in the order given.  No slot
+        is recycled: every request keeps its own."""
+        slots = [int(s) for s in slots]
+        if len(set(slots)) != len(slots) or len(heads) != len(slots) or (forced is not None and len(forced) != len(slots)):
+            raise ValueError("one head (and forced row) per slot, every slot once")
+        reqs = [(None, None, s, int(h), None if forced is None else forced[r]) for r, (s, h) in enumerate(zip(slots, heads))]
+        return self._queue(reqs, lambda _, rs: [r[2] for r in rs], max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph)
+
+    def _queue(self, requests, place, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph):
+        """the one loop of generate_queue / decode_queue.  place(slots the book hands out, requests) -> the KV slots the rows decode from, prefilled"""
+        armed = logits is not None and not logits.off
+        bound = constraints is not None and not constraints.off
+        on_dev = sampling is not None and not sampling.greedy
+        if on_dev and not sampling.on_device:
+            raise ValueError("generate_queue needs the device decode loop: these sampling parameters lie outside the device sampler's domain")
+        if bound:
+            check_constraints(constraints.stop_sequences, constraints.bad_words_ids, constraints.suppress_tokens, constraints.begin_suppress_tokens,
+                              self.cfg.total_vocab)
+
+        def checked(req):
+            req = tuple(req)
+            if len(req) not in (4, 5):
+                raise ValueError("a request is (video, timestamps, input_ids, head[, forced ids])")
+            if (armed or bound) and len(req) == 5 and req[4] is not None:
+                raise ValueError("logits processors and constraints act on the ids a row has recorded; under forced ids those are not the fed ones "
+                                 "(a forced request with logits= / constraints=)")
+            return req if len(req) == 5 else req + (None,)
+
+        if isinstance(requests, (list, tuple)):
+            requests = [checked(r) for r in requests]
+        cap = max(1, min(int(max_rows) if max_rows else self.decode_batch_max, self.decode_batch_max, self.max_batch))
+        mn = int(max_new_tokens)
+        source, buf = iter(requests), []
+
+        def waiting(want: int) -> int:
+            """requests in hand, after pulling until `want` are (or the source is dry)"""
+            while len(buf) < want:
+                try:
+                    buf.append(checked(next(source)))
+                except StopIteration:
+                    break
+            return len(buf)
+
+        def forced_of(reqs):
+            if all(r[4] is None for r in reqs):
+                return None
+            return [list(r[4]) if r[4] is not None else [-1] * mn for r in reqs]
+
+        book = QueueBook(range(cap), logprobs)
+        read_lps = lambda ids: self.decode_read_logprobs([len(x) for x in ids]) if logprobs else None
+        if on_dev:
+            self.set_sampling(sampling)
+        if logprobs:
+            self.set_logprobs(True)
+        if armed:
+            self.set_logits_params(logits)
+        try:
+            if bound:
+                self.set_constraints(constraints)
+            while waiting(cap):
+                reqs = [buf.pop(0) for _ in range(min(cap, len(buf)))]
+                base = book.requests                   # the batch's first request: Philox row indices count from it, as decode_begin's do
+                slots = place(book.admit(len(reqs)), reqs)
+                self.decode_begin(slots, [int(r[3]) for r in reqs], mn, eos, forced_of(reqs))
+                own = [0] * len(reqs)                  # steps of its own every live row has taken
+                while True:
+                    # a boundary: look at the recorded ids, retire, admit — and look again at what an admission brought (a row whose token 0 ends it
+                    # leaves before it has ridden a chunk), until nothing more is admitted
+                    while True:
+                        ids, hd = self.decode_read()
+                        finished = [len(x) >= mn or ends_stopped(x, eos, constraints if bound else None) for x in ids]
+                        live = finished.count(False)
+                        if live == 0:
+                            break
+                        if retire_plan(len(ids), live, self.retire_fraction):
+                            keep = book.keep_list(finished)
+                            book.retire(keep, ids, hd, read_lps(ids))
+                            self.retire_rows(keep)
+                            own = [own[k] for k in keep]
+                        room = min(cap - len(own), len(book.free))
+                        k = admit_plan(len(own), cap, waiting(room), len(book.free), self.admit_fraction) if room > 0 else 0
+                        if not k:
+                            break
+                        reqs = [buf.pop(0) for _ in range(k)]
+                        first = book.requests
+                        slots = place(book.admit(k), reqs)
+                        self.admit_rows(slots, [int(r[3]) for r in reqs], row_ids=list(range(first - base, first - base + k)), forced=forced_of(reqs))
+                        own += [0] * k
+                    if live == 0:                     # the batch ended: whatever waits begins the next one
+                        book.finish(ids, hd, read_lps(ids))
+                        break
+                    n = min(max(1, int(self.retire_chunk)), mn - 1 - min(own))
+                    if n <= 0:
+                        raise RuntimeError("generate_queue: a row has taken max_new_tokens - 1 steps of its own and is not finished")
+                    self.decode_steps(n, use_graph)
+                    own = [s + n for s in own]
+            return book.results()
+        finally:
+            if bound:
+                self.set_constraints(None)
+            if armed:
+                self.set_logits_params(None)
+            if logprobs:
+                self.set_logprobs(False)
+            if on_dev:
+                self.set_sampling(None)
 
     def generate_samples(self, video: torch.Tensor, timestamps, prompt_ids: Sequence[int], head: int, n: int, max_new_tokens: int, eos: int = -1,
                          sampling: Optional[SamplingParams] = None, use_graph: bool = True, logits: Optional[LogitsParams] = None,

@@ -92,13 +92,17 @@ def parse_output_ids(ids: Sequence[int], tokenizer, model, stop_str: Optional[st
 @torch.no_grad()
 def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: str, *, num_frames: Optional[int] = None,
                     max_new_tokens: int = 512, batch_size: Optional[int] = None, conv_mode: str = "llama_2",
-                    device_preprocess: bool = True, pipeline: bool = True, sampling=None, logprobs: bool = False, logits=None) -> List[dict]:
+                    device_preprocess: bool = True, pipeline: bool = True, sampling=None, logprobs: bool = False, logits=None,
+                    continuous: bool = False) -> List[dict]:
     """items: dicts with "video" (decoded frames array / list / a reader with get_batch), optional "fps", "id", "query"
     (formatted into `prompt` as the tvg / vhd tasks do, evaluate.py:303-306).  Returns one result dict per item, in order, on
     every rank: {"video", "id", "timestamps", "scores", "captions", "output_ids"}.  sampling: a trace_amd.engine.SamplingParams (None = greedy),
     the same params and seed for every chunk.  logits: a trace_amd.sampling.LogitsParams (repetition penalty, no-repeat n-grams, min_new_tokens over the
     ids each row has generated; None = off).  logprobs: every result gains "output_logprobs", one float per entry of "output_ids" (the
-    device's per-token log-probabilities; their float bits cross the ranks in the same all-gather as the ids)."""
+    device's per-token log-probabilities; their float bits cross the ranks in the same all-gather as the ids).  continuous: the rank's items flow
+    through one running decode batch of `batch_size` rows (TraceEngine.generate_queue: rows that ended leave, the next items take their KV slots)
+    instead of fixed chunks; results of the same form in the same order, and the same results wherever the rounding of the batch sizes a row is
+    decoded in does not turn a greedy pick (off by default)."""
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
     world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
     eng = model.engine
@@ -115,19 +119,28 @@ def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: 
     local_lp: list = []
     eos = tokenizer.eos_token_id if getattr(tokenizer, "eos_token_id", None) is not None else -1
 
+    def prepared(it):
+        v, ts = process_video(it["video"], processor, aspect, nf, fps=it.get("fps"), engine=eng if device_preprocess else None)
+        q = prompt.format(it["query"].strip()) if it.get("query") is not None else prompt
+        return v if v.is_cuda else v.to(eng.device, eng.dtype), ts, build_prompt_ids(q, tokenizer, conv_mode).tolist()
+
     def chunks():
         for s0 in range(0, len(mine), bs):
             chunk = [items[i] for i in mine[s0: s0 + bs]]
             vids, tss, idl = [], [], []
             for it in chunk:
-                v, ts = process_video(it["video"], processor, aspect, nf, fps=it.get("fps"), engine=eng if device_preprocess else None)
-                vids.append(v if v.is_cuda else v.to(eng.device, eng.dtype))
+                v, ts, ids = prepared(it)
+                vids.append(v)
                 tss.append(ts)
-                q = prompt.format(it["query"].strip()) if it.get("query") is not None else prompt
-                idl.append(build_prompt_ids(q, tokenizer, conv_mode).tolist())
+                idl.append(ids)
             yield vids, tss, idl, [1] * len(chunk), None
 
-    if pipelined and len(mine) > bs:
+    if continuous:
+        requests = (prepared(items[i]) + (1,) for i in mine)        # preprocessed as the queue asks for them, one by one
+        for out, _, *lp in eng.generate_queue(requests, max_new_tokens, eos=eos, max_rows=bs, sampling=sampling, logprobs=logprobs, logits=logits):
+            local.append(out)
+            local_lp.extend(lp)
+    elif pipelined and len(mine) > bs:
         for out, _, *lp in eng.generate_stream(chunks(), max_new_tokens, eos=eos, sampling=sampling, logprobs=logprobs, logits=logits):
             local.extend(out)
             local_lp.extend(lp[0] if logprobs else [])
@@ -174,6 +187,7 @@ def main():
     ap.add_argument("--pipeline", dest="pipeline", action="store_true", default=True, help="(default) two-stage pipeline over the chunks: two banks of KV slots, a chunk decodes while the next is encoded")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="chunk by chunk, one bank of KV slots")
     ap.add_argument("--logprobs", action="store_true", help='add "output_logprobs" (per-token log-probabilities, aligned with "output_ids") to every result')
+    ap.add_argument("--continuous", action="store_true", help="continuous batching: one running decode batch that finished rows leave and waiting videos join")
     args = ap.parse_args()
     from .mm_utils import get_model_name_from_path
     from .model.builder import load_pretrained_model
@@ -183,7 +197,7 @@ def main():
                                                 max_batch=min(512, (2 if args.pipeline else 1) * args.batch_size), max_new_tokens=args.max_new_tokens)
     items = json.load(open(args.items))
     res = evaluate_videos(model, tok, proc, items, args.prompt, num_frames=args.num_frames, max_new_tokens=args.max_new_tokens,
-                          batch_size=args.batch_size, pipeline=args.pipeline, logprobs=args.logprobs)
+                          batch_size=args.batch_size, pipeline=args.pipeline, logprobs=args.logprobs, continuous=args.continuous)
     if rank == 0:
         with open(args.out, "w") as f:
             json.dump(res, f)
