@@ -281,6 +281,29 @@ int trace_decode_feed(trace_ctx* ctx, const int32_t* tokens, int B, void* stream
  * The params live in device memory: a captured decode step (use_graph) stays valid when they change between calls. */
 int trace_decode_set_sampling(trace_ctx* ctx, float temperature, int top_k, float top_p, uint64_t seed);
 
+/* The same with HF's remaining sampling warpers, applied between step 3 and the draw in HF's order (min_tokens_to_keep = 1 throughout); each sees
+ * the distribution renormalised over what the steps before it kept:
+ *   3a. min_p in [0, 1] (0 = off): drop p < min_p * p_max;
+ *   3b. typical_p in (0, 1] (1 = off): H = -sum p log p; order the tokens by |-log p - H| ascending; last = the number of tokens whose inclusive
+ *       cumulative probability in that order is < typical_p (at most the last index); keep every token whose |-log p - H| is <= that of the token
+ *       at `last` (equal values stay together).  This can drop the arg-max;
+ *   3c. epsilon_cutoff in [0, 1) (0 = off): drop p < epsilon_cutoff; tokens equal to the maximum always stay;
+ *   3d. eta_cutoff in [0, 1) (0 = off): eta = min(eta_cutoff, sqrt(eta_cutoff) * exp(-H)), H of the distribution it receives; drop p < eta; tokens
+ *       equal to the maximum always stay.
+ * The draw then walks what is left in the order of step 4.  size = sizeof(trace_sampling) as the caller compiled it (a smaller one -> TRACE_ERR_ARG).
+ * temperature <= 0 = greedy (the other fields are not read).  Domain: that of trace_decode_set_sampling, and top_k in [1, 1024] as soon as one of
+ * the four is armed; anything else -> TRACE_ERR_ARG.  With the four off it is trace_decode_set_sampling: the same ids from the same rows.
+ * trace_decode_set_sampling itself means "the four off". */
+typedef struct trace_sampling {
+    int32_t size;
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    uint64_t seed;
+    float min_p, typical_p, epsilon_cutoff, eta_cutoff;
+} trace_sampling;
+int trace_decode_set_sampling_ex(trace_ctx* ctx, const trace_sampling* sampling);
+
 /* Per-token log-probabilities, computed on the device inside the decode step.  Set before trace_decode_begin; it holds for every later batch
  * until changed (like trace_decode_set_sampling).  The first call with on != 0 allocates the masked-logits rows and [256][max_new_tokens] floats.
  * For row b at step s, with head = the row's active head at that step, [lo, hi) its id range, and x the RAW masked fp32 logits of that range as
@@ -512,6 +535,9 @@ int trace_op_skinny_fused_swiglu(const float* part_gu, int ks_gu, const void* W,
  * T > 0 and the domain above; row b uses counter (steps[b], 0, b, 0). */
 int trace_op_sample(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, float T, int top_k, float top_p,
                     uint64_t seed, const int32_t* steps, int32_t* out_ids, void* stream);
+/* trace_op_sample with the four warpers of trace_decode_set_sampling_ex (temperature > 0); trace_op_sample means "the four off". */
+int trace_op_sample_ex(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const trace_sampling* sampling,
+                       const int32_t* steps, int32_t* out_ids, void* stream);
 /* The log-probability above over loose rows, the same device code: logits [B][ld] fp32 device (only the head's range is read), heads / ids
  * int32 [B] device (active head, global vocabulary id), out fp32 [B] device; an id outside the head's range gives -inf. */
 int trace_op_token_logprob(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* ids, float* out,

@@ -43,6 +43,11 @@ class TraceConstraintsC(C.Structure):
                 ("suppress_ids", C.c_void_p), ("begin_suppress_ids", C.c_void_p)]
 
 
+class TraceSamplingC(C.Structure):
+    _fields_ = [("size", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("seed", C.c_uint64),
+                ("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/trace_hip.h declares
 P, I, F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
@@ -86,6 +91,7 @@ SIGNATURES = {
     "trace_decode_host_mode": (I, [P, I]),
     "trace_decode_feed": (I, [P, P, I, P]),
     "trace_decode_set_sampling": (I, [P, F, I, F, C.c_uint64]),
+    "trace_decode_set_sampling_ex": (I, [P, P]),
     "trace_decode_set_logprobs": (I, [P, I]),
     "trace_decode_read_logprobs": (I, [P, P, P]),
     "trace_decode_set_logits_params": (I, [P, F, I, I]),
@@ -137,6 +143,7 @@ SIGNATURES = {
     "trace_op_add_rmsnorm_ex": (I, [P, I, P, I, P, I, P, P, I, P, P, I, I, F, P]),
     "trace_op_skinny_fused_swiglu": (I, [P, I, P, P, I, I, I, P]),
     "trace_op_sample": (I, [P, I, I, P, I, I, I, F, I, F, C.c_uint64, P, P, P]),
+    "trace_op_sample_ex": (I, [P, I, I, P, I, I, I, P, P, P, P]),
     "trace_op_token_logprob": (I, [P, I, I, P, I, I, I, P, P, P]),
     "trace_op_logits_process": (I, [P, I, I, P, I, I, I, P, I, P, P, I, F, I, I, P, P]),
     "trace_op_logits_process_ex": (I, [P, I, I, P, I, I, I, P, I, P, P, I, F, I, I, C.POINTER(TraceConstraintsC), P, P]),

@@ -1911,9 +1911,36 @@ static const char* sampling_bad(float T, int k, float p) {
     if (k == 0 && p < 1.f) return "top_k = 0 (off) with top_p < 1 is outside the device sampler (sort of the whole head)";
     return nullptr;
 }
+// the four warpers behind top_p (trace_sampling): HF's domains, off values accepted, and top_k in [1, 1024] once one of them is armed
+static const char* warpers_bad(const trace_sampling& t) {
+    if (!(t.min_p >= 0.f && t.min_p <= 1.f)) return "min_p must lie in [0, 1]";
+    if (!(t.typical_p > 0.f && t.typical_p <= 1.f)) return "typical_p must lie in (0, 1] (1 = off)";
+    if (!(t.epsilon_cutoff >= 0.f && t.epsilon_cutoff < 1.f)) return "epsilon_cutoff must lie in [0, 1) (0 = off)";
+    if (!(t.eta_cutoff >= 0.f && t.eta_cutoff < 1.f)) return "eta_cutoff must lie in [0, 1) (0 = off)";
+    const bool armed = t.min_p > 0.f || t.typical_p < 1.f || t.epsilon_cutoff > 0.f || t.eta_cutoff > 0.f;
+    if (armed && t.top_k < 1)
+        return "top_k = 0 (off) with min_p / typical_p / epsilon_cutoff / eta_cutoff armed is outside the device sampler (sort of the whole head)";
+    return nullptr;
+}
+// a trace_sampling is checked in this order everywhere: the struct itself (null, size), then - behind the greedy shortcut of the decode entry - the domain
+static const char* sampling_struct_bad(const trace_sampling* t) {
+    if (!t) return "null trace_sampling";
+    if (t->size < (int32_t)sizeof(trace_sampling)) return "trace_sampling::size is smaller than this library's struct";
+    return nullptr;
+}
+static const char* sampling_domain_bad(const trace_sampling& t) {
+    if (const char* e = sampling_bad(t.temperature, t.top_k, t.top_p)) return e;
+    return warpers_bad(t);
+}
 static SampleParams make_sampling(float T, int k, float p, uint64_t seed) {
     SampleParams sp{};
     sp.temperature = T; sp.top_k = k; sp.top_p = p; sp.seed_lo = (uint32_t)seed; sp.seed_hi = (uint32_t)(seed >> 32);
+    sp.min_p = 0.f; sp.typical_p = 1.f; sp.epsilon = 0.f; sp.eta = 0.f; sp.sqrt_eta = 0.f;                    // the four off
+    return sp;
+}
+static SampleParams make_sampling(const trace_sampling& t) {
+    SampleParams sp = make_sampling(t.temperature, t.top_k, t.top_p, t.seed);
+    sp.min_p = t.min_p; sp.typical_p = t.typical_p; sp.epsilon = t.epsilon_cutoff; sp.eta = t.eta_cutoff; sp.sqrt_eta = sqrtf(t.eta_cutoff);
     return sp;
 }
 
@@ -1942,6 +1969,17 @@ extern "C" int trace_decode_set_sampling(trace_ctx* c, float temperature, int to
     if (!m.sample) return set_want(c, m);
     if (const char* e = sampling_bad(temperature, top_k, top_p)) return fail(TRACE_ERR_ARG, e);
     c->samp = make_sampling(temperature, top_k, top_p, seed);
+    return set_want(c, m);
+}
+
+extern "C" int trace_decode_set_sampling_ex(trace_ctx* c, const trace_sampling* t) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    if (const char* e = sampling_struct_bad(t)) return fail(TRACE_ERR_ARG, e);
+    if (t->temperature <= 0.f) return trace_decode_set_sampling(c, 0.f, 0, 1.f, 0);                      // greedy: the other fields are not read
+    if (const char* e = sampling_domain_bad(*t)) return fail(TRACE_ERR_ARG, e);
+    TailMode m = c->want;
+    m.sample = true;
+    c->samp = make_sampling(*t);
     return set_want(c, m);
 }
 
@@ -2153,6 +2191,16 @@ extern "C" int trace_op_sample(const float* logits, int ld, int B, const int32_t
     if (!logits || !heads || !steps || !out_ids) return fail(TRACE_ERR_ARG, "null pointer");
     if (const char* m = sampling_bad(T, top_k, top_p)) return fail(TRACE_ERR_ARG, m);
     const int rc = launch_sample_rows(logits, ld, B, heads, V, Tv, Sv, make_sampling(T, top_k, top_p, seed), steps, out_ids, (hipStream_t)stream);
+    if (rc != TRACE_OK) return fail(rc, "sample launch failed (B, ld or head widths out of range)");
+    return TRACE_OK;
+}
+
+extern "C" int trace_op_sample_ex(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const trace_sampling* t,
+                                  const int32_t* steps, int32_t* out_ids, void* stream) {
+    if (!logits || !heads || !steps || !out_ids) return fail(TRACE_ERR_ARG, "null pointer");
+    if (const char* m = sampling_struct_bad(t)) return fail(TRACE_ERR_ARG, m);
+    if (const char* m = sampling_domain_bad(*t)) return fail(TRACE_ERR_ARG, m);
+    const int rc = launch_sample_rows(logits, ld, B, heads, V, Tv, Sv, make_sampling(*t), steps, out_ids, (hipStream_t)stream);
     if (rc != TRACE_OK) return fail(rc, "sample launch failed (B, ld or head widths out of range)");
     return TRACE_OK;
 }

@@ -4,9 +4,10 @@
 //   2. top_k (1..1024): keep x >= the k-th largest value (ties at the threshold kept); k >= the row width keeps everything
 //   3. top_p (0 < p <= 1): order the survivors by (value desc, id asc); keep a token iff the mass ranked strictly above it is < p (the top
 //      token always stays) — HF's "ascending cumsum <= 1 - p is removed" read from the other end
+//   3b. min_p, typical_p, epsilon_cutoff, eta_cutoff (each optional, HF's order, top_k in [1, 1024] only): see sample_warp below
 //   4. draw u in [0, 1) (philox.h, counter = (step, 0, row, 0)); walk the kept tokens in that order accumulating exp(x - max); take the first
 //      whose running sum exceeds u * total, or the last kept token if rounding leaves none.
-// top_k = 0 (off) is taken only with top_p = 1: the walk is then over the whole row in id order.
+// top_k = 0 (off) is taken only with top_p = 1 and 3b off: the walk is then over the whole row in id order.
 // One workgroup of 256 threads per row.  Top-k threshold: exact radix select (4 passes of 8 bits, per-wave LDS histograms) on the order-
 // preserving uint32 key of x — no sort of the row.  The strictly-above set (< k <= 1024 entries) is bitonic-sorted in LDS; the tie class at the
 // threshold (any size) is a block of equally probable ids in id order: the top-p cut and the draw inside it are rank arithmetic plus one
@@ -25,18 +26,25 @@ struct SampleParams {            // device-resident next to the decode step's pa
     int32_t top_k;               // 0 = off (only with top_p == 1), else 1..1024
     float top_p;                 // (0, 1]
     uint32_t seed_lo, seed_hi;
+    float min_p;                 // [0, 1], 0 = off          the four below need top_k in [1, 1024]
+    float typical_p;             // (0, 1), >= 1 = off
+    float epsilon;               // (0, 1), 0 = off
+    float eta, sqrt_eta;         // (0, 1), 0 = off; sqrt_eta = sqrtf(eta), formed on the host (IEEE sqrt: one value everywhere)
 };
 constexpr int SAMPLE_MAX_K = 1024;
 constexpr int SAMPLE_THREADS = 256;
 
 struct SampleLds {
-    uint32_t hist[4][256];
+    union {                                  // (the same 4 KB: the histograms are done with before typical_p starts)
+        uint32_t hist[4][256];
+        float sk[SAMPLE_MAX_K];              // typical_p: (-log p_j) - H of the sorted candidates (non-decreasing in j)
+    };
     unsigned long long cand[SAMPLE_MAX_K];   // (~key << 32 | id): ascending order = (value desc, id asc)
     float cw[SAMPLE_MAX_K];                  // running sums of the sorted candidates' weights
     float fbuf[SAMPLE_THREADS];
     uint32_t ubuf[SAMPLE_THREADS];
     float wmax[4];
-    uint32_t n_above, n_tie, sel, krem;
+    uint32_t n_above, n_tie, sel, krem, amin;
     int result;
 };
 
@@ -83,7 +91,8 @@ __device__ __forceinline__ V sample_scan(V v, V* buf) {
     return v;
 }
 
-// log(s) for s >= 1 (finite): s = m 2^e with m in (sqrt(1/2), sqrt(2)], log m = 2 atanh(t), t = (m - 1) / (m + 1), as the odd series up to t^9
+// log(s) for a normal s > 0 (the sums here are >= 1; the mass typical_p keeps can be less): s = m 2^e with m in (sqrt(1/2), sqrt(2)],
+// log m = 2 atanh(t), t = (m - 1) / (m + 1), as the odd series up to t^9
 // (|t| <= 0.1716: the first dropped term is below 2e-9 of the result); e ln 2 from the same two-part ln 2 as sample_exp.  Every operation is
 // rounded on its own (a true fp32 division, no FMA contraction), constants in hex: a float32 restatement gives the same bits.
 __device__ __forceinline__ float sample_log(float s) {
@@ -147,6 +156,116 @@ __device__ inline float token_logprob_row(const float* __restrict__ row, int n, 
 
 __device__ __forceinline__ void sample_min_result(SampleLds& L, int v) {
     __hip_atomic_fetch_min(&L.result, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// ---- the warpers behind top_p: min_p, typical_p, epsilon_cutoff, eta_cutoff (HF's MinP / Typical / Epsilon / Eta LogitsWarper, in that order) ----
+// What top_p leaves is the sorted candidates [lo, hi) (lo = 0) followed by mk tokens of the tie block (one value tv, weight wt each).  Every warper
+// maps such a set to such a set: min_p, epsilon and eta cut the candidates' tail, typical_p keeps an interval of them (-log p is monotone along the
+// order); the tie block has one value, hence one key under every rule: it stays or goes whole, and it stays only while the candidates reach hi.
+// Each warper sees the distribution renormalised over what the earlier ones kept: Z = (cw[hi - 1] - cw[lo - 1]) + mk wt.
+__device__ __forceinline__ float sample_cand_x(const SampleLds& L, int j) { return sample_unkey(~(uint32_t)(L.cand[j] >> 32)); }
+
+__device__ __forceinline__ float sample_kept_z(const SampleLds& L, int lo, int hi, float mkwt) {
+#pragma clang fp contract(off)
+    return ((hi ? L.cw[hi - 1] : 0.f) - (lo ? L.cw[lo - 1] : 0.f)) + mkwt;
+}
+
+// Tail cut: the first j in [lo, hi) with w_j < thr whose value is below the top's (tokens equal to the maximum always stay), else hi; the tie block
+// follows if no candidate went and it is the top itself or its weight is not below thr.  L.result is 0x7fffffff on entry and on exit.
+__device__ __forceinline__ void sample_cut(SampleLds& L, int lo, int& hi, int& mk, float thr, float wt, float M) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    const uint32_t top = lo < hi ? (uint32_t)(L.cand[lo] >> 32) : 0u;
+    for (int j = lo + tid; j < hi; j += SAMPLE_THREADS) {
+        const uint32_t kj = (uint32_t)(L.cand[j] >> 32);
+        if (kj != top && sample_exp(sample_unkey(~kj) - M) < thr) sample_min_result(L, j);
+    }
+    __syncthreads();
+    const int r = min(L.result, hi);
+    __syncthreads();
+    if (tid == 0) L.result = 0x7fffffff;
+    if (r < hi || (lo < hi && wt < thr)) mk = 0;
+    hi = r;
+    __syncthreads();
+}
+
+// H = log Z - (sum_j w_j (x_j - M)) / Z over the kept set: thread t sums its candidates 4t .. 4t + 3 in order (0 outside [lo, hi)), sample_scan over
+// the thread totals, then the tie block's mk (wt (tv - M)); a weight of exactly 0 contributes 0.
+__device__ __forceinline__ float sample_entropy(SampleLds& L, int lo, int hi, int mk, float wt, float tv, float M, float Z) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = 4 * tid + q;
+        float e = 0.f;
+        if (j >= lo && j < hi) {
+            const float d = sample_cand_x(L, j) - M, w = sample_exp(d);
+            if (w > 0.f) e = w * d;
+        }
+        s = s + e;
+    }
+    sample_scan(s, L.fbuf);
+    float D = L.fbuf[SAMPLE_THREADS - 1];
+    __syncthreads();
+    const float te = wt > 0.f ? wt * (tv - M) : 0.f;
+    D = D + (float)mk * te;
+    return sample_log(Z) - D / Z;
+}
+
+// #{i in [0, n): sk[i] < x} and #{i: sk[i] <= x} of the non-decreasing sk
+__device__ __forceinline__ int sample_count_lt(const float* sk, int n, float x) {
+    int a = 0, b = n;
+    while (a < b) { const int c = (a + b) >> 1; if (sk[c] < x) a = c + 1; else b = c; }
+    return a;
+}
+__device__ __forceinline__ int sample_count_le(const float* sk, int n, float x) {
+    int a = 0, b = n;
+    while (a < b) { const int c = (a + b) >> 1; if (sk[c] <= x) a = c + 1; else b = c; }
+    return a;
+}
+
+// typical_p on candidates [0, hi) + mk ties: s_j = (log Z - (x_j - M)) - H is non-decreasing in j, a_j = |s_j| HF's sort key.  HF keeps a <= a*,
+// a* = the smallest key v whose class {a <= v} holds mass >= typical_p — the interval {-v <= s <= v} of the order, its mass a difference of two
+// running sums.  Every candidate (and the tie block) tries its own key; the smallest that qualifies wins (non-negative floats order as their bits).
+__device__ __forceinline__ void sample_typical(SampleLds& L, int& lo, int& hi, int& mk, float tp, float wt, float tv, float M) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    const float mkwt = (float)mk * wt;
+    const float Z = sample_kept_z(L, 0, hi, mkwt);
+    const float H = sample_entropy(L, 0, hi, mk, wt, tv, M, Z);
+    const float lZ = sample_log(Z);
+    for (int j = tid; j < hi; j += SAMPLE_THREADS) L.sk[j] = (lZ - (sample_cand_x(L, j) - M)) - H;
+    if (tid == 0) L.amin = 0x7f800000u;
+    __syncthreads();
+    const float st = (lZ - (tv - M)) - H, tpZ = tp * Z;
+    for (int j = tid; j < hi + (mk > 0 ? 1 : 0); j += SAMPLE_THREADS) {
+        const float v = fabsf(j < hi ? L.sk[j] : st);
+        const int l = sample_count_lt(L.sk, hi, -v), r = sample_count_le(L.sk, hi, v);
+        float mass = (r ? L.cw[r - 1] : 0.f) - (l ? L.cw[l - 1] : 0.f);
+        if (mk > 0 && st <= v) mass = mass + mkwt;
+        if (mass >= tpZ) __hip_atomic_fetch_min(&L.amin, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    const float a = __uint_as_float(L.amin);
+    const int l = sample_count_lt(L.sk, hi, -a), r = sample_count_le(L.sk, hi, a);
+    const int mt = mk > 0 && st <= a ? mk : 0;
+    if (l < r || mt > 0) { lo = l; hi = r; mk = mt; }                 // (an empty result can come only from NaNs: keep everything then)
+    __syncthreads();
+}
+
+// min_p -> typical_p -> epsilon -> eta over the set top_p left: candidates [0, hi) + mk ties in, candidates [lo, hi) + mk ties out
+__device__ __forceinline__ void sample_warp(SampleLds& L, const SampleParams& sp, int& lo, int& hi, int& mk, float wt, float tv, float M) {
+#pragma clang fp contract(off)
+    if (sp.min_p > 0.f) sample_cut(L, 0, hi, mk, sp.min_p, wt, M);      // p_j < min_p p_max: the top's weight is exp(0) = 1
+    if (sp.typical_p < 1.f) sample_typical(L, lo, hi, mk, sp.typical_p, wt, tv, M);
+    if (sp.epsilon > 0.f) sample_cut(L, lo, hi, mk, sp.epsilon * sample_kept_z(L, lo, hi, (float)mk * wt), wt, M);
+    if (sp.eta > 0.f) {
+        const float Z = sample_kept_z(L, lo, hi, (float)mk * wt);
+        const float H = sample_entropy(L, lo, hi, mk, wt, tv, M, Z);
+        const float eta = fminf(sp.eta, sp.sqrt_eta * sample_exp(-H));
+        sample_cut(L, lo, hi, mk, eta * Z, wt, M);
+    }
 }
 
 // row = the active head's logits [0, n); returns the chosen offset in [0, n) (every thread).  step / rowid feed the Philox counter.
@@ -284,12 +403,16 @@ __device__ inline int sample_row(const float* __restrict__ row, int n, const Sam
         }
         __syncthreads();
     }
-    const float Ak = na_keep ? L.cw[na_keep - 1] : 0.f;
+    // ---- min_p, typical_p, epsilon, eta: the kept candidates become [lo, na_keep); with all four off nothing below this line changes a bit
+    int lo = 0;
+    if (sp.min_p > 0.f || sp.typical_p < 1.f || sp.epsilon > 0.f || sp.eta > 0.f) sample_warp(L, sp, lo, na_keep, mk, wt, tv, M);
+    const float base = lo ? L.cw[lo - 1] : 0.f;
+    const float Ak = (na_keep ? L.cw[na_keep - 1] : 0.f) - base;
     const float target = u * (Ak + (float)mk * wt);
 
     // ---- draw: first kept candidate whose running sum exceeds the target, else inside the tie block
-    for (int j = tid; j < na_keep; j += SAMPLE_THREADS)
-        if (L.cw[j] > target) sample_min_result(L, j);
+    for (int j = lo + tid; j < na_keep; j += SAMPLE_THREADS)
+        if (L.cw[j] - base > target) sample_min_result(L, j);
     __syncthreads();
     const int jc = L.result;
     if (jc != 0x7fffffff) return (int)(uint32_t)L.cand[jc];

@@ -48,6 +48,9 @@ class TraceEngine:
     retire_fraction = RETIRE_FRACTION
     # ... and generate_queue admits waiting requests there once the room is at least 1 / admit_fraction of the cap (admit.admit_plan)
     admit_fraction = ADMIT_FRACTION
+    # The sampling warpers behind top_p that this engine's sampler applies (csrc/sample.h sample_warp; SamplingParams carries them).  The model class
+    # asks before it maps generate()'s arguments of these names: an engine that does not list a warper gets NotImplementedError, never a silent drop.
+    sampling_warpers = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
 
     def __init__(self, cfg: TraceConfig, device: int = 0, max_batch: int = 1, max_ctx: Optional[int] = None,
                  max_frames: Optional[int] = None, max_new_tokens: int = 1024, vit_batch_frames: Optional[int] = None,
@@ -644,13 +647,12 @@ class TraceEngine:
         _lib.check(self.lib.trace_decode_feed(self.h, _i32(tokens), len(tokens), _stream()))
 
     def set_sampling(self, sampling: Optional[SamplingParams]):
-        """Device sampling for the decode batches begun from now on (trace_decode_set_sampling); None or temperature <= 0 = greedy.
+        """Device sampling for the decode batches begun from now on (trace_decode_set_sampling_ex); None or temperature <= 0 = greedy.
         Only parameters inside the device sampler's domain (SamplingParams.on_device) are accepted here; decode() routes the others."""
         if sampling is None or sampling.greedy:
             _lib.check(self.lib.trace_decode_set_sampling(self.h, 0.0, 0, 1.0, 0))
         else:
-            _lib.check(self.lib.trace_decode_set_sampling(self.h, float(sampling.temperature), int(sampling.top_k), float(sampling.top_p),
-                                                          int(sampling.seed)))
+            _lib.check(self.lib.trace_decode_set_sampling_ex(self.h, C.byref(sampling_c(sampling))))
 
     def set_logits_params(self, logits: Optional[LogitsParams]):
         """Logits processors for the decode batches begun from now on (trace_decode_set_logits_params): repetition penalty, no-repeat n-grams and
@@ -1276,6 +1278,12 @@ def constraints_c(constraints: Constraints, n_vocab):
     return k, keep
 
 
+def sampling_c(sampling: SamplingParams):
+    """trace_sampling for the C ABI (trace_decode_set_sampling_ex / trace_op_sample_ex)"""
+    return _lib.TraceSamplingC(C.sizeof(_lib.TraceSamplingC), float(sampling.temperature), int(sampling.top_k), float(sampling.top_p), int(sampling.seed),
+                               float(sampling.min_p), float(sampling.typical_p), float(sampling.epsilon_cutoff), float(sampling.eta_cutoff))
+
+
 # ---- kernel-level wrappers for unit tests / microbenchmarks -------------------------------------
 class ops:
     element = "bf16"               # which library the wrappers call: "bf16" (libtrace_hip.so) or "f16" (libtrace_hip_f16.so); ops.use()
@@ -1291,7 +1299,7 @@ class ops:
 
     @staticmethod
     def sample(logits, heads, sampling: SamplingParams, steps, V: int, Tv: int, Sv: int, element=None):
-        """trace_op_sample: logits [B, ld >= V+1+Tv+Sv] fp32 (device) -> int32 ids [B] (device), row b drawn from head heads[b] with Philox step
+        """trace_op_sample_ex: logits [B, ld >= V+1+Tv+Sv] fp32 (device) -> int32 ids [B] (device), row b drawn from head heads[b] with Philox step
         steps[b] and row index b.  heads / steps: sequences of ints or int32 device tensors."""
         lib = _lib.load(element or ops.element)
         lg = logits.contiguous()
@@ -1300,8 +1308,7 @@ class ops:
         hd = heads if isinstance(heads, torch.Tensor) else torch.tensor([int(h) for h in heads], dtype=torch.int32, device=dev)
         st = steps if isinstance(steps, torch.Tensor) else torch.tensor([int(x) for x in steps], dtype=torch.int32, device=dev)
         out = torch.empty(B, dtype=torch.int32, device=dev)
-        _lib.check(lib.trace_op_sample(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, float(sampling.temperature), int(sampling.top_k),
-                                       float(sampling.top_p), int(sampling.seed), _ptr(st), _ptr(out), _stream()))
+        _lib.check(lib.trace_op_sample_ex(_ptr(lg), ld, B, _ptr(hd), V, Tv, Sv, C.byref(sampling_c(sampling)), _ptr(st), _ptr(out), _stream()))
         return out
 
     @staticmethod

@@ -180,7 +180,8 @@ class TraceMistralForCausalLM:
         stop_sequences (lists of global ids: a row ends once its generated ids end in one, the ids stay in the output): the same precedence, on
         the device inside the decode step (trace_amd/csrc/constrain.h) - no host loop.  stopping_criteria= still runs the host loop;
         mm_utils.stop_sequences_from_keywords(criterion) gives a KeywordsStoppingCriteria's ids for stop_sequences=.  Sampling follows HF's warpers (temperature -> top_k -> top_p ->
-        multinomial) on the device (trace_amd/csrc/sample.h); the 64-bit seed is drawn from torch's default generator, so torch.manual_seed
+        min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -> multinomial; the last four as keyword arguments with the same precedence, off by
+        default) on the device (trace_amd/csrc/sample.h); the 64-bit seed is drawn from torch's default generator, so torch.manual_seed
         makes a call reproducible.  temperature == 0 or do_sample=False: greedy.
         output_logprobs=True: instead of the id tensor, an object with `.sequences` (exactly that tensor), `.logprobs` (float32 [B, n], zero
         padded: the log-probability of every emitted token under the model's own, unwarped distribution of the row's active head, computed
@@ -403,22 +404,31 @@ class TraceMistralForCausalLM:
         return default
 
     # arguments of HF's generate() this build does not implement, with the value that means "off"
-    _UNSUPPORTED = {"num_beams": 1, "num_return_sequences": 1, "typical_p": 1.0, "min_p": None, "repetition_penalty": 1.0}
+    _UNSUPPORTED = {"num_beams": 1, "num_return_sequences": 1, "repetition_penalty": 1.0}
+    # HF's sampling warpers behind top_p, read from the keyword arguments, with the value that means "off" (None reads as off too).  The engine's
+    # sampler applies them: an armed one that the engine does not list in `sampling_warpers` is refused like the names above, never dropped.
+    _WARPERS = {"min_p": 0.0, "typical_p": 1.0, "epsilon_cutoff": 0.0, "eta_cutoff": 0.0}
 
     def _sampling_params(self, do_sample, temperature, top_k, top_p, generation_config, kwargs) -> Optional[SamplingParams]:
-        """HF's precedence (_pick).  None = greedy."""
+        """HF's precedence (_pick) for temperature / top_k / top_p and min_p / typical_p / epsilon_cutoff / eta_cutoff.  None = greedy."""
         gc = generation_config
         for name, off in self._UNSUPPORTED.items():
             v = self._pick(name, kwargs.get(name), gc)
             if v is not None and v != off:
                 raise NotImplementedError(f"{name}={v!r} is not implemented on the MI355X path (only {name}={off!r})")
+        warp, have = {}, getattr(self.engine, "sampling_warpers", ())
+        for name, off in self._WARPERS.items():
+            v = self._pick(name, kwargs.get(name), gc, off)
+            if v != off and name not in have:
+                raise NotImplementedError(f"{name}={v!r}: this model's engine does not implement `{name}` (only {name}={off!r})")
+            warp[name] = float(v)
         do_sample, temperature = bool(self._pick("do_sample", do_sample, gc)), float(self._pick("temperature", temperature, gc))
         top_k, top_p = self._pick("top_k", top_k, gc, 0), float(self._pick("top_p", top_p, gc))
-        check_sampling(temperature, top_k, top_p)
+        check_sampling(temperature, top_k, top_p, **warp)
         if not do_sample or temperature <= 0:
             return None
         g = torch.randint(0, 1 << 32, (2,), dtype=torch.int64)        # torch's default generator: torch.manual_seed(s) reproduces a call
-        return SamplingParams(temperature, int(top_k), top_p, (int(g[0]) << 32) | int(g[1]))
+        return SamplingParams(temperature, int(top_k), top_p, (int(g[0]) << 32) | int(g[1]), **warp)
 
     def _logits_params(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, generation_config) -> Optional[LogitsParams]:
         """repetition_penalty / no_repeat_ngram_size / min_new_tokens with HF's precedence (_pick).  None = all three off (the decode step then

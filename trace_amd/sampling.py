@@ -3,7 +3,7 @@
 `SamplingParams` is what Engine.decode / generate / generate_stream and evaluate_videos take.  `sample_row_ref` restates the device
 sampler in float32 numpy, operation by operation (the same exp polynomial, the same run sums and Hillis-Steele scan, the same rank
 arithmetic), so it returns the device's id bit for bit; it also serves as the host path for the parameter combinations the device does not
-take (top_k > 1024, or top_k = 0 with top_p < 1), where it applies the same rules.  `philox_uniform` is the RNG contract in numpy.
+take (top_k > 1024, or top_k = 0 with top_p < 1 or with min_p / typical_p / epsilon_cutoff / eta_cutoff armed), where it applies the same rules.  `philox_uniform` is the RNG contract in numpy.
 `token_logprob_ref` restates the per-token log-probability (sample.h token_logprob_row) the same way: the device's float bits.
 `LogitsParams` / `process_row_ref`: the logits processors of the decode step (repetition penalty, no-repeat n-grams, min_new_tokens:
 trace_amd/csrc/logits.h) and their float32 restatement, again bit for bit.
@@ -24,15 +24,23 @@ _F = np.float32
 
 @dataclass(frozen=True)
 class SamplingParams:
-    """HF sampling warpers in HF's order: temperature, top_k (50 = HF's default; 0 = off), top_p (1.0 = off).  seed: 64-bit Philox key;
-    the counter of row b at decode step s is (s, 0, b, 0).  temperature <= 0 means greedy."""
+    """HF sampling warpers in HF's order: temperature, top_k (50 = HF's default; 0 = off), top_p (1.0 = off), min_p (0 = off), typical_p
+    (1.0 = off), epsilon_cutoff (0 = off), eta_cutoff (0 = off); None for one of the last four is stored as its off value.  seed: 64-bit Philox key; the counter of row b at decode step s is
+    (s, 0, b, 0).  temperature <= 0 means greedy."""
     temperature: float = 1.0
     top_k: int = 50
     top_p: float = 1.0
     seed: int = 0
+    min_p: float = 0.0
+    typical_p: float = 1.0
+    epsilon_cutoff: float = 0.0
+    eta_cutoff: float = 0.0
 
     def __post_init__(self):
-        check_sampling(self.temperature, self.top_k, self.top_p)
+        for name, off in (("min_p", 0.0), ("typical_p", 1.0), ("epsilon_cutoff", 0.0), ("eta_cutoff", 0.0)):
+            if getattr(self, name) is None:                       # HF's other spelling of "off"
+                object.__setattr__(self, name, off)
+        check_sampling(self.temperature, self.top_k, self.top_p, self.min_p, self.typical_p, self.epsilon_cutoff, self.eta_cutoff)
         if not 0 <= int(self.seed) < 1 << 64:
             raise ValueError(f"seed must be a 64-bit unsigned integer, got {self.seed}")
 
@@ -41,13 +49,31 @@ class SamplingParams:
         return self.temperature <= 0
 
     @property
+    def warpers(self) -> tuple:
+        """(min_p, typical_p, epsilon_cutoff, eta_cutoff): what sample_row_ref takes behind u and info"""
+        return float(self.min_p), float(self.typical_p), float(self.epsilon_cutoff), float(self.eta_cutoff)
+
+    @property
+    def warpers_armed(self) -> bool:
+        return self.min_p > 0 or self.typical_p < 1.0 or self.epsilon_cutoff > 0 or self.eta_cutoff > 0
+
+    @property
     def on_device(self) -> bool:
-        """the device sampler's domain: top_k in [1, 1024] with any top_p, or top_k = 0 with top_p = 1"""
-        return 1 <= self.top_k <= DEVICE_MAX_K or (self.top_k == 0 and self.top_p >= 1.0)
+        """the device sampler's domain: top_k in [1, 1024] with anything else, or top_k = 0 with top_p = 1 and min_p / typical_p /
+        epsilon_cutoff / eta_cutoff off"""
+        return 1 <= self.top_k <= DEVICE_MAX_K or (self.top_k == 0 and self.top_p >= 1.0 and not self.warpers_armed)
 
 
-def check_sampling(temperature, top_k, top_p) -> None:
-    """HF's own argument checks (TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper)"""
+def check_sampling(temperature, top_k, top_p, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0) -> None:
+    """HF's own argument checks (Temperature / TopK / TopP / MinP / Typical / Epsilon / Eta LogitsWarper), HF's wording; the off values
+    (None, or min_p 0, typical_p 1.0, the cutoffs 0) pass"""
+    if min_p is not None and not 0.0 <= float(min_p) <= 1.0:
+        raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+    if typical_p is not None and float(typical_p) != 1.0 and not 0.0 < float(typical_p) < 1.0:
+        raise ValueError(f"`typical_p` has to be a float > 0 and < 1, but is {typical_p}")
+    for name, v in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
+        if v is not None and float(v) != 0.0 and not 0.0 < float(v) < 1.0:
+            raise ValueError(f"`{name}` has to be a float > 0 and < 1, but is {v}")
     t = float(temperature)
     if t != t or t in (float("inf"), float("-inf")):
         raise ValueError(f"`temperature` has to be a finite float, but is {temperature}")
@@ -129,14 +155,95 @@ def _run_sums(w, per):
     return (excl[:, None] + runs).reshape(-1), incl[-1]
 
 
-def sample_row_ref(row, temperature, top_k, top_p, u, info=None):
+class _Kept:
+    """What top_p leaves and the warpers behind it narrow (sample.h sample_warp): the sorted candidates [lo, hi) followed by mk tokens of
+    the tie block.  xo / ko / w: the candidates' values, keys and weights in (value desc, id asc) order, cw their running sums; tv / wt the
+    tie block's value and weight; per: the candidates per thread of the fixed-order sums (4 on the device)."""
+
+    def __init__(self, xo, ko, cw, hi, mk, tv, wt, M, per):
+        self.xo, self.ko, self.cw, self.lo, self.hi, self.mk, self.tv, self.wt, self.M, self.per = xo, ko, cw, 0, hi, mk, tv, wt, M, per
+        self.w = _sexp(xo - M)
+        self.margins = {}
+
+    def z(self):
+        cw, lo, hi = self.cw, self.lo, self.hi
+        return ((cw[hi - 1] if hi else _F(0.0)) - (cw[lo - 1] if lo else _F(0.0))) + _F(self.mk) * self.wt
+
+    def cut(self, thr, stage):
+        """sample_cut: the first candidate of [lo, hi) below thr whose key is not the top's ends the candidates; the tie block follows if
+        none went and it is the top itself or its weight is not below thr"""
+        lo, hi, w = self.lo, self.hi, self.w
+        low = (self.ko[lo:hi] != self.ko[lo]) if lo < hi else np.zeros(0, bool)
+        bad = np.nonzero(low & (w[lo:hi] < thr))[0]
+        r = lo + int(bad[0]) if len(bad) else hi
+        dist = np.abs(w[lo:hi][low] - thr)
+        if self.mk > 0 and lo < hi:
+            dist = np.append(dist, abs(self.wt - thr))
+        self.margins[stage] = float(dist.min() / thr) if len(dist) else np.inf
+        if r < hi or (lo < hi and self.wt < thr):
+            self.mk = 0
+        self.hi = r
+
+    def entropy(self, Z):
+        """sample_entropy: log Z - (sum w (x - M)) / Z, the sum in runs of `per` per thread over the candidates' slots (0 outside [lo, hi)
+        and where the weight is 0), then the scan, then the tie block's mk (wt (tv - M))"""
+        with np.errstate(invalid="ignore"):
+            e = np.where(self.w > 0, self.w * (self.xo - self.M), _F(0.0)).astype(np.float32)
+            te = self.wt * (self.tv - self.M) if self.wt > 0 else _F(0.0)
+        e[: self.lo] = 0
+        e[self.hi:] = 0
+        _, D = _run_sums(e, self.per)
+        D = D + _F(self.mk) * te
+        return _slog(np.array([Z], np.float32))[0] - D / Z
+
+    def typical(self, tp):
+        """sample_typical: s_j = (log Z - (x_j - M)) - H (non-decreasing), key a_j = |s_j|; a* = the smallest key v with
+        mass{-v <= s <= v} >= tp Z, the mass as a difference of two running sums (+ the tie block's); keep a <= a*.
+        This is the device's formulation restated, not a second algorithm: agreement with the device alone would not catch a shared misreading
+        of HF's rule.  That rests on the comparison with transformers' own TypicalLogitsWarper (tests/test_sampling_warpers_cpu.py) and on the
+        distribution test on the device (tests/test_gpu_sampling_warpers.py)."""
+        hi, mk, cw = self.hi, self.mk, self.cw
+        mkwt = _F(mk) * self.wt
+        Z = self.z()
+        H = self.entropy(Z)
+        lZ = _slog(np.array([Z], np.float32))[0]
+        nlp = (lZ - (self.xo[:hi] - self.M)).astype(np.float32)
+        sk = (nlp - H).astype(np.float32)
+        nlp_t = lZ - (self.tv - self.M)
+        st = nlp_t - H
+        tpZ = tp * Z
+        s_all = np.append(sk, st).astype(np.float32) if mk > 0 else sk
+        v = np.abs(s_all)
+        l, r = np.searchsorted(sk, -v, "left"), np.searchsorted(sk, v, "right")
+        cw0 = np.concatenate([np.zeros(1, np.float32), cw[:hi]])
+        mass = (cw0[r] - cw0[l]).astype(np.float32)
+        if mk > 0:
+            mass = np.where(st <= v, mass + mkwt, mass).astype(np.float32)
+        ok = mass >= tpZ
+        a = v[ok].min() if ok.any() else _F(np.inf)
+        # margins: every mass against tp Z; every key against a*, relative to the two terms its s was formed from (tokens of a*'s own value aside)
+        x_all = np.append(self.xo[:hi], self.tv) if mk > 0 else self.xo[:hi]
+        scale = (np.append(nlp, nlp_t) if mk > 0 else nlp) + H
+        other = x_all != x_all[np.nonzero(ok & (v == a))[0][0]] if ok.any() else np.zeros(len(v), bool)
+        da = (np.abs(v - a) / scale)[other]
+        self.margins["typical_p"] = float(min((np.abs(mass - tpZ) / tpZ).min(), da.min() if len(da) else np.inf))
+        l, r = int(np.searchsorted(sk, -a, "left")), int(np.searchsorted(sk, a, "right"))
+        mt = mk if mk > 0 and st <= a else 0
+        if l < r or mt > 0:
+            self.lo, self.hi, self.mk = l, r, mt
+
+
+def sample_row_ref(row, temperature, top_k, top_p, u, info=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
     """The device sampler on one head row (float32 [n]): the chosen offset in [0, n).  `info` (a dict, optional) receives the kept
-    offsets in walk order ('kept'), the running sums ('cum'), and the target ('target') — for tests."""
+    offsets in walk order ('kept'), the running sums ('cum'), and the target ('target') — for tests; behind top_k also 'stages': the kept
+    offsets after top_p and after each armed warper, 'margins': per stage the smallest relative distance of a compared quantity to its
+    threshold over the stage's keep-or-drop decisions, and 'margin': the smallest of those."""
     x = np.asarray(row, np.float32) / _F(temperature)
     n = len(x)
     u = _F(u)
     p = _F(top_p)
-    if top_k <= 0 and p >= _F(1.0):
+    armed = min_p > 0 or typical_p < 1.0 or epsilon_cutoff > 0 or eta_cutoff > 0
+    if top_k <= 0 and p >= _F(1.0) and not armed:
         M = x.max()
         w = _sexp(x - M)
         C = (n + _THREADS - 1) // _THREADS
@@ -167,11 +274,13 @@ def sample_row_ref(row, temperature, top_k, top_p, u, info=None):
     wt = _sexp(np.array([tv - M], np.float32))[0]
     Z = A + _F(m) * wt
     na_keep, mk = na, m
+    margins = {}
     if p < _F(1.0):
         pZ = p * Z
         above_mass = np.concatenate([np.zeros(1, np.float32), cw[:-1]]) if na else cw
         bad = np.nonzero(above_mass >= pZ)[0]
         na_keep = int(bad[0]) if len(bad) else na
+        dist = np.abs(above_mass[1:] - pZ)
         if na_keep < na:
             mk = 0
         else:
@@ -179,15 +288,43 @@ def sample_row_ref(row, temperature, top_k, top_p, u, info=None):
             mk = 0 if q <= 0 else (m if q >= _F(m) else min(m, int(np.ceil(q))))
             if na == 0 and mk < 1:
                 mk = 1
-    Ak = cw[na_keep - 1] if na_keep else _F(0.0)
+            if info is not None:
+                with np.errstate(invalid="ignore"):
+                    dist = np.append(dist, np.abs(A + np.arange(1 if na == 0 else 0, m, dtype=np.float32) * wt - pZ))
+        margins["top_p"] = float(np.nanmin(dist) / pZ) if len(dist) else np.inf
+    lo = 0
+    stages = {"top_p": np.concatenate([order[:na_keep], ties[:mk]])}
+    if armed:
+        # ---- sample.h sample_warp: min_p -> typical_p -> epsilon -> eta, each on the set the one before it kept
+        K = _Kept(x[order], keys[order], cw, na_keep, mk, tv, wt, M, per)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            if min_p > 0:
+                K.cut(_F(min_p), "min_p")                              # p_j < min_p p_max: the top's weight is exp(0) = 1
+                stages["min_p"] = np.concatenate([order[K.lo:K.hi], ties[:K.mk]])
+            if typical_p < 1.0:
+                K.typical(_F(typical_p))
+                stages["typical_p"] = np.concatenate([order[K.lo:K.hi], ties[:K.mk]])
+            if epsilon_cutoff > 0:
+                K.cut(_F(epsilon_cutoff) * K.z(), "epsilon_cutoff")
+                stages["epsilon_cutoff"] = np.concatenate([order[K.lo:K.hi], ties[:K.mk]])
+            if eta_cutoff > 0:
+                Z3 = K.z()
+                H3 = K.entropy(Z3)
+                eta = min(_F(eta_cutoff), np.sqrt(_F(eta_cutoff)) * _sexp(np.array([-H3], np.float32))[0])
+                K.cut(eta * Z3, "eta_cutoff")
+                stages["eta_cutoff"] = np.concatenate([order[K.lo:K.hi], ties[:K.mk]])
+        lo, na_keep, mk = K.lo, K.hi, K.mk
+        margins.update(K.margins)
+    base = cw[lo - 1] if lo else _F(0.0)
+    Ak = (cw[na_keep - 1] if na_keep else _F(0.0)) - base
     target = u * (Ak + _F(mk) * wt)
     if info is not None:
         tcum = Ak + (np.arange(1, mk + 1, dtype=np.float32) * wt).astype(np.float32)
-        info.update(kept=np.concatenate([order[:na_keep], ties[:mk]]), cum=np.concatenate([cw[:na_keep], tcum]).astype(np.float32),
-                    target=target, total=Ak + _F(mk) * wt)
-    hit = np.nonzero(cw[:na_keep] > target)[0]
+        info.update(kept=np.concatenate([order[lo:na_keep], ties[:mk]]), cum=np.concatenate([cw[lo:na_keep] - base, tcum]).astype(np.float32),
+                    target=target, total=Ak + _F(mk) * wt, stages=stages, margins=margins, margin=min(margins.values(), default=np.inf))
+    hit = np.nonzero(cw[lo:na_keep] - base > target)[0]
     if len(hit):
-        return int(order[hit[0]])
+        return int(order[lo + hit[0]])
     if mk == 0:
         return int(order[na_keep - 1])
     r = (target - Ak) / wt
@@ -461,5 +598,5 @@ def sample_rows_host(logits, heads, V, Tv, Sv, params: SamplingParams, steps):
     for b in range(lg.shape[0]):
         lo, hi = head_bounds(heads[b], V, Tv, Sv)
         u = philox_uniform(params.seed, int(steps[b]), b)
-        out.append(lo + sample_row_ref(lg[b, lo:hi], params.temperature, params.top_k, params.top_p, u))
+        out.append(lo + sample_row_ref(lg[b, lo:hi], params.temperature, params.top_k, params.top_p, u, None, *params.warpers))
     return out
