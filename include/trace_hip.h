@@ -353,6 +353,41 @@ int trace_decode_read_logprobs(trace_ctx* ctx, float* out, void* stream);
  * setting together with forced != NULL (the history is the recorded ids, which under forced ids are not the fed ones). */
 int trace_decode_set_logits_params(trace_ctx* ctx, float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens);
 
+/* Per-row generation parameters.  One trace_row_params per row of a decode batch: the row's own sampling (its own seed included), its own logits
+ * processors and its own max_new, so that a greedy request, a sampled one and a 16-token one next to a 512-token one share one running batch.
+ * trace_decode_set_row_params hands rows [n] (HOST) to the NEXT trace_decode_begin, whose B must equal n (else TRACE_ERR_ARG from that begin); that
+ * begin consumes the request whatever it answers.  NULL or n == 0 = off: a batch begun without a request is what it has always been, launch for launch.
+ * size = sizeof the struct as the caller compiled it, the same in every entry and the stride of the array; smaller than this library's -> TRACE_ERR_ARG.
+ * Domain per row: `sampling` as trace_decode_set_sampling_ex takes it (temperature <= 0: this row is greedy and the rest of `sampling` is not read;
+ * the nested size field is read for a sampled row), the three processors as trace_decode_set_logits_params takes them, max_new in 1 .. the max_new
+ * given to trace_decode_begin.  Everything else -> TRACE_ERR_ARG: domain errors from trace_decode_set_row_params itself (max_new there against the
+ * context's max_new_tokens), a max_new above the batch's from the begin.
+ * What a per-row batch does: the selection reads row b's params — a sampled row draws as under trace_decode_set_sampling_ex with ITS seed at
+ * counter (the row's own step, 0, its Philox row index, 0); a greedy row takes the arg-max over its head range, the lowest id among equal maxima —
+ * and the row's own max_new bounds what it records, feeds from `forced`, advances and log-scores; the max_new of the begin stays the stride of the
+ * ids / forced / log-probability rows and of trace_decode_read.  A row that has recorded its own max_new ids is stepped on without recording or
+ * advancing, as a row past max_new is after an admission.  trace_decode_steps is refused only when no row has n steps of its own left, and
+ * prefill + the row's own max_new must fit max_ctx.  The logits processors' launch runs when any row's processors or a ban rule of the constraints is
+ * armed (decided at begin and at every admission).  Such a batch captures its steps into graph places of its own.
+ * Everything else stays batch-wide: a per-row batch ignores trace_decode_set_sampling / _ex and trace_decode_set_logits_params; eos, the constraints,
+ * the log-probabilities switch and the shared prefix are the batch's.  Forced ids are refused (TRACE_ERR_ARG) only for a row whose processors are
+ * armed and that is fed an id within its own max_new, or for any row when constraints are armed.  Host-select mode: TRACE_ERR_STATE (from the
+ * setter, and from a begin that finds a request).  trace_decode_retire moves a row's params with the row.
+ * trace_decode_admit_ex is trace_decode_admit with rows [n] (HOST) for the admitted rows, written before their token 0 is selected.  Rows go into a
+ * batch begun with row params only through it with rows != NULL (trace_decode_admit, which is _ex with rows == NULL, answers TRACE_ERR_STATE there);
+ * rows != NULL into a batch begun without them is TRACE_ERR_STATE.  Its other errors are trace_decode_admit's, with the row's own max_new in the
+ * max_ctx check.  After an error the batch is as it was: all argument and state checks come before anything is queued, as in trace_decode_admit. */
+typedef struct trace_row_params {
+    int32_t size;
+    trace_sampling sampling;
+    float repetition_penalty;
+    int32_t no_repeat_ngram_size, min_new_tokens;
+    int32_t max_new;
+} trace_row_params;
+int trace_decode_set_row_params(trace_ctx* ctx, const trace_row_params* rows, int n);
+int trace_decode_admit_ex(trace_ctx* ctx, const int32_t* slots, int n, const int32_t* heads, const int32_t* row_ids, const int32_t* forced,
+                          const trace_row_params* rows, void* stream);
+
 /* Constraints (generate(bad_words_ids=, suppress_tokens=, begin_suppress_tokens=, stop_sequences=, eos_token_id=[a, b, ...])): HF
  * NoBadWordsLogitsProcessor, SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor and id-level stop sequences, on the device inside
  * the decode step.  Notation as above: row b, device step s, head range [lo, hi), history h = out_ids[b][0 .. out_len[b]): generated ids only, as

@@ -48,6 +48,11 @@ class TraceSamplingC(C.Structure):
                 ("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
 
 
+class TraceRowParamsC(C.Structure):
+    _fields_ = [("size", C.c_int32), ("sampling", TraceSamplingC), ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32),
+                ("min_new_tokens", C.c_int32), ("max_new", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/trace_hip.h declares
 P, I, F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
@@ -88,6 +93,8 @@ SIGNATURES = {
     "trace_decode_read": (I, [P, P, P, P, P]),
     "trace_decode_retire": (I, [P, P, I, P]),
     "trace_decode_admit": (I, [P, P, I, P, P, P, P]),
+    "trace_decode_set_row_params": (I, [P, P, I]),
+    "trace_decode_admit_ex": (I, [P, P, I, P, P, P, P, P]),
     "trace_decode_host_mode": (I, [P, I]),
     "trace_decode_feed": (I, [P, P, I, P]),
     "trace_decode_set_sampling": (I, [P, F, I, F, C.c_uint64]),

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libtrace_hip.so")
 LIB_F16 = os.path.join(HERE, "libtrace_hip_f16.so")
-SOURCES = ["gemm", "gemm_ldr", "gemm_pers", "gemm_w4", "norm", "vit", "patch_embed", "attn", "slot_pool", "llm", "decode", "fp8", "w4", "kv8", "stc", "preproc", "sample", "select", "retire", "constrain", "logits", "score", "engine"]
+SOURCES = ["gemm", "gemm_ldr", "gemm_pers", "gemm_w4", "norm", "vit", "patch_embed", "attn", "slot_pool", "llm", "decode", "fp8", "w4", "kv8", "stc", "preproc", "sample", "select", "select_rows", "retire", "constrain", "logits", "score", "engine"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 
 

@@ -50,10 +50,13 @@ static size_t pf_rows(int max_ctx) { return std::max<size_t>((size_t)PF_MAX * ma
 constexpr int MAX_SLOTS = 512;   // KV-cache sequence slots per context (a decode batch is at most SK_ROWS of them)
 static int g_ctx_per_dev[16] = {0};
 // what the tail of a decode step does beyond the plain arg-max; index(): its place in the graph cache, 0 = the plain step
+// per_row: the batch carries per-row generation parameters (trace_decode_set_row_params) — places 16 .. 31, which no batch without them ever takes
 struct TailMode {
-    bool sample = false, logprobs = false, process = false, stop = false;
-    int index() const { return (sample ? 1 : 0) + (logprobs ? 2 : 0) + (process ? 4 : 0) + (stop ? 8 : 0); }
+    bool sample = false, logprobs = false, process = false, stop = false, per_row = false;
+    int index() const { return (sample ? 1 : 0) + (logprobs ? 2 : 0) + (process ? 4 : 0) + (stop ? 8 : 0) + (per_row ? 16 : 0); }
 };
+constexpr int TAIL_MODES = 32;
+static_assert(sizeof(SampleParams) == 4 * retire_rowp_ints(0) && sizeof(LogitsParams) == 4 * retire_rowp_ints(1), "retire.hip moves the per-row params as ints");
 
 static bool constraints_on(const ConstrainTable& t) { return t.n_stop || t.n_bad || t.n_suppress || t.n_begin; }
 
@@ -153,7 +156,7 @@ struct trace_ctx {
     // attention, so a captured step is good for one (slot, rows) pair: a graph entry has two ways keyed by it (the two banks of a pipelined caller).
     int sh_want_slot = -1, sh_want_rows = 0, sh_slot = -1, sh_rows = 0;
     struct StepGraph { hipGraphExec_t exec = nullptr; int sh_slot = -1, sh_rows = 0; };
-    StepGraph graphs[16][SK_ROWS + 1][2];
+    StepGraph graphs[TAIL_MODES][SK_ROWS + 1][2];
     int graph_evict = 0;               // the way the next miss of a full entry replaces
     // sampling (trace_decode_set_sampling): host copy of the params; the device copy d_sparams, written at trace_decode_begin, is what the selection
     // kernel reads (a captured graph stays valid across calls).  d_slog: the [SK_ROWS][NV] raw masked logits of a step with anything armed.
@@ -171,6 +174,17 @@ struct trace_ctx {
     LogitsParams lgp{1.f, 0, 0};
     LogitsParams* d_lgparams = nullptr;
     float* d_plog = nullptr;
+    // per-row generation parameters (trace_decode_set_row_params, trace_decode_admit_ex): three arrays of SK_ROWS entries beside d_row_id / d_step0 that
+    // the tail of a batch begun with them reads instead of d_sparams / d_lgparams / d_params[0] (StepState::row_sp / row_lp / row_max_new); they move
+    // with the row (trace_decode_retire) and keep their addresses, which the captured steps hold.  h_row_*: the host copies (the bounds of
+    // trace_decode_steps, the decision whether logits_process runs); want_rows: the request the next trace_decode_begin consumes.
+    SampleParams* d_row_sp = nullptr;
+    LogitsParams* d_row_lp = nullptr;
+    int32_t* d_row_max = nullptr;
+    SampleParams h_row_sp[SK_ROWS];
+    LogitsParams h_row_lp[SK_ROWS];
+    int32_t h_row_max[SK_ROWS] = {0};
+    std::vector<trace_row_params> want_rows;
     // constraints (trace_decode_set_constraints, constrain.h): the host copy of the table; the device copy d_ctab, written at trace_decode_begin, is what
     // logits_process_kernel (the ban rules: want.process is "any logits param or any ban rule") and select_next_kernel (want.stop) read.  It exists from
     // the first arming of either, so a captured step of either kind always holds its address.
@@ -507,6 +521,7 @@ static int ctx_create(const trace_config* cfg, int device_id, int kv8, int w4, t
     // decode batch in flight on another stream and needs no host copy or synchronisation per call
     A(c->hl_val, (size_t)SK_ROWS * c->ntiles); A(c->hl_idx, (size_t)SK_ROWS * c->ntiles);
     A(c->d_heads_tmp, 3 * SK_ROWS); A(c->d_slots, SK_ROWS); A(c->d_pos, SK_ROWS); A(c->d_heads, SK_ROWS); A(c->d_done, SK_ROWS); A(c->d_out_len, SK_ROWS); A(c->d_row_id, SK_ROWS); A(c->d_step0, SK_ROWS); A(c->d_step, 4); A(c->d_params, 4); A(c->d_sparams, 1); A(c->d_lgparams, 1);
+    A(c->d_row_sp, SK_ROWS); A(c->d_row_lp, SK_ROWS); A(c->d_row_max, SK_ROWS);
     A(c->d_out_ids, (size_t)SK_ROWS * cfg->max_new_tokens); A(c->d_forced, (size_t)SK_ROWS * cfg->max_new_tokens);
 #undef A
     if (rc == TRACE_OK && hipHostMalloc((void**)&c->h_ring, Lm * 8 * trace_ctx::NSTAGE_H) != hipSuccess) rc = fail(TRACE_ERR_HIP, "hipHostMalloc");
@@ -1421,6 +1436,7 @@ static StepState step_state(trace_ctx* c, TailRows t = {0, 0}) {
     st.heads = c->d_heads + r0; st.pos = c->d_pos + r0; st.done = c->d_done + r0; st.out_ids = c->d_out_ids + r0 * c->max_new; st.out_len = c->d_out_len + r0;
     st.step = t.r0 ? c->d_step + 2 : c->d_step; st.forced = c->d_forced + r0 * c->max_new; st.params = c->d_params; st.row_id = c->d_row_id + r0;
     st.step0 = t.r0 ? nullptr : c->d_step0;
+    if (c->armed.per_row) { st.row_sp = c->d_row_sp + r0; st.row_lp = c->d_row_lp + r0; st.row_max_new = c->d_row_max + r0; }
     return st;
 }
 
@@ -1451,7 +1467,9 @@ static int head_and_select(trace_ctx* c, const bf16_t* xn, int advance, float* l
     if (m.process) LCHK(launch_step_logits_process(raw, step_state(c, t), t.n, c->V, c->Tv, c->Sv, c->d_lgparams, c->d_plog + lg0, s, c->d_ctab));
     // 4. the selection: a draw from the rows, the arg-max over a processed row, or the arg-max over the tile partials (they describe the raw row);
     //    with stop sequences armed, the instantiation that matches them against the recorded ids
-    const int form = m.sample ? SELECT_SAMPLE : m.process ? SELECT_ROW : SELECT_TILES;
+    //    a batch with per-row params: the form that takes either by the row's own params, over the processed rows where any row's processors or the
+    //    batch's ban rules are armed (m.process, decided at begin / admit from the host copy), else over the raw ones
+    const int form = m.per_row ? SELECT_PER_ROW : m.sample ? SELECT_SAMPLE : m.process ? SELECT_ROW : SELECT_TILES;
     TRY(select_only(c, form, form == SELECT_TILES ? nullptr : m.process ? c->d_plog + lg0 : raw, advance, s, t));
     // 5. the log-probability of the token just recorded (it reads out_ids / out_len / the advanced step counter), on the raw rows
     if (m.logprobs) LCHK(launch_step_logprob(raw, step_state(c, t), t.n, c->V, c->Tv, c->Sv, c->d_logprobs + (size_t)t.r0 * c->max_new, s));
@@ -1660,9 +1678,17 @@ extern "C" int trace_decode_set_shared_prefix(trace_ctx* c, int slot, int rows) 
     return TRACE_OK;
 }
 
+static const char* row_params_convert(const trace_row_params& r, int cap, SampleParams& sp, LogitsParams& lp, int32_t& mx);
+static const char* row_forced_bad(const trace_ctx* c, const int32_t* forced, int n, int max_new, const LogitsParams* lp, const int32_t* mx);
+static bool logits_armed(const LogitsParams& p) { return p.penalty != 1.f || p.ngram != 0 || p.min_new != 0; }
+static bool constraint_bans(const ConstrainTable& t) { return t.n_bad || t.n_suppress || t.n_begin; }
+
 extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, const int32_t* heads, int max_new, int eos,
                                   const int32_t* forced, float* logits_out, void* stream) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    // the per-row request (trace_decode_set_row_params) is this call's alone: taken here, whatever the call then answers
+    std::vector<trace_row_params> want_rows;
+    want_rows.swap(c->want_rows);
     if (!slots || !heads || B < 1 || B > c->max_B || B > (c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS)) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS) + " sequences decode together)");
     if (max_new < 1 || max_new > c->c.max_new_tokens) return fail(TRACE_ERR_ARG, "max_new exceeds capacity");
     hipStream_t s = (hipStream_t)stream;
@@ -1670,6 +1696,16 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     const int sh_slot = c->sh_want_slot, sh_rows = B > 1 ? c->sh_want_rows : 0;
     c->sh_want_slot = -1; c->sh_want_rows = 0;
     if (sh_rows > 0 && c->slot_len[sh_slot] < sh_rows) return fail(TRACE_ERR_STATE, "the shared slot holds fewer rows than the shared prefix");
+    const bool per_row = !want_rows.empty();
+    std::vector<SampleParams> rsp(per_row ? B : 0);
+    std::vector<LogitsParams> rlp(per_row ? B : 0);
+    std::vector<int32_t> rmx(per_row ? B : 0);
+    if (per_row) {
+        if (c->host_mode) return fail(TRACE_ERR_STATE, "per-row params are not available in host-select mode");
+        if ((int)want_rows.size() != B) return fail(TRACE_ERR_ARG, "trace_decode_set_row_params gave " + std::to_string(want_rows.size()) + " rows, the batch has " + std::to_string(B));
+        for (int b = 0; b < B; ++b)
+            if (const char* e = row_params_convert(want_rows[b], max_new, rsp[b], rlp[b], rmx[b])) return fail(TRACE_ERR_ARG, "row " + std::to_string(b) + ": " + e);
+    }
     int32_t pos[SK_ROWS], zero[SK_ROWS] = {0}, iota[SK_ROWS];
     for (int b = 0; b < B; ++b) {
         iota[b] = b;
@@ -1677,10 +1713,12 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
         if (c->slot_len[slots[b]] < sh_rows) return fail(TRACE_ERR_ARG, "a sequence is shorter than the shared prefix");
         if (heads[b] < 0 || heads[b] > 2) return fail(TRACE_ERR_ARG, "head must be 0, 1 or 2");
         pos[b] = c->slot_len[slots[b]];
-        if (pos[b] + max_new > c->max_ctx) return fail(TRACE_ERR_ARG, "prefill + max_new_tokens exceeds max_ctx");
+        if (pos[b] + (per_row ? rmx[b] : max_new) > c->max_ctx) return fail(TRACE_ERR_ARG, "prefill + max_new_tokens exceeds max_ctx");
         for (int b2 = 0; b2 < b; ++b2) if (slots[b2] == slots[b]) return fail(TRACE_ERR_ARG, "duplicate slot");
     }
-    if (forced && (c->want.process || c->want.stop) && !c->host_mode)
+    if (per_row) {
+        if (const char* e = row_forced_bad(c, forced, B, max_new, rlp.data(), rmx.data())) return fail(TRACE_ERR_ARG, e);
+    } else if (forced && (c->want.process || c->want.stop) && !c->host_mode)
         return fail(TRACE_ERR_ARG, "logits processors / constraints (trace_decode_set_logits_params, trace_decode_set_constraints) with forced ids: the "
                                    "history is the recorded ids, not the fed ones");
     c->B = B; c->max_new = max_new; c->eos = eos; c->has_forced = forced != nullptr;
@@ -1702,10 +1740,23 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     HIPCHK(hipMemcpyAsync(c->d_params, prm, 12, hipMemcpyHostToDevice, s));
     // host-select mode arms nothing: the host holds the logits and calls trace_op_logits_process / trace_op_sample / trace_op_token_logprob on them
     c->armed = c->host_mode ? TailMode{} : c->want;
+    if (per_row) {      // the batch-wide sampling and logits params are ignored: every row brings its own; constraints and log-probabilities stay the batch's
+        TailMode m;
+        m.per_row = true; m.logprobs = c->want.logprobs; m.stop = c->ctab.n_stop != 0;
+        m.process = constraint_bans(c->ctab);
+        for (int b = 0; b < B; ++b) {
+            c->h_row_sp[b] = rsp[b]; c->h_row_lp[b] = rlp[b]; c->h_row_max[b] = rmx[b];
+            m.process = m.process || logits_armed(rlp[b]);
+        }
+        c->armed = m;
+        HIPCHK(hipMemcpyAsync(c->d_row_sp, c->h_row_sp, B * sizeof(SampleParams), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_row_lp, c->h_row_lp, B * sizeof(LogitsParams), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_row_max, c->h_row_max, B * 4, hipMemcpyHostToDevice, s));
+    }
     if (c->armed.sample) HIPCHK(hipMemcpyAsync(c->d_sparams, &c->samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     if (c->armed.logprobs) HIPCHK(hipMemsetAsync(c->d_logprobs, 0, (size_t)B * max_new * 4, s));    // entries past a row's length stay 0.0
     if (c->armed.process) HIPCHK(hipMemcpyAsync(c->d_lgparams, &c->lgp, sizeof(LogitsParams), hipMemcpyHostToDevice, s));
-    if (c->armed.process || c->armed.stop)       // the whole table, or the header alone when it is empty (the processors' kernel reads its four counts)
+    if (c->armed.process || c->armed.stop || per_row)       // the whole table, or the header alone when it is empty (the processors' kernel reads its four counts; a per-row batch may arm them at an admission)
         HIPCHK(hipMemcpyAsync(c->d_ctab, &c->ctab, constraints_on(c->ctab) ? sizeof(ConstrainTable) : 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     c->fed = 0; c->steps_done = 0;
     if (forced) HIPCHK(hipMemcpyAsync(c->d_forced, forced, (size_t)B * max_new * 4, hipMemcpyHostToDevice, s));
@@ -1723,7 +1774,7 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
     if (logits_out && (n != 1 || use_graph)) return fail(TRACE_ERR_ARG, "logits_out needs n == 1 and eager mode");
     if (c->host_mode && (n != 1 || use_graph)) return fail(TRACE_ERR_ARG, "host-select mode runs one eager step at a time");
     // every step appends one KV row at pos[b]++; decode_begin checked pos + max_new <= max_ctx once, so the total is bounded here
-    if (!c->admitted) {
+    if (!c->admitted && !c->armed.per_row) {
         if (c->steps_done + n > c->max_new - 1)
             return fail(TRACE_ERR_STATE, "decode steps exceed max_new - 1 since trace_decode_begin (" + std::to_string(c->steps_done) + " taken, " +
                                          std::to_string(n) + " requested, max_new " + std::to_string(c->max_new) + ")");
@@ -1736,7 +1787,8 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
         // that same row pos0 + max_new - 1 and attends pos0 + max_new rows.  The admission (like trace_decode_begin) checked pos0 + max_new <= max_ctx,
         // so pos0 + max_new - 1 <= max_ctx - 1: inside the row's own slot and inside the RoPE tables, whatever the number of such steps.
         int most = 0;                                 // the most steps any row of the batch may still take
-        for (int b = 0; b < c->B; ++b) most = std::max(most, c->max_new - 1 - (c->steps_done - c->h_step0[b]));
+        // With per-row params the same holds with the row's own max_new in place of the batch's: pos[b] stops at pos0 + own - 1, and begin / admit checked pos0 + own <= max_ctx.
+        for (int b = 0; b < c->B; ++b) most = std::max(most, (c->armed.per_row ? c->h_row_max[b] : c->max_new) - 1 - (c->steps_done - c->h_step0[b]));
         if (n > most)
             return fail(TRACE_ERR_STATE, "decode steps exceed max_new - 1 for every row of the batch (" + std::to_string(n) + " requested, at most " +
                                          std::to_string(most) + " left to any row, max_new " + std::to_string(c->max_new) + ")");
@@ -1748,7 +1800,7 @@ extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* log
     if (!use_graph) {
         for (int i = 0; i < n; ++i) { c->step_in_call = steps_before + i; TRY(decode_step(c, logits_out, s)); }
     } else {
-        trace_ctx::StepGraph* ways = c->graphs[c->armed.index()][c->B];
+        trace_ctx::StepGraph* ways = c->graphs[c->armed.index()][c->B];     // (index() < TAIL_MODES by its construction)
         trace_ctx::StepGraph* way = nullptr;
         for (int w = 0; w < 2 && !way; ++w)
             if (ways[w].exec && ways[w].sh_slot == c->sh_slot && ways[w].sh_rows == c->sh_rows) way = &ways[w];
@@ -1818,11 +1870,13 @@ extern "C" int trace_decode_retire(trace_ctx* c, const int32_t* keep, int n_keep
     a.small[0] = c->d_slots; a.small[1] = c->d_pos; a.small[2] = c->d_heads; a.small[3] = c->d_done; a.small[4] = c->d_out_len; a.small[5] = c->d_row_id; a.small[6] = c->d_step0;
     a.wide[0] = c->d_out_ids; a.wide[1] = c->d_forced; a.wide[2] = c->armed.logprobs ? reinterpret_cast<int32_t*>(c->d_logprobs) : nullptr;
     a.x = c->dX; a.H = c->H; a.max_new = c->max_new;
+    if (c->armed.per_row) { a.rowp[0] = reinterpret_cast<int32_t*>(c->d_row_sp); a.rowp[1] = reinterpret_cast<int32_t*>(c->d_row_lp); a.rowp[2] = c->d_row_max; }
     HIPCHK(hipMemcpyAsync(c->d_retire, keep, (size_t)n_keep * 4, hipMemcpyHostToDevice, s));
     LCHK(launch_retire(a, c->d_retire, n_keep, B, c->d_retire + SK_ROWS, s));
     HIPCHK(hipStreamSynchronize(s));                 // the caller's keep list must outlive the async copy
     c->pos_sum = 0;
-    for (int i = 0; i < n_keep; ++i) { c->h_pos0[i] = c->h_pos0[keep[i]]; c->h_step0[i] = c->h_step0[keep[i]]; c->h_slots[i] = c->h_slots[keep[i]]; c->pos_sum += c->h_pos0[i]; }      // (keep[i] >= i: read before overwritten)
+    for (int i = 0; i < n_keep; ++i) { c->h_pos0[i] = c->h_pos0[keep[i]]; c->h_step0[i] = c->h_step0[keep[i]]; c->h_slots[i] = c->h_slots[keep[i]]; c->pos_sum += c->h_pos0[i];
+                                       c->h_row_sp[i] = c->h_row_sp[keep[i]]; c->h_row_lp[i] = c->h_row_lp[keep[i]]; c->h_row_max[i] = c->h_row_max[keep[i]]; }      // (keep[i] >= i: read before overwritten)
     c->B = n_keep;
     if (n_keep == 1) { c->sh_slot = -1; c->sh_rows = 0; }      // one sequence shares with nobody (as at trace_decode_begin): its own slot holds the same rows
     return TRACE_OK;
@@ -1837,15 +1891,24 @@ extern "C" int trace_decode_retire(trace_ctx* c, const int32_t* keep, int n_keep
 // step adds 1), and the origin of the new rows is written by the host from that number, steps_done: the next common step reads counter steps_done + 1,
 // their local step 1.  Everything is queued on the caller's stream, in order, between two steps; the next step's graph or launches see B + n rows
 // whose check-in count is B + n, so its last workgroup, and no earlier one, advances the shared counter.
-extern "C" int trace_decode_admit(trace_ctx* c, const int32_t* slots, int n, const int32_t* heads, const int32_t* row_ids, const int32_t* forced,
-                                  void* stream) {
+// rows: one trace_row_params per admitted row, for a batch begun with them (and only for such a batch) — written at [B, B + n) of the per-row arrays before
+// the rows' token 0 is selected.
+extern "C" int trace_decode_admit_ex(trace_ctx* c, const int32_t* slots, int n, const int32_t* heads, const int32_t* row_ids, const int32_t* forced,
+                                     const trace_row_params* rows, void* stream) {
     if (!c || c->B < 1) return fail(TRACE_ERR_STATE, "trace_decode_admit: no decode batch is running (trace_decode_begin not called)");
     if (c->host_mode) return fail(TRACE_ERR_STATE, "trace_decode_admit is not available in host-select mode");
     if (c->sh_rows > 0) return fail(TRACE_ERR_STATE, "trace_decode_admit: the running batch attends a shared prefix; admitted rows would have to hold the same rows");
     if (!slots || !heads || !row_ids || n < 1) return fail(TRACE_ERR_ARG, "trace_decode_admit: bad slots / heads / row_ids / n");
+    const bool per_row = c->armed.per_row;
+    if (per_row && !rows) return fail(TRACE_ERR_STATE, "trace_decode_admit: the running batch was begun with per-row params; admit into it through trace_decode_admit_ex with rows");
+    if (!per_row && rows) return fail(TRACE_ERR_STATE, "trace_decode_admit_ex: the running batch was begun without per-row params (trace_decode_set_row_params)");
     const int B = c->B, cap = std::min(c->max_B, c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS), max_new = c->max_new;
     if (n > cap - B) return fail(TRACE_ERR_ARG, "trace_decode_admit: " + std::to_string(B) + " running + " + std::to_string(n) + " admitted rows exceed the cap (at most " + std::to_string(cap) + " sequences decode together)");
     int32_t pos[SK_ROWS], zero[SK_ROWS] = {0}, org[SK_ROWS];
+    std::vector<SampleParams> rsp(per_row ? n : 0);
+    std::vector<LogitsParams> rlp(per_row ? n : 0);
+    std::vector<int32_t> rmx(per_row ? n : 0);
+    if (per_row && rows[0].size < (int32_t)sizeof(trace_row_params)) return fail(TRACE_ERR_ARG, "trace_row_params::size is smaller than this library's struct");
     for (int i = 0; i < n; ++i) {
         if (slots[i] < 0 || slots[i] >= c->max_B || c->slot_len[slots[i]] <= 0) return fail(TRACE_ERR_STATE, "trace_decode_admit: slot not prefilled");
         for (int b = 0; b < B; ++b) if (c->h_slots[b] == slots[i]) return fail(TRACE_ERR_ARG, "trace_decode_admit: slot " + std::to_string(slots[i]) + " is already in the running batch");
@@ -1853,12 +1916,28 @@ extern "C" int trace_decode_admit(trace_ctx* c, const int32_t* slots, int n, con
         if (heads[i] < 0 || heads[i] > 2) return fail(TRACE_ERR_ARG, "trace_decode_admit: head must be 0, 1 or 2");
         if (row_ids[i] < 0) return fail(TRACE_ERR_ARG, "trace_decode_admit: row_ids must not be negative");
         pos[i] = c->slot_len[slots[i]];
-        if (pos[i] + max_new > c->max_ctx) return fail(TRACE_ERR_ARG, "trace_decode_admit: prefill + max_new_tokens exceeds max_ctx");
+        if (per_row) {
+            const trace_row_params* r = reinterpret_cast<const trace_row_params*>(reinterpret_cast<const char*>(rows) + (size_t)i * rows[0].size);   // (the caller's stride)
+            if (r->size != rows[0].size) return fail(TRACE_ERR_ARG, "trace_decode_admit_ex: every trace_row_params must carry the same size");
+            if (const char* e = row_params_convert(*r, max_new, rsp[i], rlp[i], rmx[i])) return fail(TRACE_ERR_ARG, "trace_decode_admit_ex: row " + std::to_string(i) + ": " + e);
+        }
+        if (pos[i] + (per_row ? rmx[i] : max_new) > c->max_ctx) return fail(TRACE_ERR_ARG, "trace_decode_admit: prefill + max_new_tokens exceeds max_ctx");
         org[i] = c->steps_done;
     }
-    if (forced && (c->armed.process || c->armed.stop))
+    if (per_row) {
+        if (const char* e = row_forced_bad(c, forced, n, max_new, rlp.data(), rmx.data())) return fail(TRACE_ERR_ARG, std::string("trace_decode_admit_ex: ") + e);
+    } else if (forced && (c->armed.process || c->armed.stop))
         return fail(TRACE_ERR_ARG, "trace_decode_admit: forced ids with logits processors / constraints armed: the history is the recorded ids, not the fed ones");
     hipStream_t s = (hipStream_t)stream;
+    if (per_row) {      // host copies behind the batch's rows first (the copies below read them), then the device entries [B, B + n)
+        for (int i = 0; i < n; ++i) {
+            c->h_row_sp[B + i] = rsp[i]; c->h_row_lp[B + i] = rlp[i]; c->h_row_max[B + i] = rmx[i];
+            if (logits_armed(rlp[i])) c->armed.process = true;       // from here on logits_process runs for the batch (a tail of its own graph place)
+        }
+        HIPCHK(hipMemcpyAsync(c->d_row_sp + B, c->h_row_sp + B, n * sizeof(SampleParams), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_row_lp + B, c->h_row_lp + B, n * sizeof(LogitsParams), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_row_max + B, c->h_row_max + B, n * 4, hipMemcpyHostToDevice, s));
+    }
     const size_t wide0 = (size_t)B * max_new, wide_n = (size_t)n * max_new;
     HIPCHK(hipMemcpyAsync(c->d_slots + B, slots, n * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_row_id + B, row_ids, n * 4, hipMemcpyHostToDevice, s));
@@ -1882,12 +1961,17 @@ extern "C" int trace_decode_admit(trace_ctx* c, const int32_t* slots, int n, con
     return TRACE_OK;
 }
 
+extern "C" int trace_decode_admit(trace_ctx* c, const int32_t* slots, int n, const int32_t* heads, const int32_t* row_ids, const int32_t* forced,
+                                  void* stream) {
+    return trace_decode_admit_ex(c, slots, n, heads, row_ids, forced, nullptr, stream);
+}
+
 extern "C" int trace_debug_step_graphs(trace_ctx* c, int32_t* sizes, int cap) {
     if (!c) return 0;
     int n = 0;
     for (int B = 1; B <= SK_ROWS; ++B) {
         bool any = false;
-        for (int m = 0; m < 16 && !any; ++m) any = c->graphs[m][B][0].exec || c->graphs[m][B][1].exec;
+        for (int m = 0; m < TAIL_MODES && !any; ++m) any = c->graphs[m][B][0].exec || c->graphs[m][B][1].exec;
         if (any) { if (sizes && n < cap) sizes[n] = B; ++n; }
     }
     return n;
@@ -2002,6 +2086,62 @@ extern "C" int trace_decode_set_logits_params(trace_ctx* c, float repetition_pen
     if (const char* m = logits_params_bad(repetition_penalty, no_repeat_ngram_size, min_new_tokens)) return fail(TRACE_ERR_ARG, m);
     c->lgp = LogitsParams{repetition_penalty, no_repeat_ngram_size, min_new_tokens};
     return set_want(c, c->want);
+}
+
+// ---- per-row generation parameters ----
+// one trace_row_params -> the device structs of its row; a message, or null.  cap: the largest max_new the row may ask for
+static const char* row_params_convert(const trace_row_params& r, int cap, SampleParams& sp, LogitsParams& lp, int32_t& mx) {
+    if (r.size < (int32_t)sizeof(trace_row_params)) return "trace_row_params::size is smaller than this library's struct";
+    if (std::isnan(r.sampling.temperature)) return "temperature is NaN";
+    sp = SampleParams{};                                                   // temperature 0: the row is greedy, the rest of `sampling` is not read
+    if (r.sampling.temperature > 0.f) {
+        if (const char* e = sampling_struct_bad(&r.sampling)) return e;
+        if (const char* e = sampling_domain_bad(r.sampling)) return e;
+        sp = make_sampling(r.sampling);
+    }
+    if (const char* e = logits_params_bad(r.repetition_penalty, r.no_repeat_ngram_size, r.min_new_tokens)) return e;
+    lp = LogitsParams{r.repetition_penalty, r.no_repeat_ngram_size, r.min_new_tokens};
+    if (r.max_new < 1 || r.max_new > cap) return "max_new of a row must lie in [1, the max_new given to trace_decode_begin]";
+    mx = r.max_new;
+    return nullptr;
+}
+// forced ids [n][max_new] against the rows' processors: refused for a row whose processors are armed and that is fed an id within its own max_new, and
+// for any row once the constraints are armed (the history is the recorded ids, not the fed ones)
+static const char* row_forced_bad(const trace_ctx* c, const int32_t* forced, int n, int max_new, const LogitsParams* lp, const int32_t* mx) {
+    if (!forced) return nullptr;
+    if (constraint_bans(c->ctab) || c->ctab.n_stop) return "forced ids with constraints armed: the history is the recorded ids, not the fed ones";
+    for (int b = 0; b < n; ++b) {
+        if (!logits_armed(lp[b])) continue;
+        for (int i = 0; i < mx[b]; ++i)
+            if (forced[(size_t)b * max_new + i] >= 0) return "forced ids on a row whose logits processors are armed: the history is the recorded ids, not the fed ones";
+    }
+    return nullptr;
+}
+
+extern "C" int trace_decode_set_row_params(trace_ctx* c, const trace_row_params* rows, int n) {
+    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
+    c->want_rows.clear();
+    if (!rows || n == 0) return TRACE_OK;
+    if (c->host_mode) return fail(TRACE_ERR_STATE, "per-row params are not available in host-select mode");
+    if (n < 0 || n > SK_ROWS) return fail(TRACE_ERR_ARG, "trace_decode_set_row_params: n must lie in [0, 256]");
+    if (rows[0].size < (int32_t)sizeof(trace_row_params)) return fail(TRACE_ERR_ARG, "trace_row_params::size is smaller than this library's struct");
+    std::vector<trace_row_params> take(n);
+    for (int i = 0; i < n; ++i) {
+        const trace_row_params* r = reinterpret_cast<const trace_row_params*>(reinterpret_cast<const char*>(rows) + (size_t)i * rows[0].size);   // (the caller's stride)
+        if (r->size != rows[0].size) return fail(TRACE_ERR_ARG, "trace_decode_set_row_params: every trace_row_params must carry the same size");
+        SampleParams sp; LogitsParams lp; int32_t mx;
+        if (const char* e = row_params_convert(*r, c->c.max_new_tokens, sp, lp, mx)) return fail(TRACE_ERR_ARG, "trace_decode_set_row_params: row " + std::to_string(i) + ": " + e);
+        take[i] = *r;
+    }
+    // what the tail of such a batch may read: the raw rows, the processed rows (a row's processors may arm them at an admission), the constraint table
+    if (!c->d_ctab) {
+        TRY(dalloc(c, &c->d_ctab, 1));
+        HIPCHK(hipMemset(c->d_ctab, 0, sizeof(ConstrainTable)));
+    }
+    if (!c->d_slog) TRY(dalloc(c, &c->d_slog, (size_t)SK_ROWS * c->NV));
+    if (!c->d_plog) TRY(dalloc(c, &c->d_plog, (size_t)SK_ROWS * c->NV));
+    c->want_rows.swap(take);
+    return TRACE_OK;
 }
 
 // trace_constraints -> the table, bounded and checked: a message, or null.  NV > 0: every id must lie in [0, NV).

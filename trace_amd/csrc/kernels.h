@@ -214,6 +214,7 @@ int launch_head_logits(const bf16_t* X, int ldx, const bf16_t* Wh, int H, const 
                        float* part_val, int32_t* part_idx, float* logits_out, int B, hipStream_t s);
 // token selection + state machine + next-token embedding (select.hip)
 struct SampleParams;   // sample.h
+struct LogitsParams;   // logits.h
 struct StepState {
     int32_t* heads;       // [B] in/out
     int32_t* pos;         // [B] in/out (position of the NEXT token to be written)
@@ -225,6 +226,10 @@ struct StepState {
     const int32_t* params;// device [3]: max_new, eos, record_feed (device-resident so a captured graph stays valid)
     const int32_t* row_id;// [B] the Philox row index of each row (the index it had at trace_decode_begin: trace_decode_retire moves it with the row); null = b
     const int32_t* step0; // [B] the value of *step at which the row's own step 0 happened (0 for a row of trace_decode_begin; trace_decode_admit); null = 0
+    // per-row generation parameters (trace_decode_set_row_params); null = the batch-wide value
+    const SampleParams* row_sp;    // [B] the row's sampler params, temperature <= 0 = the row is greedy (SELECT_PER_ROW)
+    const LogitsParams* row_lp;    // [B] the row's logits processors (logits_process_kernel's decode-step form)
+    const int32_t* row_max_new;    // [B] the row's own max_new (<= params[0], which stays the stride of out_ids / forced): the guards of the selection and of the log-probability launch
 };
 // Retiring rows of a decode batch (retire.hip): every per-row array of the step, gathered to its first n_keep rows through a scratch copy.
 constexpr int RETIRE_SMALL = 7;
@@ -233,20 +238,26 @@ struct RetireArgs {
     int32_t* wide[3];               // [B][max_new] each: out_ids, forced, the log-probabilities' bits (null where not armed)
     bf16_t* x;                      // [B][H] the next step's input embedding
     int H, max_new;
+    int32_t* rowp[3];               // the per-row generation parameters as ints, retire_rowp_ints(q) per row: SampleParams, LogitsParams, max_new (all null: a batch without them)
 };
-// ints of one scratch row: 8 for the small arrays, three max_new-rows padded to 16 bytes, the embedding row
-__host__ __device__ constexpr size_t retire_row_ints(int max_new, int H) { return 8 + 3 * (size_t)((max_new + 3) & ~3) + (size_t)(H >> 1); }
+__host__ __device__ constexpr int retire_rowp_ints(int q) { return q == 0 ? 10 : q == 1 ? 3 : 1; }
+// ints of one scratch row: 8 for the small arrays, three max_new-rows padded to 16 bytes, the embedding row, 16 for the per-row parameters
+__host__ __device__ constexpr size_t retire_row_ints(int max_new, int H) { return 8 + 3 * (size_t)((max_new + 3) & ~3) + (size_t)(H >> 1) + 16; }
 // new row i <- former row keep[i] (device int32 [n_keep], strictly increasing within [0, B): the caller checks); scratch: n_keep * retire_row_ints ints, 16-byte aligned
 int launch_retire(const RetireArgs& a, const int32_t* keep, int n_keep, int B, int32_t* scratch, hipStream_t s);
 // The one launcher of select_next_kernel, by form.  SELECT_TILES: the arg-max over launch_head_logits' partials (logits and sp null).  SELECT_SAMPLE:
 // a draw by sample.h's sampler from rows `logits` [B][NV] fp32 (masked, raw or processed) under the device params *sp.  SELECT_ROW: the arg-max
-// over the head's range of such rows, the lowest id among equal maxima as the partials have it (sp null).
-enum { SELECT_TILES = 0, SELECT_SAMPLE = 1, SELECT_ROW = 2 };
+// over the head's range of such rows, the lowest id among equal maxima as the partials have it (sp null).  SELECT_PER_ROW: row b under its own
+// st.row_sp[b] — SELECT_SAMPLE's draw with the row's params and seed where its temperature is > 0, SELECT_ROW's arg-max otherwise — and its own
+// st.row_max_new[b] in every max_new guard (sp null; st.row_sp and st.row_max_new set).
+enum { SELECT_TILES = 0, SELECT_SAMPLE = 1, SELECT_ROW = 2, SELECT_PER_ROW = 3 };
 // stop: a device-resident constraint table (constrain.h) whose stop sequences end a row like EOS — the instantiations with the stop match; null: the plain ones.
 struct ConstrainTable; // constrain.h
 int launch_select(int form, const float* part_val, const int32_t* part_idx, const float* logits, const SampleParams* sp, const StepState& st,
                   const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H,
                   int V, int Tv, int Sv, int advance, hipStream_t s, const ConstrainTable* stop = nullptr);
+int launch_select_rows(const float* logits, const StepState& st, const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row,
+                       bf16_t* xnext, int ldx, int B, int H, int V, int Tv, int Sv, int advance, hipStream_t s, const ConstrainTable* stop);      // (select_rows.hip: SELECT_PER_ROW; launch_select routes to it)
 int launch_select_stop(int form, const float* part_val, const int32_t* part_idx, const float* logits, const SampleParams* sp, const StepState& st,
                        const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B, int H,
                        int V, int Tv, int Sv, int advance, hipStream_t s, const ConstrainTable* ct);      // (constrain.hip; launch_select routes to it)
@@ -273,11 +284,11 @@ int launch_score_rows(const bf16_t* X, int ld, const bf16_t* W, int ldw, int K, 
 // logits processors (logits.h: repetition penalty, no-repeat n-grams, min_new_tokens) from a row of masked logits into a row of their own.
 // Loose rows: hist int32 [B][ld_hist] / hist_len / heads / steps int32 [B] (device), out [B][ldo] written whole, -inf outside the head
 // (trace_op_logits_process).  Decode step: between launch_head_logits and the selection of the same step, history = st.out_ids / st.out_len,
-// params *dlp (device), rows [B][NV] -> [B][NV] (the head's range only), which launch_select's SELECT_SAMPLE / SELECT_ROW forms then read.
+// params *dlp (device) or, where st.row_lp is set, st.row_lp[b]; rows [B][NV] -> [B][NV] (the head's range only), which launch_select's
+// SELECT_SAMPLE / SELECT_ROW / SELECT_PER_ROW forms then read.
 // ct: the device-resident constraint table (constrain.h) whose ban rules follow the three processors in the same launch — bad words, suppress,
 // begin-suppress, and min_new_tokens over every stop sequence of one id; null = none (loose rows only: the step always passes the context's table).
 // launch_stop_match: the stop rule over loose histories, fired int32 [B] device = 1 where a stop sequence equals the tail of hist[b][0 .. hist_len[b]).
-struct LogitsParams;   // logits.h
 int launch_logits_process(const float* logits, int ld, int B, const int32_t* heads, int V, int Tv, int Sv, const int32_t* hist, int ld_hist,
                           const int32_t* hist_len, const int32_t* steps, int eos, const LogitsParams& lp, float* out, int ldo, hipStream_t s,
                           const ConstrainTable* ct = nullptr);

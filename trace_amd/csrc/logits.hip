@@ -15,14 +15,15 @@ namespace {
 //     output row [0, V+1+Tv+Sv) is written, -inf outside the head.
 //   decode step (dparams != null): launched before select_next_kernel of the same step, so *steps is this step's counter (the previous step's
 //     selection finished earlier on the stream), and *steps - step0[b] the row's own step (min_new_tokens and begin-suppress count from it); the history is out_ids / out_len, its stride max_new = dparams[0], eos = dparams[1], the params
-//     *dlp — everything a captured graph must not freeze is read from device memory.  Only the head's range of the output row is written.
+//     *dlp, or row_lp[b] where the batch carries per-row params (StepState::row_lp) — everything a captured graph must not freeze is read from device memory.  Only the head's range of the output row is written.
 __global__ __launch_bounds__(LOGITS_THREADS) void logits_process_kernel(const float* __restrict__ logits, int ld, const int32_t* __restrict__ heads,
                                                                         int V, int Tv, int Sv, const int32_t* __restrict__ hist, int ld_hist,
                                                                         const int32_t* __restrict__ hist_len, const int32_t* __restrict__ steps,
                                                                         int eos, LogitsParams lpv, const int32_t* __restrict__ dparams,
                                                                         const LogitsParams* __restrict__ dlp, float* __restrict__ out, int ldo,
                                                                         int seen_words, const ConstrainTable* __restrict__ ct,
-                                                                        const int32_t* __restrict__ step0) {
+                                                                        const int32_t* __restrict__ step0,
+                                                                        const LogitsParams* __restrict__ row_lp) {
     extern __shared__ __attribute__((aligned(16))) uint32_t seen[];
     __shared__ int32_t suffix[LOGITS_MAX_NGRAM];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(LOGITS_THREADS) void logits_process_kernel(const fl
     if (((hi - lo + 31) >> 5) > seen_words) return;                     // (the launcher sizes the bitmap for the widest head: never taken)
     int step;
     LogitsParams lp;
-    if (dparams) { ld_hist = dparams[0]; eos = dparams[1]; lp = *dlp; step = steps[0] - (step0 ? step0[b] : 0); }      // the row's own step (StepState::step0)
+    if (dparams) { ld_hist = dparams[0]; eos = dparams[1]; lp = row_lp ? row_lp[b] : *dlp; step = steps[0] - (step0 ? step0[b] : 0); }      // the row's own step (StepState::step0)
     else { lp = lpv; step = steps[b]; }
     const int L = max(0, min(hist_len[b], ld_hist));
     float* orow = out + (size_t)b * ldo;
@@ -55,7 +56,7 @@ int launch_logits_process(const float* logits, int ld, int B, const int32_t* hea
     const int lds = seen_bytes(V, Tv, Sv);
     if (lds > 32768) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(LOGITS_THREADS), lds, s, logits, ld, heads, V, Tv, Sv, hist, ld_hist, hist_len, steps, eos, lp,
-                       nullptr, nullptr, out, ldo, lds / 4, ct, nullptr);
+                       nullptr, nullptr, out, ldo, lds / 4, ct, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }
 
@@ -65,6 +66,6 @@ int launch_step_logits_process(const float* logits, const StepState& st, int B, 
     const int NV = V + 1 + Tv + Sv, lds = seen_bytes(V, Tv, Sv);
     if (lds > 32768) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(LOGITS_THREADS), lds, s, logits, NV, st.heads, V, Tv, Sv, st.out_ids, 0, st.out_len, st.step, -1,
-                       LogitsParams{1.f, 0, 0}, st.params, dlp, out, NV, lds / 4, ct, st.step0);
+                       LogitsParams{1.f, 0, 0}, st.params, dlp, out, NV, lds / 4, ct, st.step0, st.row_lp);
     return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP;
 }

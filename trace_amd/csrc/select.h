@@ -1,5 +1,5 @@
-// select_next_kernel, the token selection of a decode step, as a template two translation units instantiate: select.hip the plain forms, constrain.hip
-// the forms with the stop match of constrain.h (STOP).  One workgroup per sequence.
+// select_next_kernel, the token selection of a decode step, as a template three translation units instantiate: select.hip the plain forms, constrain.hip
+// the forms with the stop match of constrain.h (STOP), select_rows.hip the per-row form with and without it.  One workgroup per sequence.
 #pragma once
 #include "common.h"
 #include "constrain.h"
@@ -16,7 +16,11 @@ namespace {
 // from the masked logits in `logits` [B, V+1+Tv+Sv] (head_logits_kernel's rows, or logits_process_kernel's) under the device-resident params
 // *sp, with the step counter and the row index as the Philox counter.  SELECT_ROW: the arg-max over the row's head range [lo, hi) of `logits`
 // (logits_process_kernel's rows), the lowest id among equal maxima as the tile partials have it; a range that is -inf throughout gives lo.
-// Forced ids, EOS, record_feed and the head switch are the same code in all three.
+// SELECT_PER_ROW: the generation parameters are the row's own (trace_decode_set_row_params) — st.row_sp[b].temperature > 0: SELECT_SAMPLE's draw
+// under st.row_sp[b] (its params, its seed; the same counter); otherwise SELECT_ROW's arg-max — and st.row_max_new[b] stands in every max_new guard
+// (the record, the advance of pos, the forced-id read, the stop match's length) while params[0] stays the stride of out_ids / forced: a row that has
+// recorded its own max_new ids is stepped on as a row past max_new is after an admission.  An instantiation of its own: the other three compile as before.
+// Forced ids, EOS, record_feed and the head switch are the same code in all four.
 // STOP: the stop rule of constrain.h over the table *ct.  Once thread 0 has recorded the token and the workgroup has met at the barrier below, thread i
 // compares stop sequence i with the tail of out_ids[b] (stop_match_row) and the workgroup's OR sets done[b] — before the kernel ends, so the next
 // step's selection sees it in stream order.  Only a row that recorded in this step is matched.  Without STOP nothing of it is compiled.
@@ -47,14 +51,23 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
     }
     float v = -INFINITY;
     int idx = 0x7fffffff;
-    if constexpr (MODE == SELECT_SAMPLE) {
+    bool sampled = MODE == SELECT_SAMPLE;                     // SELECT_PER_ROW: the row's own temperature decides — one workgroup is one row, so the branch is uniform
+    int own_max = max_new;                                    // the bound of every max_new guard below; max_new itself stays the stride of out_ids / forced
+    if constexpr (MODE == SELECT_PER_ROW) { sampled = st.row_sp[b].temperature > 0.f; own_max = st.row_max_new[b]; }
+    if constexpr (MODE == SELECT_SAMPLE || MODE == SELECT_PER_ROW) {
         __shared__ SampleLds L;
-        int lo, hi;
-        head_bounds(st.heads[b], V, Tv, Sv, lo, hi);
-        idx = lo + sample_row(logits + (size_t)b * (V + 1 + Tv + Sv) + lo, hi - lo, *sp, (uint32_t)local,
-                               (uint32_t)(st.row_id ? st.row_id[b] : b), L);      // (a row keeps the index it had at trace_decode_begin: trace_decode_retire)
-    } else {
-    if constexpr (MODE == SELECT_ROW) {
+        if (sampled) {
+            int lo, hi;
+            head_bounds(st.heads[b], V, Tv, Sv, lo, hi);
+            const SampleParams* rp = sp;
+            if constexpr (MODE == SELECT_PER_ROW) rp = st.row_sp + b;            // ITS params and ITS seed; the counter stays (local, 0, row_id[b], 0)
+            [[clang::always_inline]] idx = lo + sample_row(logits + (size_t)b * (V + 1 + Tv + Sv) + lo, hi - lo, *rp, (uint32_t)local,
+                                   (uint32_t)(st.row_id ? st.row_id[b] : b), L);      // (a row keeps the index it had at trace_decode_begin: trace_decode_retire)
+        }
+    }
+    if constexpr (MODE != SELECT_SAMPLE) {
+    if (!sampled) {
+    if constexpr (MODE == SELECT_ROW || MODE == SELECT_PER_ROW) {
         int lo, hi;
         head_bounds(st.heads[b], V, Tv, Sv, lo, hi);
         const float* row = logits + (size_t)b * (V + 1 + Tv + Sv);
@@ -84,21 +97,22 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
     if (lane == 0) { sv[wid] = v; si[wid] = idx; }
     __syncthreads();
     }
+    }
     if (tid == 0) {
-        if constexpr (MODE != SELECT_SAMPLE)
+        if (!sampled)
         for (int w = 1; w < 4; ++w)
             if (sv[w] > v || (sv[w] == v && si[w] < idx)) { v = sv[w]; idx = si[w]; }
         int tok = idx;
-        if (advance && local < max_new) st.pos[b] += 1;     // (the host bounds the step count too: engine.hip trace_decode_steps)
+        if (advance && local < own_max) st.pos[b] += 1;     // (the host bounds the step count too: engine.hip trace_decode_steps)
         int feed = tok;
-        if (local < max_new) {
+        if (local < own_max) {
             const int f = st.forced[(size_t)b * max_new + local];
             if (f >= 0) feed = f;
         }
         if (record_feed) tok = feed;          // host-driven sampling: the emitted token is the one fed back
         const bool was_done = st.done[b] != 0;
-        if constexpr (STOP) s_len = !was_done && local < max_new ? local + 1 : 0;
-        if (!was_done && local < max_new) {
+        if constexpr (STOP) s_len = !was_done && local < own_max ? local + 1 : 0;
+        if (!was_done && local < own_max) {
             st.out_ids[(size_t)b * max_new + local] = tok;
             st.out_len[b] = local + 1;
             if (eos >= 0 && tok == eos) st.done[b] = 1;
@@ -126,7 +140,7 @@ __global__ __launch_bounds__(256) void select_next_kernel(const float* __restric
 
 }  // namespace
 
-// the launch of one form (launch_select's argument checks come first)
+// the launch of one of the three batch-wide forms (launch_select's argument checks come first); SELECT_PER_ROW is select_rows.hip's
 template <bool STOP>
 inline int launch_select_forms(int form, const float* part_val, const int32_t* part_idx, const float* logits, const SampleParams* sp, const StepState& st,
                                const bf16_t* embed, const bf16_t* time_tab, const bf16_t* score_tab, const bf16_t* sync_row, bf16_t* xnext, int ldx, int B,

@@ -15,7 +15,7 @@ from .model.encoders import TimeTower, ScoreTower
 from .prefix import APPEND_GROUP_MAX, SHARE_PREFIX_MIN_BATCH, group_by_length, shared_prefix_len, split_questions
 from .admit import ADMIT_FRACTION, QueueBook, admit_plan
 from .retire import RETIRE_FRACTION, RetireBook, retire_plan
-from .sampling import Constraints, LogitsParams, SamplingParams, argmax_rows, check_constraints, ends_stopped, sample_rows_host
+from .sampling import Constraints, LogitsParams, RowParams, SamplingParams, argmax_rows, check_constraints, ends_stopped, sample_rows_host
 from . import scoring
 
 __all__ = ["TraceEngine", "SamplingParams", "ops"]
@@ -540,10 +540,19 @@ class TraceEngine:
 
     # ---- decode --------------------------------------------------------------------------------
     def decode_begin(self, slots: Sequence[int], heads: Sequence[int], max_new: int, eos: int = -1,
-                     forced: Optional[Sequence[Sequence[int]]] = None, want_logits: bool = False, shared_prefix=None):
+                     forced: Optional[Sequence[Sequence[int]]] = None, want_logits: bool = False, shared_prefix=None,
+                     row_params: Optional[Sequence[RowParams]] = None):
         """shared_prefix: (slot, rows) as encode_prefill returns it — every slot of the batch holds the same first `rows` rows, `slot` among them:
-        the decode attention reads whole 32-position blocks of them from that slot alone (trace_decode_set_shared_prefix)."""
+        the decode attention reads whole 32-position blocks of them from that slot alone (trace_decode_set_shared_prefix).
+        row_params: one RowParams per row (trace_decode_set_row_params) — every row samples (or not) under its own params and seed, runs its own
+        logits processors and stops recording at its own max_new_tokens; set_sampling / set_logits_params are ignored by such a batch, and rows join
+        it through admit_rows_ex only.  None: the batch-wide settings, as ever."""
         B = len(slots)
+        rp = None
+        if row_params is not None:
+            if len(row_params) != B:
+                raise ValueError("one RowParams per row of the batch")
+            rp = row_params_c(list(row_params), max_new)
         if shared_prefix is not None:
             _lib.check(self.lib.trace_decode_set_shared_prefix(self.h, int(shared_prefix[0]), int(shared_prefix[1]) & ~31))
         self._B, self._max_new = B, max_new
@@ -557,7 +566,13 @@ class TraceEngine:
                 flat += row + [0] * (max_new - len(row))
             f = _i32(flat)
         lg = torch.empty((B, self.cfg.total_vocab), dtype=torch.float32, device=self.device) if want_logits else None
-        _lib.check(self.lib.trace_decode_begin(self.h, _i32(slots), B, _i32(heads), max_new, eos, f, _ptr(lg), _stream()))
+        if rp is not None:
+            _lib.check(self.lib.trace_decode_set_row_params(self.h, rp, B))
+        try:
+            _lib.check(self.lib.trace_decode_begin(self.h, _i32(slots), B, _i32(heads), max_new, eos, f, _ptr(lg), _stream()))
+        finally:
+            if rp is not None:               # (a begin that failed before it looked at the request must not leave it to the next one)
+                self.lib.trace_decode_set_row_params(self.h, None, 0)
         return lg
 
     def decode_steps(self, n: int, use_graph: bool = True, want_logits: bool = False):
@@ -589,11 +604,23 @@ class TraceEngine:
         min_new_tokens, begin_suppress_tokens, the stop match and the sampler's counter are those of a row begun at its step 0.  row_ids: the Philox
         row index of each new row (default: the position it lands at), so a sampled row can draw what that row of a batch begun together draws.
         self._rows names the new rows by the next unused original indices.  Retire first, then admit.  Not in host-select mode, not under a shared
-        prefix, not with forced ids while processors or constraints are armed."""
+        prefix, not with forced ids while processors or constraints are armed.  Into a batch begun with row_params: admit_rows_ex."""
+        self._admit(slots, heads, row_ids, forced, None)
+
+    def admit_rows_ex(self, slots: Sequence[int], heads: Sequence[int], row_params: Sequence[RowParams], row_ids: Optional[Sequence[int]] = None,
+                      forced: Optional[Sequence[Sequence[int]]] = None):
+        """admit_rows into a batch begun with row_params (and only into such a batch: trace_decode_admit_ex): one RowParams per admitted row, written
+        beside the batch's before the rows' token 0 is selected.  Forced ids are refused only for a row whose processors are armed, or under constraints."""
+        if row_params is None:
+            raise ValueError("admit_rows_ex takes one RowParams per admitted slot (admit_rows admits into a batch begun without them)")
+        self._admit(slots, heads, row_ids, forced, row_params)
+
+    def _admit(self, slots, heads, row_ids, forced, row_params):
         slots, heads = [int(s) for s in slots], [int(h) for h in heads]
         n, mn = len(slots), self._max_new
-        if len(heads) != n or (row_ids is not None and len(row_ids) != n) or (forced is not None and len(forced) != n):
-            raise ValueError("one head, row index and forced row per admitted slot")
+        if len(heads) != n or (row_ids is not None and len(row_ids) != n) or (forced is not None and len(forced) != n) or \
+                (row_params is not None and len(row_params) != n):
+            raise ValueError("one head, row index, forced row and RowParams per admitted slot")
         rid = [int(r) for r in row_ids] if row_ids is not None else list(range(self._B, self._B + n))
         f = None
         if forced is not None:
@@ -602,7 +629,10 @@ class TraceEngine:
                 row = list(row)[:mn]
                 flat += row + [0] * (mn - len(row))
             f = _i32(flat)
-        _lib.check(self.lib.trace_decode_admit(self.h, _i32(slots), n, _i32(heads), _i32(rid), f, _stream()))
+        if row_params is None:
+            _lib.check(self.lib.trace_decode_admit(self.h, _i32(slots), n, _i32(heads), _i32(rid), f, _stream()))
+        else:
+            _lib.check(self.lib.trace_decode_admit_ex(self.h, _i32(slots), n, _i32(heads), _i32(rid), f, row_params_c(list(row_params), mn), _stream()))
         nxt = 1 + max([max(h) for h in self._rows_history if h] + [-1])
         self._rows = self._rows + list(range(nxt, nxt + n))
         self._B += n
@@ -816,8 +846,11 @@ class TraceEngine:
 
     def decode(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
                forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-               logits: Optional[LogitsParams] = None, shared_prefix=None, constraints: Optional[Constraints] = None, retire_finished: bool = False):
+               logits: Optional[LogitsParams] = None, shared_prefix=None, constraints: Optional[Constraints] = None, retire_finished: bool = False,
+               row_params: Optional[Sequence[RowParams]] = None):
         """Stage 2 of generate(): the decode loop over prefilled KV slots, on the current stream -> (ids per sequence, final heads).
+        row_params: one RowParams per row (decode_begin) whose None fields fall back to sampling= / logits= / max_new_tokens=; every row then decodes
+        under its own params to its own bound.  Forced ids are refused only for a row whose processors are armed, or under constraints.
         retire_finished: every retire_chunk steps the rows whose recorded ids end in EOS or a stop sequence leave the running batch (retire_rows, when
         retire.retire_plan says it pays), so the later steps attend and project the live rows only; the result has every row, in its original order,
         shaped as with the flag off.  A row's ids, length and log-probabilities are a function of its own logits: on a decoder whose logits do not
@@ -835,6 +868,11 @@ class TraceEngine:
         token under the model's own (unwarped) distribution, computed inside the decode step (trace_decode_set_logprobs)."""
         armed = logits is not None and not logits.off
         bound = constraints is not None and not constraints.off
+        if row_params is not None:
+            if len(row_params) != len(slots):
+                raise ValueError("one RowParams per slot")
+            row_params = [(r if r is not None else RowParams()).over(sampling, logits, max_new_tokens).check(max_new_tokens) for r in row_params]
+            sampling, logits, armed = None, None, False               # every row carries its own from here on
         if (armed or bound) and forced is not None:
             raise ValueError("logits processors and constraints act on the ids a row has recorded; under forced ids those are not the fed ones "
                              "(forced= with logits= / constraints=)")
@@ -858,7 +896,7 @@ class TraceEngine:
             if bound:
                 self.set_constraints(constraints)
             return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs, shared_prefix, constraints if bound else None,
-                                retire_finished)
+                                retire_finished, row_params)
         finally:
             if bound:
                 self.set_constraints(None)
@@ -933,8 +971,11 @@ class TraceEngine:
         finally:
             self.host_mode(False)
 
-    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False, shared_prefix=None, constraints=None, retire_finished=False):
-        self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, shared_prefix=shared_prefix)
+    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False, shared_prefix=None, constraints=None, retire_finished=False,
+                row_params=None):
+        self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, shared_prefix=shared_prefix, row_params=row_params)
+        if row_params is not None:
+            return self._decode_rows(row_params, eos, use_graph, logprobs, constraints, retire_finished)
         read_lps = lambda ids: self.decode_read_logprobs([len(x) for x in ids]) if logprobs else None
         book = RetireBook(len(slots), logprobs) if retire_finished else None
         if max_new_tokens > 1:
@@ -959,6 +1000,31 @@ class TraceEngine:
             return book.result(ids, hd, read_lps(ids))
         return (ids, hd, read_lps(ids)) if logprobs else (ids, hd)
 
+    def _decode_rows(self, row_params, eos, use_graph, logprobs, constraints, retire_finished):
+        """_decode's loop for a batch begun with row_params (resolved: every max_new_tokens set): a row is finished at its own bound too, and the loop
+        runs until the longest live row has had its steps"""
+        bounds = [int(r.max_new_tokens) for r in row_params]                      # by original row
+        read_lps = lambda ids: self.decode_read_logprobs([len(x) for x in ids]) if logprobs else None
+        book = RetireBook(len(bounds), logprobs) if retire_finished else None
+        chunk = max(1, int(self.retire_chunk)) if retire_finished else 32
+        done = 0
+        while True:
+            ids, hd = self.decode_read()
+            finished = [len(x) >= bounds[r] or ends_stopped(x, eos, constraints) for r, x in zip(self._rows, ids)]
+            left = max([bounds[r] - 1 - done for r, f in zip(self._rows, finished) if not f] + [0])
+            if left <= 0:
+                break
+            if book is not None and done and retire_plan(len(ids), finished.count(False), self.retire_fraction):
+                keep = book.keep_list(finished)
+                book.retire(keep, ids, hd, read_lps(ids))
+                self.retire_rows(keep)
+            n = min(chunk, left)
+            self.decode_steps(n, use_graph)
+            done += n
+        if book is not None:
+            return book.result(ids, hd, read_lps(ids))
+        return (ids, hd, read_lps(ids)) if logprobs else (ids, hd)
+
     def generate(self, videos: Sequence[torch.Tensor], timestamps: Sequence, input_ids: Sequence[Sequence[int]],
                  heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
                  forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
@@ -972,7 +1038,7 @@ class TraceEngine:
 
     def generate_queue(self, requests: Iterable, max_new_tokens: int, eos: int = -1, *, max_rows: Optional[int] = None,
                        sampling: Optional[SamplingParams] = None, logprobs: bool = False, logits: Optional[LogitsParams] = None,
-                       constraints: Optional[Constraints] = None, use_graph: bool = True):
+                       constraints: Optional[Constraints] = None, use_graph: bool = True, per_request: bool = False):
         """Continuous batching: requests (video, timestamps, input_ids, head[, forced ids]) flow through one running decode batch of at most
         max_rows rows (default and bound: decode_batch_max) -> one (ids, head[, logprobs]) per request, in request order.  The first max_rows
         requests are encoded, prefilled (whole prefills: no shared prefix) and begun as a batch; every retire_chunk steps the recorded ids are read,
@@ -985,7 +1051,11 @@ class TraceEngine:
         A row's ids, length and log-probabilities are a function of its own logits, its own step count and (sampled) its Philox row index, which is its
         request index counted from the first request of the batch it joined: on a decoder whose logits do not depend on rounding they are those of
         generate() of the request alone, exactly; on real weights a row sees the rounding of the batch sizes it is decoded in.
-        max_new_tokens, eos, sampling, logits and constraints hold for every request.  ValueError, before any work, for sampling parameters outside
+        max_new_tokens, eos, sampling, logits and constraints hold for every request, unless per_request=True: a request may then carry a sixth element,
+        a RowParams (forced ids or None in the fifth), whose None fields fall back to the call's sampling / logits / max_new_tokens — the latter stays the
+        bound of every row's and the stride; a request's own seed applies to its row, at the same Philox row index; a row leaves at its own bound and
+        the chunk is as long as the longest remainder of a live row.  eos, constraints and logprobs stay the call's.  With per_request=False a
+        six-element request is a ValueError, found as the forced-ids one below is.  ValueError, before any work, for sampling parameters outside
         the device sampler's domain.  ValueError for a request that carries forced ids while logits= / constraints= are armed: before any work when
         `requests` is a list or a tuple (every request is looked at first); an iterator is looked at as it is pulled, so there the error comes when
         the bad request is reached — the requests before it have been decoded by then, their results are lost with the call, and the batch that
@@ -1001,21 +1071,25 @@ class TraceEngine:
                 i = j
             return slots
 
-        return self._queue(requests, prefill_into, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph)
+        return self._queue(requests, prefill_into, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph, per_request)
 
     def decode_queue(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, *, max_rows: Optional[int] = None,
                      forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
-                     logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None, use_graph: bool = True):
+                     logits: Optional[LogitsParams] = None, constraints: Optional[Constraints] = None, use_graph: bool = True,
+                     row_params: Optional[Sequence[Optional[RowParams]]] = None):
         """generate_queue's decode side alone, over KV slots that are prefilled already (what decode() is to generate()): request r decodes slot
         slots[r] from head heads[r]; at most max_rows of them run together -> one (ids, head[, logprobs]) per slot, in the order given.  No slot
-        is recycled: every request keeps its own."""
+        is recycled: every request keeps its own.  row_params: one RowParams (or None) per slot = generate_queue(per_request=True)."""
         slots = [int(s) for s in slots]
-        if len(set(slots)) != len(slots) or len(heads) != len(slots) or (forced is not None and len(forced) != len(slots)):
-            raise ValueError("one head (and forced row) per slot, every slot once")
-        reqs = [(None, None, s, int(h), None if forced is None else forced[r]) for r, (s, h) in enumerate(zip(slots, heads))]
-        return self._queue(reqs, lambda _, rs: [r[2] for r in rs], max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph)
+        if len(set(slots)) != len(slots) or len(heads) != len(slots) or (forced is not None and len(forced) != len(slots)) or \
+                (row_params is not None and len(row_params) != len(slots)):
+            raise ValueError("one head (forced row, RowParams) per slot, every slot once")
+        reqs = [(None, None, s, int(h), None if forced is None else forced[r]) + (() if row_params is None else (row_params[r],))
+                for r, (s, h) in enumerate(zip(slots, heads))]
+        return self._queue(reqs, lambda _, rs: [r[2] for r in rs], max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph,
+                           row_params is not None)
 
-    def _queue(self, requests, place, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph):
+    def _queue(self, requests, place, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph, per_request=False):
         """the one loop of generate_queue / decode_queue.  place(slots the book hands out, requests) -> the KV slots the rows decode from, prefilled"""
         armed = logits is not None and not logits.off
         bound = constraints is not None and not constraints.off
@@ -1026,19 +1100,28 @@ class TraceEngine:
             check_constraints(constraints.stop_sequences, constraints.bad_words_ids, constraints.suppress_tokens, constraints.begin_suppress_tokens,
                               self.cfg.total_vocab)
 
+        mn = int(max_new_tokens)
+
         def checked(req):
             req = tuple(req)
-            if len(req) not in (4, 5):
-                raise ValueError("a request is (video, timestamps, input_ids, head[, forced ids])")
-            if (armed or bound) and len(req) == 5 and req[4] is not None:
+            if len(req) == 6 and not per_request:
+                raise ValueError("a request with a sixth element (RowParams) needs per_request=True")
+            if len(req) not in ((4, 5, 6) if per_request else (4, 5)):
+                raise ValueError("a request is (video, timestamps, input_ids, head[, forced ids[, RowParams]])" if per_request else
+                                 "a request is (video, timestamps, input_ids, head[, forced ids])")
+            req = req + (None,) * (6 - len(req))
+            own = None
+            if per_request:                               # the row's own params, every None field from the call's; checked here, before any work on it
+                own = (req[5] if req[5] is not None else RowParams()).over(sampling, logits, mn).check(mn)
+            if ((own.armed if per_request else armed) or bound) and req[4] is not None:
                 raise ValueError("logits processors and constraints act on the ids a row has recorded; under forced ids those are not the fed ones "
                                  "(a forced request with logits= / constraints=)")
-            return req if len(req) == 5 else req + (None,)
+            return req[:5] + (own,)
 
         if isinstance(requests, (list, tuple)):
-            requests = [checked(r) for r in requests]
+            for r in requests:                            # every request is looked at before any work; waiting() checks again as it pulls them
+                checked(r)
         cap = max(1, min(int(max_rows) if max_rows else self.decode_batch_max, self.decode_batch_max, self.max_batch))
-        mn = int(max_new_tokens)
         source, buf = iter(requests), []
 
         def waiting(want: int) -> int:
@@ -1057,6 +1140,10 @@ class TraceEngine:
 
         book = QueueBook(range(cap), logprobs)
         read_lps = lambda ids: self.decode_read_logprobs([len(x) for x in ids]) if logprobs else None
+        params_of = lambda reqs: [r[5] for r in reqs] if per_request else None
+        limits_of = lambda reqs: [int(r[5].max_new_tokens) if per_request else mn for r in reqs]      # every row's own bound
+        if per_request:
+            on_dev = armed = False                     # a per-row batch ignores the batch-wide sampling and logits params: nothing to set or take down
         if on_dev:
             self.set_sampling(sampling)
         if logprobs:
@@ -1070,14 +1157,15 @@ class TraceEngine:
                 reqs = [buf.pop(0) for _ in range(min(cap, len(buf)))]
                 base = book.requests                   # the batch's first request: Philox row indices count from it, as decode_begin's do
                 slots = place(book.admit(len(reqs)), reqs)
-                self.decode_begin(slots, [int(r[3]) for r in reqs], mn, eos, forced_of(reqs))
+                self.decode_begin(slots, [int(r[3]) for r in reqs], mn, eos, forced_of(reqs), row_params=params_of(reqs))
                 own = [0] * len(reqs)                  # steps of its own every live row has taken
+                lim = limits_of(reqs)                  # ids it may record
                 while True:
                     # a boundary: look at the recorded ids, retire, admit — and look again at what an admission brought (a row whose token 0 ends it
                     # leaves before it has ridden a chunk), until nothing more is admitted
                     while True:
                         ids, hd = self.decode_read()
-                        finished = [len(x) >= mn or ends_stopped(x, eos, constraints if bound else None) for x in ids]
+                        finished = [len(x) >= m or ends_stopped(x, eos, constraints if bound else None) for x, m in zip(ids, lim)]
                         live = finished.count(False)
                         if live == 0:
                             break
@@ -1085,7 +1173,7 @@ class TraceEngine:
                             keep = book.keep_list(finished)
                             book.retire(keep, ids, hd, read_lps(ids))
                             self.retire_rows(keep)
-                            own = [own[k] for k in keep]
+                            own, lim = [own[k] for k in keep], [lim[k] for k in keep]
                         room = min(cap - len(own), len(book.free))
                         k = admit_plan(len(own), cap, waiting(room), len(book.free), self.admit_fraction) if room > 0 else 0
                         if not k:
@@ -1093,12 +1181,13 @@ class TraceEngine:
                         reqs = [buf.pop(0) for _ in range(k)]
                         first = book.requests
                         slots = place(book.admit(k), reqs)
-                        self.admit_rows(slots, [int(r[3]) for r in reqs], row_ids=list(range(first - base, first - base + k)), forced=forced_of(reqs))
+                        self._admit(slots, [int(r[3]) for r in reqs], list(range(first - base, first - base + k)), forced_of(reqs), params_of(reqs))
                         own += [0] * k
+                        lim += limits_of(reqs)
                     if live == 0:                     # the batch ended: whatever waits begins the next one
                         book.finish(ids, hd, read_lps(ids))
                         break
-                    n = min(max(1, int(self.retire_chunk)), mn - 1 - min(own))
+                    n = min(max(1, int(self.retire_chunk)), max(m - 1 - s for m, s in zip(lim, own)))      # the largest remainder of a row
                     if n <= 0:
                         raise RuntimeError("generate_queue: a row has taken max_new_tokens - 1 steps of its own and is not finished")
                     self.decode_steps(n, use_graph)
@@ -1282,6 +1371,19 @@ def sampling_c(sampling: SamplingParams):
     """trace_sampling for the C ABI (trace_decode_set_sampling_ex / trace_op_sample_ex)"""
     return _lib.TraceSamplingC(C.sizeof(_lib.TraceSamplingC), float(sampling.temperature), int(sampling.top_k), float(sampling.top_p), int(sampling.seed),
                                float(sampling.min_p), float(sampling.typical_p), float(sampling.epsilon_cutoff), float(sampling.eta_cutoff))
+
+
+def row_params_c(rows: Sequence[RowParams], max_new: int):
+    """trace_row_params [len(rows)] for the C ABI (trace_decode_set_row_params / trace_decode_admit_ex), every row checked (RowParams.check) first;
+    a None max_new_tokens is the batch's"""
+    arr = (_lib.TraceRowParamsC * len(rows))()
+    for i, r in enumerate(rows):
+        r = (r if r is not None else RowParams()).check(max_new)
+        sp = r.sampling if r.sampling is not None and not r.sampling.greedy else SamplingParams(temperature=0.0)
+        lp = r.logits if r.logits is not None else LogitsParams()
+        arr[i] = _lib.TraceRowParamsC(C.sizeof(_lib.TraceRowParamsC), sampling_c(sp), float(lp.repetition_penalty), int(lp.no_repeat_ngram_size),
+                                      int(lp.min_new_tokens), int(r.max_new_tokens if r.max_new_tokens is not None else max_new))
+    return arr
 
 
 # ---- kernel-level wrappers for unit tests / microbenchmarks -------------------------------------

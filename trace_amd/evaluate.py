@@ -24,6 +24,7 @@ from . import dist as tdist
 from .constants import DEFAULT_MMODAL_TOKEN
 from .conversation import SeparatorStyle, conv_templates
 from .mm_utils import process_video, tokenizer_MMODAL_token_all
+from .sampling import RowParams
 
 
 def build_prompt_ids(question: str, tokenizer, conv_mode: str = "llama_2") -> torch.Tensor:
@@ -102,7 +103,9 @@ def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: 
     device's per-token log-probabilities; their float bits cross the ranks in the same all-gather as the ids).  continuous: the rank's items flow
     through one running decode batch of `batch_size` rows (TraceEngine.generate_queue: rows that ended leave, the next items take their KV slots)
     instead of fixed chunks; results of the same form in the same order, and the same results wherever the rounding of the batch sizes a row is
-    decoded in does not turn a greedy pick (off by default)."""
+    decoded in does not turn a greedy pick (off by default).  With continuous=True an item may carry "sampling" (SamplingParams), "logits" (LogitsParams) and
+    "max_new_tokens" of its own: their presence in any item makes every row decode under its own params (generate_queue(per_request=True)), the
+    call's sampling / logits / max_new_tokens filling what an item leaves out."""
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
     world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
     eng = model.engine
@@ -136,8 +139,14 @@ def evaluate_videos(model, tokenizer, processor, items: Sequence[dict], prompt: 
             yield vids, tss, idl, [1] * len(chunk), None
 
     if continuous:
-        requests = (prepared(items[i]) + (1,) for i in mine)        # preprocessed as the queue asks for them, one by one
-        for out, _, *lp in eng.generate_queue(requests, max_new_tokens, eos=eos, max_rows=bs, sampling=sampling, logprobs=logprobs, logits=logits):
+        # an item that carries "sampling" / "logits" / "max_new_tokens" of its own turns the queue's per-request params on: every request then brings a
+        # RowParams whose missing fields are the call's
+        own = ("sampling", "logits", "max_new_tokens")
+        per_request = any(k in it for it in items for k in own)
+        tail = (lambda it: (1, None, RowParams(it.get("sampling"), it.get("logits"), it.get("max_new_tokens")))) if per_request else (lambda it: (1,))
+        requests = (prepared(items[i]) + tail(items[i]) for i in mine)        # preprocessed as the queue asks for them, one by one
+        for out, _, *lp in eng.generate_queue(requests, max_new_tokens, eos=eos, max_rows=bs, sampling=sampling, logprobs=logprobs, logits=logits,
+                                              per_request=per_request):
             local.append(out)
             local_lp.extend(lp)
     elif pipelined and len(mine) > bs:

@@ -439,6 +439,51 @@ class LogitsParams:
         return float(self.repetition_penalty) == 1.0 and self.no_repeat_ngram_size == 0 and self.min_new_tokens == 0
 
 
+@dataclass(frozen=True)
+class RowParams:
+    """The generation parameters of ONE row of a decode batch (trace_row_params: TraceEngine.decode_begin / admit_rows_ex / decode / decode_queue
+    row_params=, the sixth element of a generate_queue(per_request=True) request).  sampling: None or temperature <= 0 = this row is greedy; its seed
+    is the row's own.  logits: None = no processors.  max_new_tokens: None = the batch's; else 1 .. the batch's — the row records, is fed forced ids
+    and is log-scored up to its own bound, while the batch's stays the stride of every result row.  A None field of a queue request falls back to the
+    call's own sampling= / logits= / max_new_tokens=."""
+    sampling: Optional[SamplingParams] = None
+    logits: Optional[LogitsParams] = None
+    max_new_tokens: Optional[int] = None
+
+    def check(self, max_new_tokens: Optional[int] = None) -> "RowParams":
+        """ValueError unless the row can run on the device: HF's own checks of the sampling warpers (check_sampling), the device sampler's domain
+        (SamplingParams.on_device) for a sampled row, the processors' domains (check_logits_params), and 1 <= max_new_tokens (<= the batch's, when
+        given).  Returns self."""
+        sp, lp, mn = self.sampling, self.logits, self.max_new_tokens
+        if sp is not None:
+            if not isinstance(sp, SamplingParams):
+                raise ValueError(f"RowParams.sampling has to be a SamplingParams or None, but is {type(sp).__name__}")
+            check_sampling(sp.temperature, sp.top_k, sp.top_p, sp.min_p, sp.typical_p, sp.epsilon_cutoff, sp.eta_cutoff)
+            if not sp.greedy and not sp.on_device:
+                raise ValueError("per-row sampling runs in the device decode loop: these sampling parameters lie outside the device sampler's domain "
+                                 f"(top_k {sp.top_k}, top_p {sp.top_p})")
+        if lp is not None:
+            if not isinstance(lp, LogitsParams):
+                raise ValueError(f"RowParams.logits has to be a LogitsParams or None, but is {type(lp).__name__}")
+            check_logits_params(lp.repetition_penalty, lp.no_repeat_ngram_size, lp.min_new_tokens)
+        if mn is not None:
+            if not isinstance(mn, (int, np.integer)) or isinstance(mn, bool) or mn < 1:
+                raise ValueError(f"`max_new_tokens` of a row has to be a positive integer, but is {mn}")
+            if max_new_tokens is not None and mn > max_new_tokens:
+                raise ValueError(f"`max_new_tokens` of a row is at most the batch's ({max_new_tokens}), but is {mn}")
+        return self
+
+    def over(self, sampling: Optional[SamplingParams], logits: Optional[LogitsParams], max_new_tokens: int) -> "RowParams":
+        """self with every None field taken from the call's own values"""
+        return RowParams(self.sampling if self.sampling is not None else sampling, self.logits if self.logits is not None else logits,
+                         self.max_new_tokens if self.max_new_tokens is not None else int(max_new_tokens))
+
+    @property
+    def armed(self) -> bool:
+        """the row's logits processors are on"""
+        return self.logits is not None and not self.logits.off
+
+
 def process_row_ref(row, hist, lo, hi, params: LogitsParams, step, eos):
     """The device's processed row (logits.h logits_process_row), bit for bit: row = one whole row of masked logits (float32 [NV]), hist = the ids
     the row has generated so far (global ids; ids outside [lo, hi) touch nothing), [lo, hi) the active head's range, step the device step, eos
