@@ -157,7 +157,7 @@ def queue_schedule(lengths, max_new, cap, chunk, retire_fraction=8, admit_fracti
 
 
 def fixed_schedule(lengths, ends_in_eos, max_new, batch, chunk, retire_fraction=8):
-    """rows x steps of TraceEngine._decode(retire_finished=True) over fixed batches of `batch` requests: a row is finished once it has recorded its EOS
+    """rows x steps of TraceEngine.decode(retire_finished=True) over fixed batches of `batch` requests: a row is finished once it has recorded its EOS
     (ends_in_eos[r]); a row that runs to max_new ids is never retired"""
     from trace_amd.retire import retire_plan
     total = 0

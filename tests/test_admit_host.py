@@ -1,5 +1,5 @@
-"""Continuous batching, host side: the admit rule, the bookkeeping of TraceEngine.generate_queue as a model that needs no engine
-(trace_amd/admit.py driven with scripted chunk read-backs), the per-row step rule restated over a shared counter (tests/admit_probes.py) with its
+"""Continuous batching, host side: the admit rule, the loop and the book of TraceEngine.generate_queue without an engine
+(trace_amd/decode_loop.py under QUEUE's rules on the scripted device of tests/decode_loop_probes.py), the per-row step rule restated over a shared counter (tests/admit_probes.py) with its
 near misses, and the interface (header, signatures).  No device."""
 import inspect
 import os
@@ -11,12 +11,12 @@ import pytest
 import admit_probes as AP
 import constraint_probes as CP
 import token_select_probes as P
-from trace_amd.admit import ADMIT_FRACTION, QueueBook, admit_plan
-from trace_amd.retire import RETIRE_FRACTION, retire_plan
-from trace_amd.sampling import ends_stopped
+from decode_loop_probes import expected, run as run_scripted, script_with_ends
+from trace_amd.admit import ADMIT_FRACTION, admit_plan
+from trace_amd.decode_loop import QUEUE, RowBook
+from trace_amd.retire import RETIRE_FRACTION
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EOS = 7
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rule
@@ -43,87 +43,10 @@ def test_admit_plan_table(cap):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the bookkeeping model
-class ScriptedDevice:
-    """What the device does to the recorded ids, on lists: request r records script[r] from its own step 0 until EOS or max_new ids; positions hold
-    requests; begin / admit append, retire keeps positions.  Every KV slot remembers the request prefilled into it."""
-
-    def __init__(self, script, max_new):
-        self.script, self.max_new = script, max_new
-        self.rows, self.own, self.slot_of = [], [], []
-        self.prefilled = {}
-        self.row_steps = 0
-
-    def admit(self, reqs, slots):
-        for r, s in zip(reqs, slots):
-            assert s not in self.slot_of, "a live row's KV slot was handed out again"
-            self.prefilled[s] = r
-        self.rows += list(reqs)
-        self.own += [1] * len(reqs)                       # begin / admit record id 0
-        self.slot_of += list(slots)
-
-    def steps(self, n):
-        self.own = [s + n for s in self.own]
-        self.row_steps += n * len(self.rows)
-
-    def read(self):
-        ids = []
-        for r, s, slot in zip(self.rows, self.own, self.slot_of):
-            assert self.prefilled[slot] == r, "the row attends another request's KV slot"
-            out = []
-            for t in self.script[r][: min(s, self.max_new)]:
-                out.append(t)
-                if t == EOS:
-                    break
-            ids.append(out)
-        heads = [100 + r for r in self.rows]
-        lps = [np.array([-(r + 1) - 0.001 * s for s in range(len(x))], np.float32) for r, x in zip(self.rows, ids)]
-        return ids, heads, lps
-
-    def retire(self, keep):
-        self.rows, self.own, self.slot_of = ([a[k] for k in keep] for a in (self.rows, self.own, self.slot_of))
-
-
 def run_queue(script, max_new, chunk, cap, logprobs=True):
-    """TraceEngine.generate_queue's loop on the scripted device"""
-    dev, book = ScriptedDevice(script, max_new), QueueBook(range(cap), logprobs)
-    todo = list(range(len(script)))
-    while todo:
-        reqs, todo = todo[:cap], todo[cap:]
-        assert book.requests == reqs[0]
-        dev.admit(reqs, book.admit(len(reqs)))
-        while True:
-            while True:                                   # a boundary: look, retire, admit, and look again at what was admitted
-                ids, hd, lps = dev.read()
-                finished = [len(x) >= max_new or ends_stopped(x, EOS) for x in ids]
-                live = finished.count(False)
-                if live == 0:
-                    break
-                if retire_plan(len(ids), live):
-                    keep = book.keep_list(finished)
-                    book.retire(keep, ids, hd, lps if logprobs else None)
-                    dev.retire(keep)
-                k = admit_plan(len(dev.rows), cap, len(todo), len(book.free))
-                assert book.rows == dev.rows and book.slots == dev.slot_of and sorted(book.free + book.slots) == list(range(cap))
-                if not k:
-                    break
-                reqs, todo = todo[:k], todo[k:]
-                dev.admit(reqs, book.admit(k))
-            if live == 0:
-                book.finish(ids, hd, lps if logprobs else None)
-                dev.retire([])
-                break
-            n = min(chunk, max_new - min(dev.own))
-            assert n > 0
-            dev.steps(n)
+    """the loop of TraceEngine.generate_queue on the scripted device: decode_loop under QUEUE's rules"""
+    book, dev = run_scripted(script, max_new, chunk, cap, QUEUE, logprobs)
     return book.results(), book, dev
-
-
-def script_with_ends(ends, max_new):
-    return [[EOS if s == e else 10 + r for s in range(max_new)] for r, e in enumerate(ends)]
-
-
-def expected(script):
-    return [row[: row.index(EOS) + 1 if EOS in row else len(row)] for row in script]
 
 
 def test_request_order_through_interleaved_retires_and_admits():
@@ -177,8 +100,8 @@ def test_nothing_ever_finishes_early():
 def test_queue_book_errors():
     for bad in ([], [1, 1], [-1, 2]):
         with pytest.raises(ValueError):
-            QueueBook(bad)
-    book = QueueBook([3, 1, 2])
+            RowBook(bad)
+    book = RowBook([3, 1, 2])
     with pytest.raises(ValueError):
         book.admit(0)
     with pytest.raises(ValueError):
@@ -195,7 +118,7 @@ def test_queue_book_errors():
     with pytest.raises(ValueError):
         book.results()                                    # rows are still live
     with pytest.raises(ValueError):
-        QueueBook([0], logprobs=True).finish([], [], None)
+        RowBook([0], logprobs=True).finish([], [], None)
     assert book.rows == [0, 1] and book.retires == 0
     book.retire([1], ids, hd)
     assert book.rows == [1] and book.slots == [2] and book.free == [1, 3]

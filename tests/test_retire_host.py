@@ -1,5 +1,6 @@
-"""Retiring finished rows from a running decode batch, host side: the retire rule, the bookkeeping of TraceEngine._decode as a model that needs no
-engine (trace_amd/retire.py driven with scripted chunk read-backs), and the interface (header, signatures).  No device."""
+"""Retiring finished rows from a running decode batch, host side: the retire rule, the loop and the book of TraceEngine.decode(retire_finished=True)
+without an engine (trace_amd/decode_loop.py under DECODE's rules on the scripted device of tests/decode_loop_probes.py), and the interface (header,
+signatures).  No device."""
 import inspect
 import os
 import re
@@ -7,11 +8,11 @@ import re
 import numpy as np
 import pytest
 
-from trace_amd.retire import RETIRE_FRACTION, RetireBook, retire_plan
-from trace_amd.sampling import ends_stopped
+from decode_loop_probes import expected, run, script_with_ends
+from trace_amd.decode_loop import DECODE, RowBook
+from trace_amd.retire import RETIRE_FRACTION, retire_plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EOS = 7
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rule
@@ -32,78 +33,17 @@ def test_retire_plan_small_batches_retire_single_rows():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the bookkeeping model
-class ScriptedDevice:
-    """What the engine's device side does to the recorded ids, on lists: row r of the script is the full id stream the row would record with
-    no EOS rule; a row records until it has recorded EOS; retire() keeps positions.  read() is decode_read + decode_read_logprobs."""
-
-    def __init__(self, script, max_new):
-        self.script, self.max_new = script, max_new
-        self.rows = list(range(len(script)))        # which script row sits at each position: what must equal RetireBook.rows
-        self.step = 1                               # decode_begin records id 0
-        self.row_steps = 0
-
-    def steps(self, n):
-        self.step += n
-        self.row_steps += n * len(self.rows)
-
-    def _ids(self, r):
-        out = []
-        for t in self.script[r][: self.step]:
-            out.append(t)
-            if t == EOS:
-                break
-        return out
-
-    def read(self):
-        ids = [self._ids(r) for r in self.rows]
-        heads = [100 + r for r in self.rows]                                          # a head that names its row
-        lps = [np.array([-(r + 1) - 0.001 * s for s in range(len(x))], np.float32) for r, x in zip(self.rows, ids)]
-        return ids, heads, lps
-
-    def retire(self, keep):
-        assert list(keep) == sorted(set(keep)) and 0 <= keep[0] and keep[-1] < len(self.rows)
-        self.rows = [self.rows[k] for k in keep]
-
-
-def run_loop(script, max_new, chunk, logprobs=True):
-    """TraceEngine._decode's loop with retire_finished=True, on the scripted device"""
-    dev, book = ScriptedDevice(script, max_new), RetireBook(len(script), logprobs)
-    done = 0
-    while done < max_new - 1:
-        n = min(chunk, max_new - 1 - done)
-        dev.steps(n)
-        done += n
-        ids, hd, lps = dev.read()
-        finished = [ends_stopped(x, EOS) for x in ids]
-        if all(finished):
-            break
-        if done < max_new - 1 and retire_plan(len(ids), finished.count(False)):
-            keep = book.keep_list(finished)
-            book.retire(keep, ids, hd, lps if logprobs else None)
-            dev.retire(keep)
-            assert book.rows == dev.rows
-    ids, hd, lps = dev.read()
-    return book.result(ids, hd, lps if logprobs else None), book, dev
-
-
-def script_with_ends(ends, max_new):
-    """row r records ids 10 + r until position ends[r], where it records EOS (None: never)"""
-    return [[EOS if s == e else 10 + r for s in range(max_new)] for r, e in enumerate(ends)]
-
-
-def expected(script):
-    out = []
-    for row in script:
-        cut = row.index(EOS) + 1 if EOS in row else len(row)
-        out.append(row[:cut])
-    return out
+def decode_retiring(script, max_new, chunk, logprobs=True):
+    """the loop of TraceEngine.decode(retire_finished=True) on the scripted device: decode_loop under DECODE's rules, the batch begun at once"""
+    book, dev = run(script, max_new, chunk, len(script), DECODE, logprobs)
+    return book.columns(), book, dev
 
 
 def test_rows_finish_in_different_chunks_and_come_back_in_order():
     max_new, chunk = 21, 4
     ends = [0, 17, 3, None, 9, 5, 20, 1, 13]          # chunk boundaries after steps 4, 8, 12, 16, 20 (ids recorded: 5, 9, 13, 17, 21)
     script = script_with_ends(ends, max_new)
-    (ids, heads, lps), book, dev = run_loop(script, max_new, chunk)
+    (ids, heads, lps), book, dev = decode_retiring(script, max_new, chunk)
     assert ids == expected(script)
     assert heads == [100 + r for r in range(len(ends))]
     for r, (x, lp) in enumerate(zip(ids, lps)):
@@ -113,14 +53,14 @@ def test_rows_finish_in_different_chunks_and_come_back_in_order():
                             [1, 3, 4, 6, 8],          # after 9 ids: row 5
                             [1, 3, 6, 8],             # after 13 ids: row 4 (ends at 9: its EOS is id 10)
                             [1, 3, 6]]                # after 17 ids: row 8; row 1 (EOS is id 18) ends inside the last chunk: no retire after the last step
-    assert book.retires == 4 and book.rows == [1, 3, 6]
+    assert book.retires == 4 and book.history[-1] == [1, 3, 6]
     assert dev.row_steps == 4 * (9 + 6 + 5 + 4 + 3) < 9 * (max_new - 1)
 
 
 def test_every_row_finishes_in_the_first_chunk():
     max_new = 21
     script = script_with_ends([0, 1, 2, 3, 4], max_new)
-    (ids, heads), book, dev = run_loop(script, max_new, 8, logprobs=False)
+    (ids, heads), book, dev = decode_retiring(script, max_new, 8, logprobs=False)
     assert ids == expected(script) and heads == [100, 101, 102, 103, 104]
     assert book.history == [[0, 1, 2, 3, 4]] and book.retires == 0 and dev.row_steps == 8 * 5
 
@@ -128,7 +68,7 @@ def test_every_row_finishes_in_the_first_chunk():
 def test_no_row_ever_finishes():
     max_new = 21
     script = script_with_ends([None] * 6, max_new)
-    (ids, heads, lps), book, dev = run_loop(script, max_new, 4)
+    (ids, heads, lps), book, dev = decode_retiring(script, max_new, 4)
     assert ids == expected(script) and all(len(x) == max_new for x in ids)
     assert book.history == [[0, 1, 2, 3, 4, 5]] and dev.row_steps == 6 * (max_new - 1)
 
@@ -139,15 +79,16 @@ def test_threshold_holds_rows_back_until_enough_have_finished():
     ends = [None] * 32
     ends[5], ends[9], ends[20], ends[21], ends[30] = 1, 6, 10, 11, 30
     script = script_with_ends(ends, max_new)
-    (ids, heads), book, _ = run_loop(script, max_new, chunk, logprobs=False)
+    (ids, heads), book, _ = decode_retiring(script, max_new, chunk, logprobs=False)
     assert ids == expected(script)
     live = [r for r in range(32) if r not in (5, 9, 20, 21)]
     # one retire of four rows at the boundary after rows 20 and 21 ended; row 30 ends later, alone: one of 28 is below 28 // 8 and it stays
-    assert book.history == [list(range(32)), live] and book.retires == 1 and 30 in book.rows
+    assert book.history == [list(range(32)), live] and book.retires == 1 and 30 in book.history[-1]
 
 
 def test_retire_book_rejects_bad_keep_lists():
-    book = RetireBook(4)
+    book = RowBook(range(4))
+    book.admit(4)
     ids, hd = [[1], [2], [3], [4]], [0, 0, 0, 0]
     for keep in ([], [2, 1], [1, 1], [0, 4], [-1, 2]):
         with pytest.raises(ValueError):
@@ -158,7 +99,9 @@ def test_retire_book_rejects_bad_keep_lists():
         book.keep_list([True, False])
     assert book.rows == [0, 1, 2, 3] and book.retires == 0
     book.retire([1, 3], ids, hd)
-    assert book.rows == [1, 3] and book.result([[2, 9], [4, 9]], [1, 2]) == ([[1], [2, 9], [3], [4, 9]], [0, 1, 0, 2])
+    assert book.rows == [1, 3]
+    book.finish([[2, 9], [4, 9]], [1, 2])
+    assert book.columns() == ([[1], [2, 9], [3], [4, 9]], [0, 1, 0, 2])
 
 
 # ---------------------------------------------------------------------------------------------------------------- the interface

@@ -1,6 +1,6 @@
 """Per-row generation parameters, on the CPU: the restatement the GPU tests compare against (tests/row_params_probes.py) is anchored to
 admit_probes.restate_origins, every scenario tells the near misses it names, and the host side — RowParams.check, the request shapes of
-generate_queue(per_request=), the trace_row_params struct, the queue's schedule with a bound per row — is checked without the library's GPU half."""
+generate_queue(per_request=), the trace_row_params struct, the queue's schedule with a bound per row, the schedule models against decode_loop — is checked without the library's GPU half."""
 import os
 import re
 
@@ -138,18 +138,13 @@ def test_row_params_check():
     assert RowParams().over(None, None, 41) == RowParams(None, None, 41) and not RowParams().armed
 
 
-class _NoDevice:
-    """TraceEngine._queue's argument checks run before anything touches the device: an object with the few attributes they read"""
-    decode_batch_max = 8
-    max_batch = 8
-
-    class cfg:
-        total_vocab = 400
-
-
 def _queue(requests, **kw):
-    from trace_amd.engine import TraceEngine
-    return TraceEngine._queue(_NoDevice(), requests, None, 41, -1, 8, kw.pop("sampling", None), False, kw.pop("logits", None), None, True, **kw)
+    """the request checks of generate_queue / decode_queue (max_new_tokens 41, a vocabulary of 400) on requests of which one is bad: a list or a tuple
+    has to fail at the call itself, before anything is pulled; an iterator passes the call and fails when the bad request is pulled"""
+    from trace_amd.decode_loop import checked_requests
+    pulled = checked_requests(requests, 41, 400, kw.pop("sampling", None), kw.pop("logits", None), None, **kw)
+    assert not isinstance(requests, (list, tuple)), "a list with a bad request passed the call"
+    return list(pulled)
 
 
 def test_per_request_request_shapes():
@@ -168,6 +163,19 @@ def test_per_request_request_shapes():
         _queue([(None, None, [1], 0, [5] * 41, RowParams(logits=LogitsParams(1.3)))], per_request=True)
     with pytest.raises(ValueError, match="forced"):                            # ... or armed through the call's fallback
         _queue([(None, None, [1], 0, [5] * 41, RowParams())], per_request=True, logits=LogitsParams(1.3))
+
+
+def test_a_list_is_checked_whole_before_any_work_and_an_iterator_as_it_is_pulled():
+    from trace_amd.decode_loop import checked_requests
+    good, bad = (None, None, [1], 0), (None, None, [1], 0, None, RowParams(max_new_tokens=3))
+    for seq in ([good, good, bad], (good, good, bad)):
+        with pytest.raises(ValueError, match="per_request=True"):
+            checked_requests(seq, 41, 400)                                      # the bad request is the last one; nothing has been pulled
+    pulled = checked_requests(iter([good, good, bad]), 41, 400)                # an iterator: the call itself looks at nothing
+    assert next(pulled) == good + (None, None) and next(pulled) == good + (None, None)
+    with pytest.raises(ValueError, match="per_request=True"):
+        next(pulled)
+    assert list(checked_requests([good, good], 41, 400)) == [good + (None, None)] * 2
 
 
 def test_row_params_struct_matches_header():
@@ -198,3 +206,22 @@ def test_queue_schedule_with_a_bound_per_row(world):
     assert row_steps < AP.queue_schedule(uniform, mn, 8, CHUNK)[0] and max(sizes) <= 8 and admits >= 2 and retires >= 2 and begun >= 1
     # every request gets the steps it needs: rows x steps covers the ids recorded after every row's token 0
     assert row_steps >= sum(n - 1 for n in lengths)
+
+
+def test_the_schedule_models_are_the_loop_that_ships(world):
+    """the schedules the GPU tests take as oracles (restated from lengths alone) against decode_loop itself on the scripted device"""
+    from decode_loop_probes import run, script_with_ends
+    from trace_amd.decode_loop import DECODE, QUEUE
+    mn, ends = world[4], AP.QUEUE_ENDS
+    script = script_with_ends(ends, mn)
+    shape = lambda book, dev: (dev.row_steps, dev.sizes, dev.admits, dev.retires, dev.begun)
+    uniform = [mn if e is None else e + 1 for e in ends]
+    book, dev = run(script, mn, CHUNK, 8, QUEUE, logprobs=False)
+    assert shape(book, dev) == AP.queue_schedule(uniform, mn, 8, CHUNK) and (book.admits, book.retires) == (dev.admits, dev.retires)
+    bounds = [RP.queue_params(i, mn).max_new_tokens for i in range(24)]
+    lengths = [min(b, n) for b, n in zip(bounds, uniform)]
+    book, dev = run(script, mn, CHUNK, 8, QUEUE, logprobs=False, bounds=bounds)
+    assert shape(book, dev) == RP.queue_schedule(lengths, bounds, 8, CHUNK)
+    assert [len(o[0]) for o in book.results()] == lengths
+    fixed = sum(run(script[i:i + 8], mn, CHUNK, 8, DECODE, logprobs=False)[1].row_steps for i in range(0, 24, 8))
+    assert fixed == AP.fixed_schedule(uniform, [e is not None for e in ends], mn, 8, CHUNK)

@@ -13,8 +13,9 @@ from . import _lib
 from .config import TraceConfig
 from .model.encoders import TimeTower, ScoreTower
 from .prefix import APPEND_GROUP_MAX, SHARE_PREFIX_MIN_BATCH, group_by_length, shared_prefix_len, split_questions
-from .admit import ADMIT_FRACTION, QueueBook, admit_plan
-from .retire import RETIRE_FRACTION, RetireBook, retire_plan
+from .admit import ADMIT_FRACTION
+from .decode_loop import DECODE, DECODE_ROWS, QUEUE, Device, RowBook, checked_requests, decode_loop, flat_forced
+from .retire import RETIRE_FRACTION
 from .sampling import Constraints, LogitsParams, RowParams, SamplingParams, argmax_rows, check_constraints, ends_stopped, sample_rows_host
 from . import scoring
 
@@ -558,13 +559,7 @@ class TraceEngine:
         self._B, self._max_new = B, max_new
         self._rows = list(range(B))
         self._rows_history = [list(self._rows)]
-        f = None
-        if forced is not None:
-            flat = []
-            for row in forced:
-                row = list(row)[:max_new]
-                flat += row + [0] * (max_new - len(row))
-            f = _i32(flat)
+        f = None if forced is None else _i32(flat_forced(forced, max_new))
         lg = torch.empty((B, self.cfg.total_vocab), dtype=torch.float32, device=self.device) if want_logits else None
         if rp is not None:
             _lib.check(self.lib.trace_decode_set_row_params(self.h, rp, B))
@@ -622,13 +617,7 @@ class TraceEngine:
                 (row_params is not None and len(row_params) != n):
             raise ValueError("one head, row index, forced row and RowParams per admitted slot")
         rid = [int(r) for r in row_ids] if row_ids is not None else list(range(self._B, self._B + n))
-        f = None
-        if forced is not None:
-            flat = []
-            for row in forced:
-                row = list(row)[:mn]
-                flat += row + [0] * (mn - len(row))
-            f = _i32(flat)
+        f = None if forced is None else _i32(flat_forced(forced, mn))
         if row_params is None:
             _lib.check(self.lib.trace_decode_admit(self.h, _i32(slots), n, _i32(heads), _i32(rid), f, _stream()))
         else:
@@ -885,7 +874,22 @@ class TraceEngine:
                                  "domain and run one host-selected step at a time")
             return self.decode_stepwise(slots, heads, max_new_tokens, eos, forced, sampling, logprobs, logits, shared_prefix=shared_prefix,
                                         constraints=constraints)
+        slots = list(slots)
+        if len(heads) != len(slots) or (forced is not None and len(forced) != len(slots)):
+            raise ValueError("one head (and forced row) per slot")
+        reqs = [(None, None, s, h, None if forced is None else forced[r], None if row_params is None else row_params[r])
+                for r, (s, h) in enumerate(zip(slots, heads))]
+        with self._modes(sampling, logprobs, logits, constraints):
+            return self._loop(iter(reqs), lambda _, rs: [r[2] for r in rs], DECODE if row_params is None else DECODE_ROWS, len(slots), max_new_tokens, eos,
+                              logprobs, constraints, use_graph, retire_finished, shared_prefix).columns()
+
+    @contextlib.contextmanager
+    def _modes(self, sampling, logprobs, logits, constraints):
+        """the modes of the decode batches begun inside: device sampling, log-probabilities, logits processors and constraints, each set only when
+        it is on and taken down, in reverse order, whatever happens inside"""
         on_dev = sampling is not None and not sampling.greedy
+        armed = logits is not None and not logits.off
+        bound = constraints is not None and not constraints.off
         if on_dev:
             self.set_sampling(sampling)
         if logprobs:
@@ -895,8 +899,7 @@ class TraceEngine:
         try:
             if bound:
                 self.set_constraints(constraints)
-            return self._decode(slots, heads, max_new_tokens, eos, use_graph, forced, logprobs, shared_prefix, constraints if bound else None,
-                                retire_finished, row_params)
+            yield
         finally:
             if bound:
                 self.set_constraints(None)
@@ -906,6 +909,17 @@ class TraceEngine:
                 self.set_logprobs(False)
             if on_dev:
                 self.set_sampling(None)
+
+    def _loop(self, requests, place, rules, cap, max_new_tokens, eos, logprobs, constraints, use_graph, retiring, shared_prefix=None) -> RowBook:
+        """decode_loop.decode_loop on this engine's device primitives -> the book that holds every request's result"""
+        mn = int(max_new_tokens)
+        dev = Device(begin=lambda slots, heads, forced, rp: self.decode_begin(slots, heads, mn, eos, forced, shared_prefix=shared_prefix, row_params=rp),
+                     admit=self._admit, steps=lambda n: self.decode_steps(n, use_graph), retire=self.retire_rows, read=self.decode_read,
+                     read_logprobs=self.decode_read_logprobs)
+        bound = constraints is not None and not constraints.off
+        return decode_loop(dev, requests, place, RowBook(range(cap), logprobs), rules, cap=cap, max_new=mn, eos=eos,
+                           constraints=constraints if bound else None, chunk=self.retire_chunk, retiring=retiring, retire_fraction=self.retire_fraction,
+                           admit_fraction=self.admit_fraction)
 
     def decode_stepwise(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1,
                         forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
@@ -971,60 +985,6 @@ class TraceEngine:
         finally:
             self.host_mode(False)
 
-    def _decode(self, slots, heads, max_new_tokens, eos, use_graph, forced, logprobs=False, shared_prefix=None, constraints=None, retire_finished=False,
-                row_params=None):
-        self.decode_begin(list(slots), heads, max_new_tokens, eos, forced, shared_prefix=shared_prefix, row_params=row_params)
-        if row_params is not None:
-            return self._decode_rows(row_params, eos, use_graph, logprobs, constraints, retire_finished)
-        read_lps = lambda ids: self.decode_read_logprobs([len(x) for x in ids]) if logprobs else None
-        book = RetireBook(len(slots), logprobs) if retire_finished else None
-        if max_new_tokens > 1:
-            if eos < 0 and not (constraints is not None and constraints.stop_sequences):
-                self.decode_steps(max_new_tokens - 1, use_graph)        # (no row can finish: nothing to look at between the steps, nothing to retire)
-            else:
-                done, chunk = 0, max(1, int(self.retire_chunk)) if retire_finished else 32
-                while done < max_new_tokens - 1:
-                    n = min(chunk, max_new_tokens - 1 - done)
-                    self.decode_steps(n, use_graph)
-                    done += n
-                    ids, hd = self.decode_read()
-                    finished = [ends_stopped(x, eos, constraints) for x in ids]
-                    if all(finished):
-                        break
-                    if book is not None and done < max_new_tokens - 1 and retire_plan(len(ids), finished.count(False), self.retire_fraction):
-                        keep = book.keep_list(finished)
-                        book.retire(keep, ids, hd, read_lps(ids))
-                        self.retire_rows(keep)
-        ids, hd = self.decode_read()
-        if book is not None:
-            return book.result(ids, hd, read_lps(ids))
-        return (ids, hd, read_lps(ids)) if logprobs else (ids, hd)
-
-    def _decode_rows(self, row_params, eos, use_graph, logprobs, constraints, retire_finished):
-        """_decode's loop for a batch begun with row_params (resolved: every max_new_tokens set): a row is finished at its own bound too, and the loop
-        runs until the longest live row has had its steps"""
-        bounds = [int(r.max_new_tokens) for r in row_params]                      # by original row
-        read_lps = lambda ids: self.decode_read_logprobs([len(x) for x in ids]) if logprobs else None
-        book = RetireBook(len(bounds), logprobs) if retire_finished else None
-        chunk = max(1, int(self.retire_chunk)) if retire_finished else 32
-        done = 0
-        while True:
-            ids, hd = self.decode_read()
-            finished = [len(x) >= bounds[r] or ends_stopped(x, eos, constraints) for r, x in zip(self._rows, ids)]
-            left = max([bounds[r] - 1 - done for r, f in zip(self._rows, finished) if not f] + [0])
-            if left <= 0:
-                break
-            if book is not None and done and retire_plan(len(ids), finished.count(False), self.retire_fraction):
-                keep = book.keep_list(finished)
-                book.retire(keep, ids, hd, read_lps(ids))
-                self.retire_rows(keep)
-            n = min(chunk, left)
-            self.decode_steps(n, use_graph)
-            done += n
-        if book is not None:
-            return book.result(ids, hd, read_lps(ids))
-        return (ids, hd, read_lps(ids)) if logprobs else (ids, hd)
-
     def generate(self, videos: Sequence[torch.Tensor], timestamps: Sequence, input_ids: Sequence[Sequence[int]],
                  heads: Sequence[int], max_new_tokens: int, eos: int = -1, use_graph: bool = True,
                  forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
@@ -1071,7 +1031,7 @@ class TraceEngine:
                 i = j
             return slots
 
-        return self._queue(requests, prefill_into, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph, per_request)
+        return self._serve_queue(requests, prefill_into, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph, per_request)
 
     def decode_queue(self, slots: Sequence[int], heads: Sequence[int], max_new_tokens: int, eos: int = -1, *, max_rows: Optional[int] = None,
                      forced: Optional[Sequence[Sequence[int]]] = None, sampling: Optional[SamplingParams] = None, logprobs: bool = False,
@@ -1086,122 +1046,18 @@ class TraceEngine:
             raise ValueError("one head (forced row, RowParams) per slot, every slot once")
         reqs = [(None, None, s, int(h), None if forced is None else forced[r]) + (() if row_params is None else (row_params[r],))
                 for r, (s, h) in enumerate(zip(slots, heads))]
-        return self._queue(reqs, lambda _, rs: [r[2] for r in rs], max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph,
-                           row_params is not None)
+        return self._serve_queue(reqs, lambda _, rs: [r[2] for r in rs], max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph,
+                                 row_params is not None)
 
-    def _queue(self, requests, place, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph, per_request=False):
-        """the one loop of generate_queue / decode_queue.  place(slots the book hands out, requests) -> the KV slots the rows decode from, prefilled"""
-        armed = logits is not None and not logits.off
-        bound = constraints is not None and not constraints.off
-        on_dev = sampling is not None and not sampling.greedy
-        if on_dev and not sampling.on_device:
-            raise ValueError("generate_queue needs the device decode loop: these sampling parameters lie outside the device sampler's domain")
-        if bound:
-            check_constraints(constraints.stop_sequences, constraints.bad_words_ids, constraints.suppress_tokens, constraints.begin_suppress_tokens,
-                              self.cfg.total_vocab)
-
-        mn = int(max_new_tokens)
-
-        def checked(req):
-            req = tuple(req)
-            if len(req) == 6 and not per_request:
-                raise ValueError("a request with a sixth element (RowParams) needs per_request=True")
-            if len(req) not in ((4, 5, 6) if per_request else (4, 5)):
-                raise ValueError("a request is (video, timestamps, input_ids, head[, forced ids[, RowParams]])" if per_request else
-                                 "a request is (video, timestamps, input_ids, head[, forced ids])")
-            req = req + (None,) * (6 - len(req))
-            own = None
-            if per_request:                               # the row's own params, every None field from the call's; checked here, before any work on it
-                own = (req[5] if req[5] is not None else RowParams()).over(sampling, logits, mn).check(mn)
-            if ((own.armed if per_request else armed) or bound) and req[4] is not None:
-                raise ValueError("logits processors and constraints act on the ids a row has recorded; under forced ids those are not the fed ones "
-                                 "(a forced request with logits= / constraints=)")
-            return req[:5] + (own,)
-
-        if isinstance(requests, (list, tuple)):
-            for r in requests:                            # every request is looked at before any work; waiting() checks again as it pulls them
-                checked(r)
+    def _serve_queue(self, requests, place, max_new_tokens, eos, max_rows, sampling, logprobs, logits, constraints, use_graph, per_request):
+        """generate_queue / decode_queue: the requests are checked (decode_loop.checked_requests: a list whole and before any work, an iterator as it
+        is pulled), the modes armed and the loop run.  place(slots the book hands out, requests) -> the KV slots the rows decode from, prefilled"""
+        requests = checked_requests(requests, max_new_tokens, self.cfg.total_vocab, sampling, logits, constraints, per_request)
         cap = max(1, min(int(max_rows) if max_rows else self.decode_batch_max, self.decode_batch_max, self.max_batch))
-        source, buf = iter(requests), []
-
-        def waiting(want: int) -> int:
-            """requests in hand, after pulling until `want` are (or the source is dry)"""
-            while len(buf) < want:
-                try:
-                    buf.append(checked(next(source)))
-                except StopIteration:
-                    break
-            return len(buf)
-
-        def forced_of(reqs):
-            if all(r[4] is None for r in reqs):
-                return None
-            return [list(r[4]) if r[4] is not None else [-1] * mn for r in reqs]
-
-        book = QueueBook(range(cap), logprobs)
-        read_lps = lambda ids: self.decode_read_logprobs([len(x) for x in ids]) if logprobs else None
-        params_of = lambda reqs: [r[5] for r in reqs] if per_request else None
-        limits_of = lambda reqs: [int(r[5].max_new_tokens) if per_request else mn for r in reqs]      # every row's own bound
         if per_request:
-            on_dev = armed = False                     # a per-row batch ignores the batch-wide sampling and logits params: nothing to set or take down
-        if on_dev:
-            self.set_sampling(sampling)
-        if logprobs:
-            self.set_logprobs(True)
-        if armed:
-            self.set_logits_params(logits)
-        try:
-            if bound:
-                self.set_constraints(constraints)
-            while waiting(cap):
-                reqs = [buf.pop(0) for _ in range(min(cap, len(buf)))]
-                base = book.requests                   # the batch's first request: Philox row indices count from it, as decode_begin's do
-                slots = place(book.admit(len(reqs)), reqs)
-                self.decode_begin(slots, [int(r[3]) for r in reqs], mn, eos, forced_of(reqs), row_params=params_of(reqs))
-                own = [0] * len(reqs)                  # steps of its own every live row has taken
-                lim = limits_of(reqs)                  # ids it may record
-                while True:
-                    # a boundary: look at the recorded ids, retire, admit — and look again at what an admission brought (a row whose token 0 ends it
-                    # leaves before it has ridden a chunk), until nothing more is admitted
-                    while True:
-                        ids, hd = self.decode_read()
-                        finished = [len(x) >= m or ends_stopped(x, eos, constraints if bound else None) for x, m in zip(ids, lim)]
-                        live = finished.count(False)
-                        if live == 0:
-                            break
-                        if retire_plan(len(ids), live, self.retire_fraction):
-                            keep = book.keep_list(finished)
-                            book.retire(keep, ids, hd, read_lps(ids))
-                            self.retire_rows(keep)
-                            own, lim = [own[k] for k in keep], [lim[k] for k in keep]
-                        room = min(cap - len(own), len(book.free))
-                        k = admit_plan(len(own), cap, waiting(room), len(book.free), self.admit_fraction) if room > 0 else 0
-                        if not k:
-                            break
-                        reqs = [buf.pop(0) for _ in range(k)]
-                        first = book.requests
-                        slots = place(book.admit(k), reqs)
-                        self._admit(slots, [int(r[3]) for r in reqs], list(range(first - base, first - base + k)), forced_of(reqs), params_of(reqs))
-                        own += [0] * k
-                        lim += limits_of(reqs)
-                    if live == 0:                     # the batch ended: whatever waits begins the next one
-                        book.finish(ids, hd, read_lps(ids))
-                        break
-                    n = min(max(1, int(self.retire_chunk)), max(m - 1 - s for m, s in zip(lim, own)))      # the largest remainder of a row
-                    if n <= 0:
-                        raise RuntimeError("generate_queue: a row has taken max_new_tokens - 1 steps of its own and is not finished")
-                    self.decode_steps(n, use_graph)
-                    own = [s + n for s in own]
-            return book.results()
-        finally:
-            if bound:
-                self.set_constraints(None)
-            if armed:
-                self.set_logits_params(None)
-            if logprobs:
-                self.set_logprobs(False)
-            if on_dev:
-                self.set_sampling(None)
+            sampling = logits = None                   # a per-row batch ignores the batch-wide sampling and logits params: nothing to set or take down
+        with self._modes(sampling, logprobs, logits, constraints):
+            return self._loop(requests, place, QUEUE, cap, max_new_tokens, eos, logprobs, constraints, use_graph, True).results()
 
     def generate_samples(self, video: torch.Tensor, timestamps, prompt_ids: Sequence[int], head: int, n: int, max_new_tokens: int, eos: int = -1,
                          sampling: Optional[SamplingParams] = None, use_graph: bool = True, logits: Optional[LogitsParams] = None,
