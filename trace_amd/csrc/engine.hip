@@ -1217,24 +1217,35 @@ static int prefill_kv8_pack(trace_ctx* c, int l, int slot0, int nb, int L, int p
     return launch_kv8_pack(c->kv_stage_k + (size_t)past * c->HD, (long)c->slot_stride, (long)c->kv_head_stride, c->HD,
                            c->pQKV + (size_t)(c->NQ + c->NKV) * c->HD, (long)L * c->QKV, c->HD, c->QKV, kv8_layer(c, l), c->d_ident + slot0, past, L, nb, c->NKV, s);
 }
+// The rows of the row-major workspaces (pX, pH, pO, pACT, pQKV) that a stage reads and writes in place: rows first + i * mult, i < n.  A stage takes the
+// pointers `first` rows in and mult x width as the leading dimensions.
+struct PfRows { int first, n, mult; };
 static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out, hipStream_t s, int past = 0) {
     const int H = c->H, I = c->I, HD = c->HD, QKV = c->QKV, M = nb * L;
+    const int QW = c->NQ * HD, KVW = 2 * c->NKV * HD;  // the q and the k | v columns of a qkv row
     const int kslot0 = c->kv8 ? 0 : slot0;            // first K / V^T slot the layer's kernels use
     AttnArgs a{};
-    a.Q = c->pQKV; a.O = c->pO;
     a.q_bs = (long)L * QKV; a.q_hs = HD; a.q_rs = QKV;
     a.k_bs = (long)c->slot_stride; a.k_hs = (long)c->kv_head_stride; a.k_rs = HD;
     a.v_bs = (long)c->slot_stride; a.v_hs = (long)c->kv_head_stride; a.v_rs = c->ctx_pad;      // V^T straight from the cache
     a.o_bs = (long)L * H; a.o_hs = HD; a.o_rs = H;
-    a.nq_rows = L; a.nkv_rows = past + L; a.batch = nb; a.heads = c->NQ; a.kv_heads = c->NKV;
+    a.nkv_rows = past + L; a.batch = nb; a.heads = c->NQ; a.kv_heads = c->NKV;
     a.scale = 1.0f / sqrtf((float)HD); a.causal = 1;
     for (int l = 0; l < c->NL; ++l) {
-        LlmLayer W = c->llm[l];
-        if (c->w4) {          // this layer's four projections as 16-bit rows (exactly the weights the decode GEMVs widen); the GEMMs below run on them unchanged
-            const int wn[4] = {QKV, H, 2 * I, H}, wk[4] = {H, H, H, I};
-            for (int p = 0; p < 4; ++p) LCHK(launch_dequant_w4(W.w4c[p], W.w4e[p], c->w4_row[p], wk[p], wn[p], wk[p], s));
-            W.wqkv = c->w4_row[0]; W.wo = c->w4_row[1]; W.wgu = c->w4_row[2]; W.wd = c->w4_row[3];
-        }
+        const LlmLayer& W = c->llm[l];
+        struct { int N, K; const bf16_t* w; const uint8_t* w8; const float* sw; } P[4] = {       // qkv, o, gate|up, down: W[N][K], 16-bit or e4m3 + row scales
+            {QKV, H, W.wqkv, W.wqkv8, W.sqkv}, {H, H, W.wo, W.wo8, W.so}, {2 * I, H, W.wgu, W.wgu8, W.sgu}, {H, I, W.wd, W.wd8, W.sd}};
+        if (c->w4)            // this layer's four projections as 16-bit rows (exactly the weights the decode GEMVs widen); the GEMMs below run on them unchanged
+            for (int p = 0; p < 4; ++p) {
+                LCHK(launch_dequant_w4(W.w4c[p], W.w4e[p], c->w4_row[p], P[p].K, P[p].N, P[p].K, s));
+                P[p].w = c->w4_row[p];
+            }
+        // Projection p over n rows: C = A W^T, + R when given (R lies where C does: ldr = ldc).  cols > 0: only the output columns col0 .. col0 + cols - 1.
+        auto proj = [&](int p, const bf16_t* A, int lda, bf16_t* C, int ldc, const bf16_t* R, int n, int epi, int col0 = 0, int cols = 0) {
+            const int N = cols ? cols : P[p].N, K = P[p].K, ldr = R ? ldc : 0;
+            if (c->fp8) return gemm_fp8(c, A, lda, P[p].w8 + (size_t)col0 * K, P[p].sw + col0, C, ldc, R, ldr, n, N, K, epi, s);
+            return gemm(A, lda, P[p].w + (size_t)col0 * K, K, C, ldc, nullptr, R, ldr, n, N, K, epi, s);
+        };
         bf16_t* kc = c->kv8 ? c->kv_stage_k : c->kcache + (size_t)l * c->layer_stride;
         bf16_t* vc = c->kv8 ? c->kv_stage_v : c->vcache + (size_t)l * c->layer_stride;
         if (c->kv8 && past > 0)
@@ -1245,52 +1256,34 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
         // everything, trace_mistral.py:190-200, and then uses logits[:, -1]) — so: the k | v slice of the qkv projection over all M rows, and q,
         // attention, o-proj and the MLP for the nb last rows, on the same kernels reading / writing those rows in place (row stride L x width).
         // Same MFMA tile kernels, same K order, same epilogues: bit-identical to the full layer (tests/test_gpu_parity.py), ~3 % of a prefill saved.
-        if (g_tune.prefill_last_rows && l == c->NL - 1 && !hidden_out && !c->fp8 && L > 1) {
-            const int KV = 2 * c->NKV * HD, QW = c->NQ * HD;
-            const size_t last = (size_t)(L - 1);
-            TRY(gemm(c->pH, H, W.wqkv + (size_t)QW * H, H, c->pQKV + QW, QKV, nullptr, nullptr, 0, M, KV, H, EPI_NONE, s));
-            TRY(gemm(c->pH + last * H, L * H, W.wqkv, H, c->pQKV + last * QKV, L * QKV, nullptr, nullptr, 0, nb, QW, H, EPI_NONE, s));
-            LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, kslot0, past, M,
-                                c->NQ, c->NKV, HD, c->rope_cos, c->rope_sin, L, s));      // (also rotates the stale q of the other rows: 10 us, nobody reads them)
-            LCHK(launch_transpose_v(c->pQKV + (size_t)(c->NQ + c->NKV) * HD, (long)L * QKV, HD, QKV, vc + (size_t)kslot0 * c->slot_stride,
-                                    (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, L, HD, c->NKV, nb, s, 0, past));
-            AttnArgs a1 = a;
-            a1.Q = c->pQKV + last * QKV; a1.O = c->pO + last * H;
-            a1.nq_rows = 1;                                  // one query row per prompt: row L - 1 attends all past + L keys (causal offset nkv - nq)
-            a1.K = kc + (size_t)kslot0 * c->slot_stride;
-            a1.V = vc + (size_t)kslot0 * c->slot_stride;
-            LCHK(launch_attn_prefill(a1, s));
-            if (c->kv8) LCHK(prefill_kv8_pack(c, l, slot0, nb, L, past, s));
-            bf16_t* xl = c->pX + last * H;
-            bf16_t* hl = c->pH + last * H;
-            TRY(gemm(c->pO + last * H, L * H, W.wo, H, xl, L * H, nullptr, xl, L * H, nb, H, H, EPI_RESIDUAL, s));
-            LCHK(launch_rmsnorm(xl, L * H, hl, L * H, W.rms2, nb, H, c->c.rms_eps, s));
-            TRY(gemm(hl, L * H, W.wgu, H, c->pACT + last * I, L * I, nullptr, nullptr, 0, nb, 2 * I, H, EPI_SWIGLU, s));
-            TRY(gemm(c->pACT + last * I, L * I, W.wd, I, xl, L * H, nullptr, xl, L * H, nb, H, I, EPI_RESIDUAL, s));
-            continue;
-        }
-        if (c->fp8) { TRY(gemm_fp8(c, c->pH, H, W.wqkv8, W.sqkv, c->pQKV, QKV, nullptr, 0, M, QKV, H, EPI_NONE, s)); }
-        else TRY(gemm(c->pH, H, W.wqkv, H, c->pQKV, QKV, nullptr, nullptr, 0, M, QKV, H, EPI_NONE, s));
+        // In the terms of this body the shortcut is a row set {L - 1, nb, L} for everything after the cache write, and a qkv projection split in two.
+        // (The e4m3 weight paths do not take it — proj would serve them, the condition keeps them out.)
+        const bool shortcut = g_tune.prefill_last_rows && l == c->NL - 1 && !hidden_out && !c->fp8 && L > 1;
+        const PfRows r = shortcut ? PfRows{L - 1, nb, L} : PfRows{0, M, 1};
+        const size_t r0 = (size_t)r.first;
+        const int ldH = r.mult * H, ldI = r.mult * I, ldQ = r.mult * QKV;
+        if (shortcut) {       // the one place where the shortcut is more than a row set: k | v for every row, q for the row set
+            TRY(proj(0, c->pH, H, c->pQKV + QW, QKV, nullptr, M, EPI_NONE, QW, KVW));
+            TRY(proj(0, c->pH + r0 * H, ldH, c->pQKV + r0 * QKV, ldQ, nullptr, r.n, EPI_NONE, 0, QW));
+        } else TRY(proj(0, c->pH, H, c->pQKV, QKV, nullptr, M, EPI_NONE));
+        // cache write and attend.  q and k rotated, k into the cache (under the shortcut this also rotates the stale q of the other rows: 10 us, nobody reads them)
         LCHK(launch_rope_kv(c->pQKV, QKV, kc, nullptr, (long)c->slot_stride, (long)c->kv_head_stride, nullptr, nullptr, kslot0, past, M,
                             c->NQ, c->NKV, HD, c->rope_cos, c->rope_sin, L, s));
         // V goes into the cache transposed ([kvh][hd][ctx_pad]; positions past+L..Lpad-1 are zero-filled, later overwritten)
         LCHK(launch_transpose_v(c->pQKV + (size_t)(c->NQ + c->NKV) * HD, (long)L * QKV, HD, QKV, vc + (size_t)kslot0 * c->slot_stride,
                                 (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, L, HD, c->NKV, nb, s, 0, past));
+        // the row set's queries against all past + L keys of their prompt (r.n / nb query rows a prompt: L, or the one row L - 1 — causal offset nkv - nq)
+        a.Q = c->pQKV + r0 * QKV; a.O = c->pO + r0 * H; a.nq_rows = r.n / nb;
         a.K = kc + (size_t)kslot0 * c->slot_stride;
         a.V = vc + (size_t)kslot0 * c->slot_stride;
         LCHK(launch_attn_prefill(a, s));
         if (c->kv8) LCHK(prefill_kv8_pack(c, l, slot0, nb, L, past, s));
-        if (c->fp8) {
-            TRY(gemm_fp8(c, c->pO, H, W.wo8, W.so, c->pX, H, c->pX, H, M, H, H, EPI_RESIDUAL, s));
-            LCHK(launch_rmsnorm(c->pX, H, c->pH, H, W.rms2, M, H, c->c.rms_eps, s));
-            TRY(gemm_fp8(c, c->pH, H, W.wgu8, W.sgu, c->pACT, I, nullptr, 0, M, 2 * I, H, EPI_SWIGLU, s));
-            TRY(gemm_fp8(c, c->pACT, I, W.wd8, W.sd, c->pX, H, c->pX, H, M, H, I, EPI_RESIDUAL, s));
-            continue;
-        }
-        TRY(gemm(c->pO, H, W.wo, H, c->pX, H, nullptr, c->pX, H, M, H, H, EPI_RESIDUAL, s));
-        LCHK(launch_rmsnorm(c->pX, H, c->pH, H, W.rms2, M, H, c->c.rms_eps, s));
-        TRY(gemm(c->pH, H, W.wgu, H, c->pACT, I, nullptr, nullptr, 0, M, 2 * I, H, EPI_SWIGLU, s));
-        TRY(gemm(c->pACT, I, W.wd, I, c->pX, H, nullptr, c->pX, H, M, H, I, EPI_RESIDUAL, s));
+        // tail over the row set: o-proj + residual, norm, gate|up SwiGLU, down + residual
+        bf16_t *x = c->pX + r0 * H, *h = c->pH + r0 * H, *act = c->pACT + r0 * I;
+        TRY(proj(1, c->pO + r0 * H, ldH, x, ldH, x, r.n, EPI_RESIDUAL));
+        LCHK(launch_rmsnorm(x, ldH, h, ldH, W.rms2, r.n, H, c->c.rms_eps, s));
+        TRY(proj(2, h, ldH, act, ldI, nullptr, r.n, EPI_SWIGLU));
+        TRY(proj(3, act, ldI, x, ldH, x, r.n, EPI_RESIDUAL));
     }
     if (hidden_out) LCHK(launch_rmsnorm(c->pX, H, (bf16_t*)hidden_out, H, c->final_norm, M, H, c->c.rms_eps, s));
     for (int b = 0; b < nb; ++b) {
@@ -1301,41 +1294,10 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
     return TRACE_OK;
 }
 
-extern "C" int trace_llm_prefill(trace_ctx* c, int slot, const void* embeds, int L, void* hidden_out, void* stream) {
-    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
-    if (slot < 0 || slot >= c->max_B || L < 1 || L > c->max_ctx) return fail(TRACE_ERR_ARG, "bad slot / L");
-    hipStream_t s = (hipStream_t)stream;
-    if (embeds) HIPCHK(hipMemcpyAsync(c->pX, embeds, (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
-    return prefill_impl(c, slot, 1, L, hidden_out, s);
-}
-
-extern "C" int trace_llm_prefill_pair(trace_ctx* c, int slot0, const void* embeds0, const void* embeds1, int L, void* stream) {
-    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
-    if (slot0 < 0 || slot0 + 1 >= c->max_B || L < 1 || L > c->max_ctx || !embeds0 || !embeds1) return fail(TRACE_ERR_ARG, "bad slot / L / embeds");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(c->pX, embeds0, (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->pX + (size_t)L * c->H, embeds1, (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
-    return prefill_impl(c, slot0, 2, L, nullptr, s);
-}
-
-// n <= 8 prompts of EQUAL spliced length in one pass while n x L <= max(4 max_ctx, min(8192, 8 max_ctx)) rows (the prefill workspaces) -> KV slots slot0 .. slot0 + n - 1.  Four 1967-row prompts give the GEMMs M = 7868 = 31 row tiles:
-// qkv 744 tiles = 2.9 rounds of the 256 CUs (a pair: 384 = 1.5 rounds, a quarter of the second round's CUs idle), o / down 496 = 1.94, gate|up 13.6
-extern "C" int trace_llm_prefill_multi(trace_ctx* c, int slot0, const void* const* embeds, int n, int L, void* stream) {
-    if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
-    if (!embeds || n < 1 || n > PF_MAX_N || slot0 < 0 || slot0 + n > c->max_B || L < 1 || L > c->max_ctx) return fail(TRACE_ERR_ARG, "bad slot / n / L / embeds");
-    if ((size_t)n * L > pf_rows(c->max_ctx)) return fail(TRACE_ERR_ARG, "n x L exceeds the prefill workspace (max(4 max_ctx, min(8192, 8 max_ctx)) rows)");
-    hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < n; ++i) {
-        if (!embeds[i]) return fail(TRACE_ERR_ARG, "null embeds");
-        HIPCHK(hipMemcpyAsync(c->pX + (size_t)i * L * c->H, embeds[i], (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
-    }
-    return prefill_impl(c, slot0, n, L, nullptr, s);
-}
-
-// Continue n slots that hold at least `past` rows each (a prompt prefix prefilled or copied there earlier) with L new rows per slot: what
-// trace_llm_prefill_multi is for whole prompts.  Everything is checked before the first launch.
-// the argument rules of an append, for trace_llm_prefill_append and trace_llm_score_append alike (the latter has no hidden_out and passes NULL)
-// (have >= 0: the rows every slot WILL hold when the append runs, for a caller that fills them first)
+// ---- the entry path: all six calls that prefill come through prefill_entry ----
+// The argument rules of a pass: n slots that hold at least `past` rows each (a prompt prefix prefilled or copied there earlier; a whole prompt is
+// past == 0) take L new rows per slot.  (trace_llm_score_append has no hidden_out and passes NULL;
+// have >= 0: the rows every slot WILL hold when the pass runs, for a caller that fills them first)
 static int append_check(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, const void* hidden_out, int have = -1) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
     if (n < 1 || n > PF_MAX_N || slot0 < 0 || slot0 + n > c->max_B) return fail(TRACE_ERR_ARG, "bad slot / n");
@@ -1350,17 +1312,41 @@ static int append_check(trace_ctx* c, int slot0, int n, int past, const void* co
     }
     return TRACE_OK;
 }
-// the n prompts' new rows end to end into pX (embeds == NULL: the internal buffer already holds them)
-static int append_stage_embeds(trace_ctx* c, int n, const void* const* embeds, int L, hipStream_t s) {
+// append_check, then `before` (what a caller has left to refuse or to enqueue ahead of the pass: trace_llm_prefill_shared's fan-out of the prefix,
+// trace_llm_score_append's heads and ids), then the n prompts' new rows end to end into pX (embeds == NULL: the internal buffer already holds them), then
+// prefill_impl.  Everything is checked before the first launch.  rows_hidden: every row's final-norm hidden state is kept in pH, which is free once
+// the last layer is done (any n; hidden_out is the caller's buffer and n == 1 only).
+static int nothing_before() { return TRACE_OK; }
+template <class Before = int (*)()>
+static int prefill_entry(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, void* hidden_out, void* stream, int have = -1,
+                         bool rows_hidden = false, Before before = nothing_before) {
+    TRY(append_check(c, slot0, n, past, embeds, L, hidden_out, have));
+    TRY(before());
+    hipStream_t s = (hipStream_t)stream;
     if (embeds)
         for (int i = 0; i < n; ++i) HIPCHK(hipMemcpyAsync(c->pX + (size_t)i * L * c->H, embeds[i], (size_t)L * c->H * 2, hipMemcpyDeviceToDevice, s));
-    return TRACE_OK;
+    return prefill_impl(c, slot0, n, L, rows_hidden ? c->pH : hidden_out, s, past);
 }
+
+extern "C" int trace_llm_prefill(trace_ctx* c, int slot, const void* embeds, int L, void* hidden_out, void* stream) {
+    return prefill_entry(c, slot, 1, 0, embeds ? &embeds : nullptr, L, hidden_out, stream);
+}
+
+extern "C" int trace_llm_prefill_pair(trace_ctx* c, int slot0, const void* embeds0, const void* embeds1, int L, void* stream) {
+    const void* embeds[2] = {embeds0, embeds1};
+    return prefill_entry(c, slot0, 2, 0, embeds, L, nullptr, stream);
+}
+
+// n <= 8 prompts of EQUAL spliced length in one pass while n x L <= max(4 max_ctx, min(8192, 8 max_ctx)) rows (the prefill workspaces) -> KV slots slot0 .. slot0 + n - 1.  Four 1967-row prompts give the GEMMs M = 7868 = 31 row tiles:
+// qkv 744 tiles = 2.9 rounds of the 256 CUs (a pair: 384 = 1.5 rounds, a quarter of the second round's CUs idle), o / down 496 = 1.94, gate|up 13.6
+extern "C" int trace_llm_prefill_multi(trace_ctx* c, int slot0, const void* const* embeds, int n, int L, void* stream) {
+    if (c && c->finalized && !embeds) return fail(TRACE_ERR_ARG, "null embeds");      // (the internal buffer is trace_llm_prefill's and trace_llm_prefill_append's to use)
+    return prefill_entry(c, slot0, n, 0, embeds, L, nullptr, stream);
+}
+
+// Continue n slots that hold at least `past` rows each with L new rows per slot: what trace_llm_prefill_multi is for whole prompts.
 extern "C" int trace_llm_prefill_append(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, void* hidden_out, void* stream) {
-    TRY(append_check(c, slot0, n, past, embeds, L, hidden_out));
-    hipStream_t s = (hipStream_t)stream;
-    TRY(append_stage_embeds(c, n, embeds, L, s));
-    return prefill_impl(c, slot0, n, L, hidden_out, s, past);
+    return prefill_entry(c, slot0, n, past, embeds, L, hidden_out, stream);
 }
 
 // Rows [0, rows) of every layer's K and V^T from one slot to n others (launch_kv_copy, KV_COPY_MAX destinations per launch).  A copy of ALL the
@@ -1401,14 +1387,12 @@ extern "C" int trace_llm_prefill_shared(trace_ctx* c, int src_slot, int slot0, i
     if (src_slot < 0 || src_slot >= c->max_B || past < 1) return fail(TRACE_ERR_ARG, "bad source slot / past");
     if (past > c->slot_len[src_slot]) return fail(TRACE_ERR_STATE, "past exceeds the rows the source slot holds");
     if (!embeds) return fail(TRACE_ERR_ARG, "null embeds");
-    TRY(append_check(c, slot0, n, past, embeds, L, nullptr, past));
-    int32_t dst[PF_MAX_N];
-    int m = 0;
-    for (int i = 0; i < n; ++i) if (slot0 + i != src_slot) dst[m++] = slot0 + i;
-    if (m) TRY(trace_kv_copy(c, src_slot, dst, m, past, stream));
-    hipStream_t s = (hipStream_t)stream;
-    TRY(append_stage_embeds(c, n, embeds, L, s));
-    return prefill_impl(c, slot0, n, L, nullptr, s, past);
+    return prefill_entry(c, slot0, n, past, embeds, L, nullptr, stream, past, false, [&] {
+        int32_t dst[PF_MAX_N];
+        int m = 0;
+        for (int i = 0; i < n; ++i) if (slot0 + i != src_slot) dst[m++] = slot0 + i;
+        return m ? trace_kv_copy(c, src_slot, dst, m, past, stream) : (int)TRACE_OK;
+    });
 }
 
 // masked logits of R final-norm hidden rows under ONE head: what forward() returns for every position of a sequence
@@ -2302,23 +2286,24 @@ extern "C" int trace_llm_score_rows(trace_ctx* c, const void* hidden, int R, con
     if (rc != TRACE_OK) return fail(rc, "score_rows launch failed");
     return TRACE_OK;
 }
-// trace_llm_prefill_append's checks (append_check: one function for both) and body with every row's final-norm hidden state kept (in pH, free once the last layer is done), then the score of
-// the n x L rows.  Everything is checked before the first launch.
+// trace_llm_prefill_append's pass (prefill_entry) with every row's final-norm hidden state kept, then the score of the n x L rows.  Everything is
+// checked before the first launch.
 extern "C" int trace_llm_score_append(trace_ctx* c, int slot0, int n, int past, const void* const* embeds, int L, const int32_t* heads, const int32_t* ids,
                                       float* out, void* stream) {
-    TRY(append_check(c, slot0, n, past, embeds, L, nullptr));
-    if (!heads || !ids || !out) return fail(TRACE_ERR_ARG, "null heads / ids / out");
-    const int M = n * L;
-    for (int i = 0; i < M; ++i) {
-        if (heads[i] < 0 || heads[i] > 2) return fail(TRACE_ERR_ARG, "head must be 0, 1 or 2");
-        if (ids[i] < -1 || ids[i] >= c->NV) return fail(TRACE_ERR_ARG, "id must be -1 (ignore) or a vocabulary id");
-    }
-    TRY(score_buffers(c));
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(c->d_score_heads, heads, (size_t)M * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_score_ids, ids, (size_t)M * 4, hipMemcpyHostToDevice, s));
-    TRY(append_stage_embeds(c, n, embeds, L, s));
-    TRY(prefill_impl(c, slot0, n, L, c->pH, s, past));
+    int M = 0;
+    TRY(prefill_entry(c, slot0, n, past, embeds, L, nullptr, stream, -1, true, [&] {
+        if (!heads || !ids || !out) return fail(TRACE_ERR_ARG, "null heads / ids / out");
+        M = n * L;
+        for (int i = 0; i < M; ++i) {
+            if (heads[i] < 0 || heads[i] > 2) return fail(TRACE_ERR_ARG, "head must be 0, 1 or 2");
+            if (ids[i] < -1 || ids[i] >= c->NV) return fail(TRACE_ERR_ARG, "id must be -1 (ignore) or a vocabulary id");
+        }
+        TRY(score_buffers(c));
+        HIPCHK(hipMemcpyAsync(c->d_score_heads, heads, (size_t)M * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_score_ids, ids, (size_t)M * 4, hipMemcpyHostToDevice, s));
+        return (int)TRACE_OK;
+    }));
     const int rc = launch_score_rows(c->pH, c->H, c->wheads, c->H, c->H, M, c->d_score_heads, c->d_score_ids, c->V, c->Tv, c->Sv, c->score_ws, c->d_score_out, s);
     if (rc != TRACE_OK) return fail(rc, "score_rows launch failed");
     HIPCHK(hipMemcpyAsync(out, c->d_score_out, (size_t)M * 4, hipMemcpyDeviceToHost, s));

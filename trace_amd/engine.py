@@ -141,7 +141,7 @@ class TraceEngine:
         self._rows_history: List[List[int]] = []      # _rows after decode_begin and after every retire of the running batch
         self.retires = 0                      # retire_rows calls that shrank a batch, so far
         self.admits = 0                       # admit_rows calls that grew a batch, so far
-        self._prefix = None            # (key, rows): KV slot 0 holds `rows` prefilled prompt rows described by `key` (set_prefix_entry); see _drop_prefix
+        self._prefix = None            # (key, rows): KV slot 0 holds `rows` prefilled prompt rows described by `key` (set_prefix_entry); see _prefill_call
         self._dbg = None               # debugging hook: callable(tag, index, tensor-or-None) called between the stages (tools/pipeline_stress.py)
 
     @property
@@ -331,15 +331,35 @@ class TraceEngine:
         _lib.check(self.lib.trace_splice_embeds(self.h, ids, len(ids), tr, len(tr), sr, len(sr), C.byref(L), _ptr(out), _stream()))
         return (L.value, out[: L.value]) if want_output else L.value
 
-    def prefill(self, slot: int, L: int, embeds: Optional[torch.Tensor] = None, want_hidden: bool = False):
+    # The model's prefix cache (TraceMistralForCausalLM.enable_prefix_cache) keeps its one entry in KV slot 0.  Whether the slot still holds those rows is
+    # decided here: every call that rewrites slot 0 from row 0 or below the entry's length, or encodes a video (the entry's owner then no longer knows
+    # which video the engine last saw), drops it.  Decoding never does: it writes rows at and above the slot's length.
+    def _prefill_call(self, call: str, slot0: int, past: int, tensors, L: int, want_hidden: bool = False, src=None, score=()):
+        """One prefill pass through the C symbol trace_llm_<call>: the pointer array of `tensors` (contiguous device [L, hidden] rows of this engine's
+        dtype, one per slot; None: the engine's own embedding buffer, one slot), the prefix-entry rule, stats["prefill_rows"].  Returns the [L, hidden]
+        final-norm rows if want_hidden.  src: prefill_shared's source slot; score: score_append's (heads, ids, out)."""
+        n = len(tensors) if tensors else 1
+        ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in tensors]) if tensors else None
         hid = torch.empty((L, self.cfg.hidden_size), dtype=self.dtype, device=self.device) if want_hidden else None
-        if embeds is not None:
-            embeds = embeds.to(self.device, self.dtype).contiguous()
-        if slot == 0:
+        if call in ("prefill_append", "score_append"):                 # rows below `past` stay: the entry survives unless they reach into it
+            drop = slot0 == 0 and self._prefix is not None and past < self._prefix[1]
+        else:                                                          # a whole prompt, or the shared rows copied in, from row 0
+            drop = slot0 == 0
+        if drop:
             self._drop_prefix()
-        _lib.check(self.lib.trace_llm_prefill(self.h, slot, _ptr(embeds), L, _ptr(hid), _stream()))
-        self.stats["prefill_rows"] += L
+        args = {"prefill": lambda: (slot0, ptrs and ptrs[0], L, _ptr(hid)),
+                "prefill_pair": lambda: (slot0, ptrs[0], ptrs[1], L),
+                "prefill_multi": lambda: (slot0, ptrs, n, L),
+                "prefill_append": lambda: (slot0, n, past, ptrs, L, _ptr(hid)),
+                "prefill_shared": lambda: (src, slot0, n, past, ptrs, L),
+                "score_append": lambda: (slot0, n, past, ptrs, L, *score)}[call]()
+        _lib.check(getattr(self.lib, "trace_llm_" + call)(self.h, *args, _stream()))
+        self.stats["prefill_rows"] += n * L
         return hid
+
+    def prefill(self, slot: int, L: int, embeds: Optional[torch.Tensor] = None, want_hidden: bool = False):
+        keep = None if embeds is None else [embeds.to(self.device, self.dtype).contiguous()]
+        return self._prefill_call("prefill", slot, 0, keep, L, want_hidden)
 
     # ---- prompt-prefix reuse: continue a slot that holds rows, copy rows between slots, embed rows without a video ----
     def embed_rows(self, ids: Sequence[int], time_rows: Sequence[int] = (), score_rows: Sequence[int] = (), want_output: bool = False):
@@ -357,7 +377,7 @@ class TraceEngine:
         if embeds is None:
             if L is None:
                 raise ValueError("prefill_append(embeds=None) needs L, the row count of the last embed_rows()")
-            keep, n = [], 1
+            keep, n = None, 1
         else:
             keep = [e.to(self.device, self.dtype).contiguous() for e in ([embeds] if isinstance(embeds, torch.Tensor) else list(embeds))]
             n = len(keep)
@@ -366,13 +386,7 @@ class TraceEngine:
             L = keep[0].shape[0]
         if want_hidden and n != 1:
             raise ValueError("want_hidden with one slot only")
-        hid = torch.empty((L, self.cfg.hidden_size), dtype=self.dtype, device=self.device) if want_hidden else None
-        ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in keep]) if keep else None
-        if self._prefix is not None and slot0 == 0 and past < self._prefix[1]:
-            self._drop_prefix()
-        _lib.check(self.lib.trace_llm_prefill_append(self.h, int(slot0), n, int(past), ptrs, int(L), _ptr(hid), _stream()))
-        self.stats["prefill_rows"] += n * L
-        return hid
+        return self._prefill_call("prefill_append", int(slot0), int(past), keep, int(L), want_hidden)
 
     def kv_copy(self, src: int, dsts: Sequence[int], rows: int):
         """KV rows [0, rows) of slot `src` to every slot of `dsts` (trace_kv_copy); their length becomes `rows`."""
@@ -387,15 +401,8 @@ class TraceEngine:
         keep = [e.contiguous() for e in embeds]
         n = len(keep)
         assert 1 <= n <= APPEND_GROUP_MAX and all(e.shape == keep[0].shape and e.dtype == self.dtype and e.is_cuda for e in keep)
-        ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in keep])
-        if slot0 == 0:
-            self._drop_prefix()
-        _lib.check(self.lib.trace_llm_prefill_shared(self.h, int(src), int(slot0), n, int(past), ptrs, keep[0].shape[0], _stream()))
-        self.stats["prefill_rows"] += n * keep[0].shape[0]
+        self._prefill_call("prefill_shared", int(slot0), int(past), keep, keep[0].shape[0], src=int(src))
 
-    # The model's prefix cache (TraceMistralForCausalLM.enable_prefix_cache) keeps its one entry in KV slot 0.  Whether the slot still holds those rows is
-    # decided here: every call that rewrites slot 0 from row 0 or below the entry's length, or encodes a video (the entry's owner then no longer knows
-    # which video the engine last saw), drops it.  Decoding never does: it writes rows at and above the slot's length.
     def set_prefix_entry(self, key, rows: int):
         self._prefix = (key, int(rows))
 
@@ -478,12 +485,8 @@ class TraceEngine:
             n = len(run)
             if n > 1 and past > 0:
                 self.kv_copy(slot0, list(range(slot0 + 1, slot0 + n)), past)
-            if self._prefix is not None and slot0 == 0 and past < self._prefix[1]:
-                self._drop_prefix()
             res = (C.c_float * (n * L))()
-            ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in embeds])
-            _lib.check(self.lib.trace_llm_score_append(self.h, int(slot0), n, past, ptrs, L, _i32(hd), _i32(tg), res, _stream()))
-            self.stats["prefill_rows"] += n * L
+            self._prefill_call("score_append", int(slot0), past, embeds, L, score=(_i32(hd), _i32(tg), res))
             self.stats["score_rows"] += n * L
             arr = np.frombuffer(res, dtype=np.float32).reshape(n, L)
             for j, b in enumerate(run):
@@ -494,11 +497,7 @@ class TraceEngine:
     def prefill_pair(self, slot0: int, embeds0: torch.Tensor, embeds1: torch.Tensor):
         """two spliced prompts of equal length -> KV slots slot0, slot0 + 1 in one pass (trace_llm_prefill_pair)"""
         assert embeds0.shape == embeds1.shape and embeds0.dtype == self.dtype and embeds0.is_cuda
-        if slot0 == 0:
-            self._drop_prefix()
-        _lib.check(self.lib.trace_llm_prefill_pair(self.h, slot0, _ptr(embeds0.contiguous()), _ptr(embeds1.contiguous()),
-                                                   embeds0.shape[0], _stream()))
-        self.stats["prefill_rows"] += 2 * embeds0.shape[0]
+        self._prefill_call("prefill_pair", slot0, 0, [embeds0.contiguous(), embeds1.contiguous()], embeds0.shape[0])
 
     PREFILL_GROUP = 4          # equal-length prompts of max_ctx rows one prefill pass takes (trace_llm_prefill_multi); shorter prompts: prefill_group(L)
     PREFILL_GROUP_MAX = 8
@@ -529,15 +528,10 @@ class TraceEngine:
         return best
 
     def prefill_multi(self, slot0: int, embeds: Sequence[torch.Tensor]):
-        """up to 4 spliced prompts of equal length -> KV slots slot0 .. slot0 + n - 1 in one pass"""
+        """up to 8 spliced prompts of equal length, n x L within prefill_rows -> KV slots slot0 .. slot0 + n - 1 in one pass (trace_llm_prefill_multi)"""
         n = len(embeds)
         assert 1 <= n <= self.PREFILL_GROUP_MAX and n * embeds[0].shape[0] <= self.prefill_rows and all(e.shape == embeds[0].shape and e.dtype == self.dtype and e.is_cuda for e in embeds)
-        keep = [e.contiguous() for e in embeds]
-        ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in keep])
-        if slot0 == 0:
-            self._drop_prefix()
-        _lib.check(self.lib.trace_llm_prefill_multi(self.h, slot0, ptrs, n, keep[0].shape[0], _stream()))
-        self.stats["prefill_rows"] += n * keep[0].shape[0]
+        self._prefill_call("prefill_multi", slot0, 0, [e.contiguous() for e in embeds], embeds[0].shape[0])
 
     # ---- decode --------------------------------------------------------------------------------
     def decode_begin(self, slots: Sequence[int], heads: Sequence[int], max_new: int, eos: int = -1,
