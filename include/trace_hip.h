@@ -445,6 +445,11 @@ int trace_set_profile(trace_ctx* ctx, int on);
 int trace_debug_buffers(trace_ctx* ctx, void** kcache, void** vcache, void** xlast, int64_t* strides);
 /* The batch sizes a captured decode step exists for (any tail mode), ascending, into sizes[0 .. cap) (HOST, may be NULL); returns their number. */
 int trace_debug_step_graphs(trace_ctx* ctx, int32_t* sizes, int cap);
+/* One per-row column of the running decode batch, rows [0, B), as 32-bit words into out[0 .. cap) (HOST); synchronous.  Returns the column's words per
+ * row, or 0 with nothing written where the armed mode has no such column (logprobs; the per-row params).  trace_debug_decode_column(ctx, i) names
+ * column i (slots, pos, heads, done, out_len, row_id, step0, out_ids, forced, logprobs, row_sp, row_lp, row_max, x), NULL past the end. */
+int trace_debug_decode_rows(trace_ctx* ctx, int column, int32_t* out, int cap);
+const char* trace_debug_decode_column(trace_ctx* ctx, int i);
 /* The same for a kv_cache_fp8 context: device addresses of K8, V8 (bytes), ks, vs (fp32), strides[8] = layer, slot, kv-head strides of the payload in
  * BYTES (those of the scales are these / 128), ctx_pad, layers, kv heads, head_dim, hidden.  TRACE_ERR_STATE on a 16-bit-cache context. */
 int trace_debug_kv8_buffers(trace_ctx* ctx, void** k8, void** v8, void** ks, void** vs, int64_t* strides);

@@ -108,6 +108,8 @@ SIGNATURES = {
     "trace_set_gemm_cus": (I, [P, I]),
     "trace_set_profile": (I, [P, I]),
     "trace_debug_step_graphs": (I, [P, P, I]),
+    "trace_debug_decode_rows": (I, [P, I, P, I]),
+    "trace_debug_decode_column": (C.c_char_p, [P, I]),
     "trace_debug_buffers": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64)]),
     "trace_debug_kv8_buffers": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64)]),
     "trace_get_profile": (I, [P, P, I]),

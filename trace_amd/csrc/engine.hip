@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <string>
 #include <unordered_map>
@@ -42,6 +43,18 @@ struct LlmLayer {
     // in the decode tile layout; the 16-bit pointers above stay null
     uint8_t *w4c[4], *w4e[4];
 };
+// A layer's four projections as a table, in w4c's order (0 qkv, 1 o, 2 gate|up, 3 down): W[N][K] in every copy a body may run it on.
+struct Proj {
+    int N, K;
+    const bf16_t *w, *wd;            // 16-bit: row-major (prefill GEMMs, the wide decode step), GEMV tile layout
+    const uint8_t *w8, *w8d;         // e4m3: row-major, tile layout
+    const float* sw;                 // their scale per output row
+    const uint8_t *w4c, *w4e;        // w4: codes and exponent bytes, tile layout
+};
+static std::array<Proj, 4> layer_projs(const LlmLayer& W, int H, int I, int QKV) {
+    return {{{QKV, H, W.wqkv, W.wqkv_d, W.wqkv8, W.wqkv8_d, W.sqkv, W.w4c[0], W.w4e[0]}, {H, H, W.wo, W.wo_d, W.wo8, W.wo8_d, W.so, W.w4c[1], W.w4e[1]},
+             {2 * I, H, W.wgu, W.wgu_d, W.wgu8, W.wgu8_d, W.sgu, W.w4c[2], W.w4e[2]}, {H, I, W.wd, W.wd_d, W.wd8, W.wd8_d, W.sd, W.w4c[3], W.w4e[3]}}};
+}
 struct StcBlock { bf16_t *w1, *n1w, *n1b, *wdw, *n2w, *n2b, *fc1w, *fc1b, *fc2w, *fc2b, *w3, *n3w, *n3b, *wd, *ndw, *ndb; int cin, rd; };
 
 constexpr int PF_MAX = 4;        // equal-length prompts of max_ctx rows one prefill pass can take: the workspaces hold pf_rows() rows, and a pass takes up to PF_MAX_N
@@ -113,7 +126,7 @@ struct trace_ctx {
     int h_next = 0; size_t h_len = 0;
     int spliced_len = 0;
     // decode state
-    bf16_t *dX, *dH, *dQKV, *dO, *dACT, *xlast;   // [16, *]
+    bf16_t *dX, *dH, *dQKV, *dO, *dACT, *xlast;   // [SK_ROWS, *]: one row per sequence of the decode batch; xlast [slots, H]: every KV slot's last prefill hidden row
     float* attn_ws; unsigned int* tickets;
     void* pp_buf = nullptr; size_t pp_bytes = 0;       // frame preprocessing: tap tables + staged rows (grow-only)
     float* sk_ws = nullptr; unsigned int* sk_tickets = nullptr; size_t sk_ws_floats = 0; int sk_ntickets = 0;   // decode GEMV K-chunk partials
@@ -131,7 +144,7 @@ struct trace_ctx {
     int32_t* d_retire = nullptr;       // trace_decode_retire's keep list [SK_ROWS] and scratch rows (allocated at the first retire)
     int32_t h_pos0[SK_ROWS] = {0};     // host copy: the prefill length of every row of the batch (pos_sum after a retire)
     int32_t* d_heads_tmp;                // head id per row for trace_llm_head_logits
-    int B = 0, max_new = 0, eos = -1, has_forced = 0, ntiles = 0, nsplit = 32;
+    int B = 0, max_new = 0, eos = -1, ntiles = 0, nsplit = 32;
     int slot_len[MAX_SLOTS] = {0};
     int fp8 = 0;                       // decoder projections on the fp8 path
     int fp8_wonly = 0;                 // llm_weights_fp8 == 2: the decode GEMVs keep bf16 activations (weight-only; the prefill GEMMs stay W8A8)
@@ -201,7 +214,6 @@ struct trace_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> kev;      // event pool for per-launch brackets (eager mode)
     int kev_used = 0;
-    hipEvent_t gev0 = nullptr, gev1 = nullptr;   // pair recorded from inside the captured graph
     double ksum_ms = 0.0; int ksamples = 0;
     hipEvent_t mev0 = nullptr, mev1 = nullptr;   // bracket of one ViT fc1 GEMM launch per trace_vit_forward (profile == 2)
     double msum_ms = 0.0; int msamples = 0; double mflops = 0.0; int mM = 0;
@@ -536,7 +548,6 @@ static int ctx_create(const trace_config* cfg, int device_id, int kv8, int w4, t
     for (int i = 0; i < trace_ctx::NSTAGE_H; ++i) hipEventCreateWithFlags(&c->h_ev[i], hipEventDisableTiming);
     hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
     hipEventCreate(&c->ev0); hipEventCreate(&c->ev1);
-    hipEventCreate(&c->gev0); hipEventCreate(&c->gev1);
     hipEventCreate(&c->mev0); hipEventCreate(&c->mev1);
     for (auto& e : c->vev) hipEventCreate(&e);
     c->kev.resize(1024);
@@ -556,8 +567,6 @@ extern "C" int trace_ctx_destroy(trace_ctx* c) {
     for (auto& e : c->vev) if (e) hipEventDestroy(e);
     if (c->mev0) hipEventDestroy(c->mev0);
     if (c->mev1) hipEventDestroy(c->mev1);
-    if (c->gev0) hipEventDestroy(c->gev0);
-    if (c->gev1) hipEventDestroy(c->gev1);
     for (void* p : c->allocs) hipFree(p);
     if (c->pp_buf) hipFree(c->pp_buf);
     if (c->h_ring) hipHostFree(c->h_ring);
@@ -1233,11 +1242,10 @@ static int prefill_impl(trace_ctx* c, int slot0, int nb, int L, void* hidden_out
     a.scale = 1.0f / sqrtf((float)HD); a.causal = 1;
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
-        struct { int N, K; const bf16_t* w; const uint8_t* w8; const float* sw; } P[4] = {       // qkv, o, gate|up, down: W[N][K], 16-bit or e4m3 + row scales
-            {QKV, H, W.wqkv, W.wqkv8, W.sqkv}, {H, H, W.wo, W.wo8, W.so}, {2 * I, H, W.wgu, W.wgu8, W.sgu}, {H, I, W.wd, W.wd8, W.sd}};
+        auto P = layer_projs(W, H, I, QKV);           // the row-major copies: 16-bit, or e4m3 + row scales
         if (c->w4)            // this layer's four projections as 16-bit rows (exactly the weights the decode GEMVs widen); the GEMMs below run on them unchanged
             for (int p = 0; p < 4; ++p) {
-                LCHK(launch_dequant_w4(W.w4c[p], W.w4e[p], c->w4_row[p], P[p].K, P[p].N, P[p].K, s));
+                LCHK(launch_dequant_w4(P[p].w4c, P[p].w4e, c->w4_row[p], P[p].K, P[p].N, P[p].K, s));
                 P[p].w = c->w4_row[p];
             }
         // Projection p over n rows: C = A W^T, + R when given (R lies where C does: ldr = ldc).  cols > 0: only the output columns col0 .. col0 + cols - 1.
@@ -1424,6 +1432,24 @@ static StepState step_state(trace_ctx* c, TailRows t = {0, 0}) {
     return st;
 }
 
+// Everything the batch holds per row, each column named ONCE, in the order retire.hip moves them (RetireArgs: 7 of one int, 3 of max_new ints, the 3
+// per-row params, x): the device base as ints, the ints a row, whether the armed mode has the column, the host mirror of the SEATED values (h_pos0 keeps
+// the prefill length: the device column advances).  seat_write, trace_decode_retire and trace_debug_decode_rows walk it: a new one-int column is one
+// line here before out_ids (RETIRE_SMALL + 1 in kernels.h) and its seat value at the same place in seat_write.
+struct RowCol { const char* name; int32_t* dev; int ints; bool on; void* host; };
+constexpr int N_COLS = RETIRE_SMALL + 7;
+static std::array<RowCol, N_COLS> row_cols(trace_ctx* c) {
+    const int W = c->max_new, SP = sizeof(SampleParams) / 4, LP = sizeof(LogitsParams) / 4;
+    const bool pr = c->armed.per_row;
+    auto I = [](auto* p) { return reinterpret_cast<int32_t*>(p); };
+    return {{{"slots", c->d_slots, 1, true, c->h_slots}, {"pos", c->d_pos, 1, true, c->h_pos0}, {"heads", c->d_heads, 1, true, nullptr},
+             {"done", c->d_done, 1, true, nullptr}, {"out_len", c->d_out_len, 1, true, nullptr}, {"row_id", c->d_row_id, 1, true, nullptr},
+             {"step0", c->d_step0, 1, true, c->h_step0},
+             {"out_ids", c->d_out_ids, W, true, nullptr}, {"forced", c->d_forced, W, true, nullptr}, {"logprobs", I(c->d_logprobs), W, c->armed.logprobs, nullptr},
+             {"row_sp", I(c->d_row_sp), SP, pr, c->h_row_sp}, {"row_lp", I(c->d_row_lp), LP, pr, c->h_row_lp}, {"row_max", c->d_row_max, 1, pr, c->h_row_max},
+             {"x", I(c->dX), c->H / 2, true, nullptr}}};
+}
+
 static int head_only(trace_ctx* c, const bf16_t* xn, float* logits_out, hipStream_t s, TailRows t) {
     LCHK(launch_head_logits(xn, c->H, c->wheads, c->H, c->d_heads + t.r0, c->V, c->Tv, c->Sv, c->part_val + (size_t)t.r0 * c->ntiles,
                             c->part_idx + (size_t)t.r0 * c->ntiles, logits_out, t.n, s));
@@ -1523,42 +1549,6 @@ static int qkv_finish_layer(trace_ctx* c, int l, int ks, hipStream_t s, const fl
                              (long)c->slot_stride, (long)c->kv_head_stride, c->ctx_pad, c->d_slots, c->d_pos, c->B, c->NQ, c->NKV, c->rope_cos, c->rope_sin, s);
 }
 
-// One decode step for SKINNY_ROWS < B <= SK_ROWS sequences.  A GEMV that parks its activations in LDS cannot hold more than 64 rows x 1024 k, and
-// its fp32 partial rows would grow with the row count; above 64 rows the four projections are small-M GEMMs on the MFMA tile kernel instead
-// (gemm.hip, 128x128 tiles, weights from the row-major prefill copies): gate|up with the SwiGLU epilogue straight to bf16 — no partial rows,
-// no combine kernel — and qkv / o / down cut along K into gemm_partial_ks() chunks whose fp32 partial rows the same consumers as below sum on
-// load.  The weights (14 GB per step) are then streamed once per 128 tokens instead of once per 64: bytes per token 0.50 -> 0.39 GB at
-// ctx ~2100, where the KV stream (0.27 GB per token) is the larger part.
-static int decode_step_wide(trace_ctx* c, const DecodeRoute& r, float* logits_out, hipStream_t s) {
-    const int H = c->H, I = c->I, QKV = c->QKV, B = c->B;
-    if (c->fp8 || c->w4) return fail(TRACE_ERR_STATE, "the fp8 and w4 weight paths decode at most 64 sequences together");
-    const int wt = g_tune.decode_gemm_tiled;
-    auto pgemm = [&](const bf16_t* A, int lda, const bf16_t* Wrow, const bf16_t* Wtile, int ldw, int N, int K, int ks) -> int {
-        GemmArgs g{A, lda, (wt & 1) ? Wtile : Wrow, ldw, nullptr, 0, nullptr, nullptr, 0, B, N, K, nullptr, 0, nullptr, nullptr, 0, c->sk_ws, ks, (wt & 1) ? wt : 0};
-        if ((size_t)ks * SK_ROWS * N > c->sk_ws_floats) return fail(TRACE_ERR_STATE, "partial-row workspace too small");
-        return gemm_checked(g, EPI_PARTIAL, s, "partial GEMM");
-    };
-    LCHK(launch_rmsnorm(c->dX, H, c->dH, H, c->llm[0].rms1, B, H, c->c.rms_eps, s));
-    for (int l = 0; l < c->NL; ++l) {
-        const LlmLayer& W = c->llm[l];
-        TRY(pgemm(c->dH, H, W.wqkv, W.wqkv_d, H, QKV, H, r.ks_q));
-        if (r.qkv_finish) LCHK(qkv_finish_layer(c, l, r.ks_q, s));
-        {   // bracketed: the layer-0 decode attention, which streams the batch's whole KV cache of that layer
-            StepBracket br(c, l, 3, s);
-            if (br.e1) c->kbytes_sum += attn_kv_bytes(c);
-            LCHK(attn_decode_layer(c, l, r, c->sk_ws, s));
-        }
-        TRY(pgemm(c->dO, H, W.wo, W.wo_d, H, H, H, r.ks_o));
-        LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s));
-        GemmArgs gu{c->dH, H, (wt & 1) ? W.wgu_d : W.wgu, H, c->dACT, I, nullptr, nullptr, 0, B, 2 * I, H, (wt & 1) ? nullptr : g_gemm_trace, 0, nullptr, nullptr, 0, nullptr, 0, (wt & 1) ? wt : 0};
-        TRY(gemm_checked(gu, EPI_SWIGLU, s, "gate|up GEMM"));
-        TRY(pgemm(c->dACT, I, W.wd, W.wd_d, I, H, I, r.ks_d));
-        const bf16_t* nw = l + 1 < c->NL ? c->llm[l + 1].rms1 : c->final_norm;
-        LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s));
-    }
-    return head_and_select(c, c->dH, 1, logits_out, s);
-}
-
 // One decode step for 1..4 sequences (the reference drivers' own call shape is 1): the two "sum the partial rows + residual -> new residual, RMSNorm"
 // kernels of a layer are folded into the GEMVs that consume their output (decode.hip, SkinnyPro), and (round 4) the SwiGLU combine into the down
 // GEMV — 4 launches per layer instead of 7:
@@ -1571,22 +1561,23 @@ static int decode_step_fused(trace_ctx* c, const DecodeRoute& r, float* logits_o
     bf16_t *xa = c->dX, *xb = c->dX2;             // current / next residual rows
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
-        LCHK(launch_skinny_gemm_fused_norm(l ? c->sk_ws : nullptr, l ? r.ks_d : 0, xa, H, xb, H, W.rms1, c->c.rms_eps, W.wqkv_d, B, QKV, H, c->sk_ws2,
+        const auto P = layer_projs(W, H, I, QKV);      // the bf16 tile copies
+        LCHK(launch_skinny_gemm_fused_norm(l ? c->sk_ws : nullptr, l ? r.ks_d : 0, xa, H, xb, H, W.rms1, c->c.rms_eps, P[0].wd, B, QKV, H, c->sk_ws2,
                                            c->sk_ws_floats, s));
         std::swap(xa, xb);
         if (r.qkv_finish) LCHK(qkv_finish_layer(c, l, r.ks_q, s, c->sk_ws2));      // (the e4m3 KV cache only: this step's 16-bit form always fuses the append)
         LCHK(attn_decode_layer(c, l, r, c->sk_ws2, s));
-        LCHK(launch_skinny_gemm(c->dO, H, W.wo_d, H, nullptr, H, nullptr, 0, B, H, H, EPI_PARTIAL, 1, SKWS(c), s));
+        LCHK(launch_skinny_gemm(c->dO, H, P[1].wd, H, nullptr, H, nullptr, 0, B, H, H, EPI_PARTIAL, 1, SKWS(c), s));
         {
             StepBracket br(c, l, 2, s);
-            LCHK(launch_skinny_gemm_fused_norm(c->sk_ws, r.ks_o, xa, H, xb, H, W.rms2, c->c.rms_eps, W.wgu_d, B, 2 * I, H, c->sk_ws2, c->sk_ws_floats, s));
+            LCHK(launch_skinny_gemm_fused_norm(c->sk_ws, r.ks_o, xa, H, xb, H, W.rms2, c->c.rms_eps, P[2].wd, B, 2 * I, H, c->sk_ws2, c->sk_ws_floats, s));
         }
         std::swap(xa, xb);
         if (g_tune.decode_fuse_swiglu) {        // SwiGLU folded into the down GEMV's parking step (round 4, bit-identical to swiglu_combine + GEMV): 4 launches per layer
-            LCHK(launch_skinny_gemm_fused_swiglu(c->sk_ws2, r.ks_g, W.wd_d, B, H, I, c->sk_ws, c->sk_ws_floats, s));
+            LCHK(launch_skinny_gemm_fused_swiglu(c->sk_ws2, r.ks_g, P[3].wd, B, H, I, c->sk_ws, c->sk_ws_floats, s));
         } else {
             LCHK(launch_swiglu_combine(c->sk_ws2, r.ks_g, 2 * I, c->dACT, I, B, s));
-            LCHK(launch_skinny_gemm(c->dACT, I, W.wd_d, I, nullptr, H, nullptr, 0, B, H, I, EPI_PARTIAL, 1, SKWS(c), s));
+            LCHK(launch_skinny_gemm(c->dACT, I, P[3].wd, I, nullptr, H, nullptr, 0, B, H, I, EPI_PARTIAL, 1, SKWS(c), s));
         }
     }
     // an even number of fused GEMVs: the residual rows are back in dX; the last layer's down partials + residual -> final norm -> heads
@@ -1594,48 +1585,73 @@ static int decode_step_fused(trace_ctx* c, const DecodeRoute& r, float* logits_o
     return head_and_select(c, c->dH, 1, logits_out, s);
 }
 
-// One decode step for up to SKINNY_ROWS sequences, on any kind of weights.
-static int decode_step_skinny(trace_ctx* c, const DecodeRoute& r, float* logits_out, hipStream_t s) {
+// One decode step on partial rows, in its two forms.  Every projection leaves fp32 k-chunk partial rows in sk_ws and its consumer sums them on load (an
+// in-kernel merge costs 5-8 us of dependent round trips per GEMV): qkv -> attention (RoPE + cache append + attention) -> o -> [sum + residual -> new
+// residual, RMSNorm] -> gate|up -> [sum, SwiGLU] -> down -> [sum + residual, next layer's / the final RMSNorm].
+//   The GEMV step (r.step == 1), up to SKINNY_ROWS sequences on any kind of weights: a projection is a GEMV of the step's kind over the tile copies.
+//   The wide step (r.step == 3), SKINNY_ROWS < B <= SK_ROWS sequences, 16-bit weights.  A GEMV that parks its activations in LDS cannot hold more than
+//     64 rows x 1024 k, and its fp32 partial rows would grow with the row count; above 64 rows the projections are small-M GEMMs on the MFMA tile kernel
+//     instead (gemm.hip, 128x128 tiles, weights from the row-major prefill copies, or the tile copies by decode.gemm_tiled), qkv / o / down cut along K
+//     into gemm_partial_ks() chunks.  The weights (14 GB per step) are then streamed once per 128 tokens instead of once per 64: bytes per token
+//     0.50 -> 0.39 GB at ctx ~2100, where the KV stream (0.27 GB per token) is the larger part.
+// The two differ in two places, both below: what gate|up is, and which launch takes bracket bit 1.
+static int decode_step_rows(trace_ctx* c, const DecodeRoute& r, float* logits_out, hipStream_t s) {
     const int H = c->H, I = c->I, QKV = c->QKV, B = c->B;
-    // Every GEMV leaves fp32 k-chunk partial rows in sk_ws and its consumer sums them on load (an in-kernel merge costs
-    // 5-8 us of dependent round trips per GEMV): qkv -> attention (RoPE + cache append + attention) -> o -> [sum + residual
-    // -> new residual, RMSNorm] -> gate|up -> [sum, SwiGLU] -> down -> [sum + residual, next layer's / the final RMSNorm].
-    const bool wo = r.kind == SK_W8A16;              // weight-only decode GEMVs: bf16 activations straight from dH / dO / dACT, no quantiser launches
-    const bool f8 = r.kind == SK_W8A8;
-    // One projection of the step (p: 0 qkv, 1 o, 2 gate|up, 3 down), X [B, K] -> partial rows in sk_ws, on the step's kind of weights: the w4 tile copy (codes
-    // and exponent bytes) with bf16 activations, bf16 tile copies (Wd), or the e4m3 tile copy (W8d, scales sw) with bf16 activations (weight-only) or with
-    // activations quantised row-wise first (quant_rows_fp8: [B, K] bf16 -> e4m3 + per-row scale).  The normed hidden rows dH arrive already quantised
-    // (dH8 / dsh) from add_rmsnorm; only the step's first norm needs the quantiser.  Partial rows, their consumers and the attention are the bf16 path's.
-    auto gemv = [&](const bf16_t* X, const LlmLayer& W, int p, int N, int K) -> int {
-        if (r.kind == SK_W4A16) return launch_skinny_w4(X, K, W.w4c[p], W.w4e[p], B, N, K, c->sk_ws, c->sk_ws_floats, s);
-        const bf16_t* Wd = p == 0 ? W.wqkv_d : p == 1 ? W.wo_d : p == 2 ? W.wgu_d : W.wd_d;
-        const uint8_t* W8d = p == 0 ? W.wqkv8_d : p == 1 ? W.wo8_d : p == 2 ? W.wgu8_d : W.wd8_d;
-        const float* sw = p == 0 ? W.sqkv : p == 1 ? W.so : p == 2 ? W.sgu : W.sd;
-        if (wo) return launch_skinny_w8(X, K, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
-        if (!f8) return launch_skinny_gemm(X, K, Wd, K, nullptr, N, nullptr, 0, B, N, K, EPI_PARTIAL, 1, SKWS(c), s);
-        if (X == c->dH) return launch_skinny_fp8(c->dH8, K, c->dsh, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
-        const int rc = launch_quant_rows_fp8(X, K, c->dA8, K, c->dsa, B, K, s);
-        return rc != TRACE_OK ? rc : launch_skinny_fp8(c->dA8, K, c->dsa, W8d, sw, B, N, K, c->sk_ws, c->sk_ws_floats, s);
+    const bool wide = r.step == 3;
+    if (wide && (c->fp8 || c->w4)) return fail(TRACE_ERR_STATE, "the fp8 and w4 weight paths decode at most 64 sequences together");
+    const int wt = g_tune.decode_gemm_tiled;
+    const bool f8 = r.kind == SK_W8A8;               // activations quantised row-wise: dH arrives quantised (dH8 / dsh) from add_rmsnorm, only the step's first norm needs the quantiser
+    const int ks[4] = {r.ks_q, r.ks_o, r.ks_g, r.ks_d};
+    std::array<Proj, 4> P{};
+    // Projection p of the layer in P, X [B, K] -> partial rows in sk_ws.  Wide: the partial GEMM.  Else the GEMV of the step's kind: the w4 tile copy (codes and
+    // exponent bytes) with bf16 activations, the bf16 tile copy, or the e4m3 tile copy with bf16 activations (weight-only) or with activations quantised
+    // first (quant_rows_fp8: [B, K] bf16 -> e4m3 + per-row scale; the normed rows dH are there already).
+    auto proj = [&](int p, const bf16_t* X) -> int {
+        const int N = P[p].N, K = P[p].K;
+        if (wide) {
+            GemmArgs g{X, K, (wt & 1) ? P[p].wd : P[p].w, K, nullptr, 0, nullptr, nullptr, 0, B, N, K, nullptr, 0, nullptr, nullptr, 0, c->sk_ws, ks[p], (wt & 1) ? wt : 0};
+            if ((size_t)ks[p] * SK_ROWS * N > c->sk_ws_floats) return fail(TRACE_ERR_STATE, "partial-row workspace too small");
+            return gemm_checked(g, EPI_PARTIAL, s, "partial GEMM");
+        }
+        if (r.kind == SK_W4A16) LCHK(launch_skinny_w4(X, K, P[p].w4c, P[p].w4e, B, N, K, c->sk_ws, c->sk_ws_floats, s));
+        else if (r.kind == SK_W8A16) LCHK(launch_skinny_w8(X, K, P[p].w8d, P[p].sw, B, N, K, c->sk_ws, c->sk_ws_floats, s));
+        else if (!f8) LCHK(launch_skinny_gemm(X, K, P[p].wd, K, nullptr, N, nullptr, 0, B, N, K, EPI_PARTIAL, 1, SKWS(c), s));
+        else if (X == c->dH) LCHK(launch_skinny_fp8(c->dH8, K, c->dsh, P[p].w8d, P[p].sw, B, N, K, c->sk_ws, c->sk_ws_floats, s));
+        else {
+            LCHK(launch_quant_rows_fp8(X, K, c->dA8, K, c->dsa, B, K, s));
+            LCHK(launch_skinny_fp8(c->dA8, K, c->dsa, P[p].w8d, P[p].sw, B, N, K, c->sk_ws, c->sk_ws_floats, s));
+        }
+        return TRACE_OK;
     };
     LCHK(launch_rmsnorm(c->dX, H, c->dH, H, c->llm[0].rms1, B, H, c->c.rms_eps, s));
     if (f8) LCHK(launch_quant_rows_fp8(c->dH, H, c->dH8, H, c->dsh, B, H, s));
     for (int l = 0; l < c->NL; ++l) {
         const LlmLayer& W = c->llm[l];
+        P = layer_projs(W, H, I, QKV);
         // (fusing the RMSNorm into the GEMV itself was tried: re-scaling the same activations in every workgroup cost
         //  more than a row kernel — 65 us vs 52 + 6 us for the gate|up GEMV)
-        LCHK(gemv(c->dH, W, 0, QKV, H));
+        TRY(proj(0, c->dH));
         if (r.qkv_finish) LCHK(qkv_finish_layer(c, l, r.ks_q, s));
-        LCHK(attn_decode_layer(c, l, r, c->sk_ws, s));
-        LCHK(gemv(c->dO, W, 1, H, H));
+        if (wide) {     // bracket bit 1, wide: the layer-0 decode attention, which streams the batch's whole KV cache of that layer
+            StepBracket br(c, l, 3, s);
+            if (br.e1) c->kbytes_sum += attn_kv_bytes(c);
+            LCHK(attn_decode_layer(c, l, r, c->sk_ws, s));
+        } else LCHK(attn_decode_layer(c, l, r, c->sk_ws, s));
+        TRY(proj(1, c->dO));
         LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_o, c->dX, H, c->dX, H, W.rms2, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
-        {   // bracketed: the layer-0 gate|up GEMV (fp8: the bracket spans what the projection launches)
-            StepBracket br(c, l, 1, s);
-            LCHK(gemv(c->dH, W, 2, 2 * I, H));
+        if (wide) {     // gate|up with the SwiGLU epilogue straight to bf16: no partial rows, no combine kernel
+            GemmArgs gu{c->dH, H, (wt & 1) ? P[2].wd : P[2].w, H, c->dACT, I, nullptr, nullptr, 0, B, 2 * I, H, (wt & 1) ? nullptr : g_gemm_trace, 0, nullptr, nullptr, 0, nullptr, 0, (wt & 1) ? wt : 0};
+            TRY(gemm_checked(gu, EPI_SWIGLU, s, "gate|up GEMM"));
+        } else {
+            {   // bracket bit 1, GEMV: the layer-0 gate|up GEMV (fp8: the bracket spans what the projection launches)
+                StepBracket br(c, l, 1, s);
+                TRY(proj(2, c->dH));
+            }
+            // (SwiGLU inside the gate|up GEMV at batch <= 16 — one K chunk, no combine kernel — measured 3.73 vs 3.5 ms per batch-1 step: its 224
+            //  workgroups leave 32 CUs without a weight stream)
+            LCHK(launch_swiglu_combine(c->sk_ws, r.ks_g, 2 * I, c->dACT, I, B, s));
         }
-        // (SwiGLU inside the gate|up GEMV at batch <= 16 — one K chunk, no combine kernel — measured 3.73 vs 3.5 ms per batch-1 step: its 224
-        //  workgroups leave 32 CUs without a weight stream)
-        LCHK(launch_swiglu_combine(c->sk_ws, r.ks_g, 2 * I, c->dACT, I, B, s));
-        LCHK(gemv(c->dACT, W, 3, H, I));
+        TRY(proj(3, c->dACT));
         const bf16_t* nw = l + 1 < c->NL ? c->llm[l + 1].rms1 : c->final_norm;
         LCHK(launch_add_rmsnorm(c->sk_ws, r.ks_d, c->dX, H, c->dX, H, nw, c->dH, H, B, H, c->c.rms_eps, s, f8 ? c->dH8 : nullptr, f8 ? c->dsh : nullptr));
     }
@@ -1646,7 +1662,7 @@ static int decode_step_skinny(trace_ctx* c, const DecodeRoute& r, float* logits_
 static int decode_step(trace_ctx* c, float* logits_out, hipStream_t s) {
     DecodeRoute r = decode_route(c->B, c->w4 ? 3 : c->fp8 ? 1 + c->fp8_wonly : 0, c->H, c->I, c->QKV, g_tune);    // (fp8 contexts: at most 64 rows, checked at begin)
     if (c->kv8) r.qkv_finish = true;                 // the e4m3 KV cache always appends with a launch of its own (qkv_finish_kv8), in every step body
-    return r.step == 3 ? decode_step_wide(c, r, logits_out, s) : r.step == 2 ? decode_step_fused(c, r, logits_out, s) : decode_step_skinny(c, r, logits_out, s);
+    return r.step == 2 ? decode_step_fused(c, r, logits_out, s) : decode_step_rows(c, r, logits_out, s);
 }
 
 // The batch the NEXT trace_decode_begin starts holds the same K / V rows at positions below `rows` in every slot, and `slot` is one that holds them: the
@@ -1667,13 +1683,67 @@ static const char* row_forced_bad(const trace_ctx* c, const int32_t* forced, int
 static bool logits_armed(const LogitsParams& p) { return p.penalty != 1.f || p.ngram != 0 || p.min_new != 0; }
 static bool constraint_bans(const ConstrainTable& t) { return t.n_bad || t.n_suppress || t.n_begin; }
 
+static int decode_cap(const trace_ctx* c) { return c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS; }    // sequences that decode together on the context's kind of weights
+
+// What trace_decode_begin and trace_decode_admit(_ex) share, in two halves with the entry point's own checks and state between them.
+// seat_check: n prefilled sequences may take rows of the batch — slot in range and prefilled, no slot twice, head 0..2, the per-row params (rows at `stride`
+// bytes; null: a batch without them) converted, prefill + max_new <= max_ctx, forced ids against the rows' processors.  who / who_rows prefix the messages.
+struct Seated { int32_t pos[SK_ROWS]; std::vector<SampleParams> sp; std::vector<LogitsParams> lp; std::vector<int32_t> mx; bool procs = false; };
+static int seat_check(trace_ctx* c, const std::string& who, const std::string& who_rows, int n, const int32_t* slots, const int32_t* heads, const int32_t* forced,
+                      const trace_row_params* rows, size_t stride, int max_new, Seated& q) {
+    q.sp.resize(rows ? n : 0); q.lp.resize(rows ? n : 0); q.mx.resize(rows ? n : 0);
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= c->max_B || c->slot_len[slots[i]] <= 0) return fail(TRACE_ERR_STATE, who + "slot not prefilled");
+        for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(TRACE_ERR_ARG, who + "duplicate slot");
+        if (heads[i] < 0 || heads[i] > 2) return fail(TRACE_ERR_ARG, who + "head must be 0, 1 or 2");
+        q.pos[i] = c->slot_len[slots[i]];
+        if (rows) {
+            const trace_row_params* r = reinterpret_cast<const trace_row_params*>(reinterpret_cast<const char*>(rows) + (size_t)i * stride);   // (the caller's stride)
+            if (r->size != rows[0].size) return fail(TRACE_ERR_ARG, who_rows + "every trace_row_params must carry the same size");
+            if (const char* e = row_params_convert(*r, max_new, q.sp[i], q.lp[i], q.mx[i])) return fail(TRACE_ERR_ARG, who_rows + "row " + std::to_string(i) + ": " + e);
+            q.procs = q.procs || logits_armed(q.lp[i]);       // a row brings armed logits processors
+        }
+        if (q.pos[i] + (rows ? q.mx[i] : max_new) > c->max_ctx) return fail(TRACE_ERR_ARG, who + "prefill + max_new_tokens exceeds max_ctx");
+    }
+    if (const char* e = rows ? row_forced_bad(c, forced, n, max_new, q.lp.data(), q.mx.data()) : nullptr) return fail(TRACE_ERR_ARG, who_rows + e);
+    return TRACE_OK;
+}
+// seat_write: the checked sequences take rows [r0, r0 + n) — every column of row_cols gets its seat value, the rows' last prefill hidden rows are gathered,
+// the head and the selection of their step 0 run on those rows alone with no position advance, and then the host mirrors and pos_sum follow.
+static int seat_write(trace_ctx* c, int r0, int n, const int32_t* slots, const int32_t* heads, const int32_t* row_ids, const int32_t* forced, int origin,
+                      const Seated& q, float* logits_out, hipStream_t s) {
+    int32_t zero[SK_ROWS] = {0}, org[SK_ROWS];
+    for (int i = 0; i < n; ++i) org[i] = origin;
+    // seat values in row_cols' order: host rows to copy, else the byte the ints are filled with (forced: -1 = not forced; logprobs: entries past a row's
+    // length stay 0.0), else (x, fill < 0) nothing: the selection below writes it
+    const struct { const void* rows; int fill; } v[N_COLS] = {{slots}, {q.pos}, {heads}, {zero}, {zero}, {row_ids}, {org}, {nullptr, 0}, {forced, 0xff}, {nullptr, 0},
+                                                              {q.sp.data()}, {q.lp.data()}, {q.mx.data()}, {nullptr, -1}};
+    const auto col = row_cols(c);
+    for (int k = 0; k < N_COLS; ++k) {
+        int32_t* dst = col[k].dev + (size_t)r0 * col[k].ints;
+        const size_t bytes = (size_t)n * col[k].ints * 4;
+        if (!col[k].on) continue;
+        if (v[k].rows) HIPCHK(hipMemcpyAsync(dst, v[k].rows, bytes, hipMemcpyHostToDevice, s));
+        else if (v[k].fill >= 0) HIPCHK(hipMemsetAsync(dst, v[k].fill, bytes, s));
+    }
+    bf16_t* h = c->dH + (size_t)r0 * c->H;
+    for (int i = 0; i < n; ++i)
+        HIPCHK(hipMemcpyAsync(h + (size_t)i * c->H, c->xlast + (size_t)slots[i] * c->H, (size_t)c->H * 2, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));     // the host arrays above, and the caller's, must outlive the async copies
+    TRY(head_and_select(c, h, 0, logits_out, s, TailRows{r0, n}));
+    for (int k = 0; k < N_COLS; ++k)
+        if (col[k].on && col[k].host) memcpy(static_cast<char*>(col[k].host) + (size_t)r0 * col[k].ints * 4, v[k].rows, (size_t)n * col[k].ints * 4);
+    for (int i = 0; i < n; ++i) c->pos_sum += q.pos[i];
+    return TRACE_OK;
+}
+
 extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, const int32_t* heads, int max_new, int eos,
                                   const int32_t* forced, float* logits_out, void* stream) {
     if (!c || !c->finalized) return fail(TRACE_ERR_STATE, "context not finalized");
     // the per-row request (trace_decode_set_row_params) is this call's alone: taken here, whatever the call then answers
     std::vector<trace_row_params> want_rows;
     want_rows.swap(c->want_rows);
-    if (!slots || !heads || B < 1 || B > c->max_B || B > (c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS)) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS) + " sequences decode together)");
+    if (!slots || !heads || B < 1 || B > c->max_B || B > decode_cap(c)) return fail(TRACE_ERR_ARG, "bad batch (at most " + std::to_string(decode_cap(c)) + " sequences decode together)");
     if (max_new < 1 || max_new > c->c.max_new_tokens) return fail(TRACE_ERR_ARG, "max_new exceeds capacity");
     hipStream_t s = (hipStream_t)stream;
     // the shared-prefix request is this call's alone: taken here, whatever the call then answers (one sequence shares with nobody)
@@ -1681,75 +1751,39 @@ extern "C" int trace_decode_begin(trace_ctx* c, const int32_t* slots, int B, con
     c->sh_want_slot = -1; c->sh_want_rows = 0;
     if (sh_rows > 0 && c->slot_len[sh_slot] < sh_rows) return fail(TRACE_ERR_STATE, "the shared slot holds fewer rows than the shared prefix");
     const bool per_row = !want_rows.empty();
-    std::vector<SampleParams> rsp(per_row ? B : 0);
-    std::vector<LogitsParams> rlp(per_row ? B : 0);
-    std::vector<int32_t> rmx(per_row ? B : 0);
-    if (per_row) {
-        if (c->host_mode) return fail(TRACE_ERR_STATE, "per-row params are not available in host-select mode");
-        if ((int)want_rows.size() != B) return fail(TRACE_ERR_ARG, "trace_decode_set_row_params gave " + std::to_string(want_rows.size()) + " rows, the batch has " + std::to_string(B));
-        for (int b = 0; b < B; ++b)
-            if (const char* e = row_params_convert(want_rows[b], max_new, rsp[b], rlp[b], rmx[b])) return fail(TRACE_ERR_ARG, "row " + std::to_string(b) + ": " + e);
-    }
-    int32_t pos[SK_ROWS], zero[SK_ROWS] = {0}, iota[SK_ROWS];
+    if (per_row && c->host_mode) return fail(TRACE_ERR_STATE, "per-row params are not available in host-select mode");
+    if (per_row && (int)want_rows.size() != B) return fail(TRACE_ERR_ARG, "trace_decode_set_row_params gave " + std::to_string(want_rows.size()) + " rows, the batch has " + std::to_string(B));
+    Seated q;
+    TRY(seat_check(c, "", "", B, slots, heads, forced, per_row ? want_rows.data() : nullptr, sizeof(trace_row_params), max_new, q));
+    int32_t iota[SK_ROWS];
     for (int b = 0; b < B; ++b) {
         iota[b] = b;
-        if (slots[b] < 0 || slots[b] >= c->max_B || c->slot_len[slots[b]] <= 0) return fail(TRACE_ERR_STATE, "slot not prefilled");
         if (c->slot_len[slots[b]] < sh_rows) return fail(TRACE_ERR_ARG, "a sequence is shorter than the shared prefix");
-        if (heads[b] < 0 || heads[b] > 2) return fail(TRACE_ERR_ARG, "head must be 0, 1 or 2");
-        pos[b] = c->slot_len[slots[b]];
-        if (pos[b] + (per_row ? rmx[b] : max_new) > c->max_ctx) return fail(TRACE_ERR_ARG, "prefill + max_new_tokens exceeds max_ctx");
-        for (int b2 = 0; b2 < b; ++b2) if (slots[b2] == slots[b]) return fail(TRACE_ERR_ARG, "duplicate slot");
     }
-    if (per_row) {
-        if (const char* e = row_forced_bad(c, forced, B, max_new, rlp.data(), rmx.data())) return fail(TRACE_ERR_ARG, e);
-    } else if (forced && (c->want.process || c->want.stop) && !c->host_mode)
+    if (!per_row && forced && (c->want.process || c->want.stop) && !c->host_mode)
         return fail(TRACE_ERR_ARG, "logits processors / constraints (trace_decode_set_logits_params, trace_decode_set_constraints) with forced ids: the "
                                    "history is the recorded ids, not the fed ones");
-    c->B = B; c->max_new = max_new; c->eos = eos; c->has_forced = forced != nullptr;
+    c->B = 0; c->max_new = max_new; c->eos = eos;         // (no batch until the rows are seated)
     c->sh_slot = sh_rows > 0 ? sh_slot : -1; c->sh_rows = sh_rows;
-    c->pos_sum = 0;
-    for (int b = 0; b < B; ++b) { c->pos_sum += pos[b]; c->h_pos0[b] = pos[b]; }
-    HIPCHK(hipMemcpyAsync(c->d_slots, slots, B * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_row_id, iota, B * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_pos, pos, B * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_heads, heads, B * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_done, zero, B * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_out_len, zero, B * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_step, zero, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_step0, zero, B * 4, hipMemcpyHostToDevice, s));
-    for (int b = 0; b < B; ++b) { c->h_step0[b] = 0; c->h_slots[b] = slots[b]; }
-    c->admitted = 0;
-    HIPCHK(hipMemsetAsync(c->d_out_ids, 0, (size_t)B * max_new * 4, s));
-    const int32_t prm[3] = {max_new, eos, c->host_mode};
-    HIPCHK(hipMemcpyAsync(c->d_params, prm, 12, hipMemcpyHostToDevice, s));
+    c->pos_sum = 0; c->admitted = 0; c->fed = 0; c->steps_done = 0;
     // host-select mode arms nothing: the host holds the logits and calls trace_op_logits_process / trace_op_sample / trace_op_token_logprob on them
     c->armed = c->host_mode ? TailMode{} : c->want;
     if (per_row) {      // the batch-wide sampling and logits params are ignored: every row brings its own; constraints and log-probabilities stay the batch's
         TailMode m;
         m.per_row = true; m.logprobs = c->want.logprobs; m.stop = c->ctab.n_stop != 0;
-        m.process = constraint_bans(c->ctab);
-        for (int b = 0; b < B; ++b) {
-            c->h_row_sp[b] = rsp[b]; c->h_row_lp[b] = rlp[b]; c->h_row_max[b] = rmx[b];
-            m.process = m.process || logits_armed(rlp[b]);
-        }
+        m.process = constraint_bans(c->ctab) || q.procs;
         c->armed = m;
-        HIPCHK(hipMemcpyAsync(c->d_row_sp, c->h_row_sp, B * sizeof(SampleParams), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_row_lp, c->h_row_lp, B * sizeof(LogitsParams), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_row_max, c->h_row_max, B * 4, hipMemcpyHostToDevice, s));
     }
+    const int32_t zero = 0, prm[3] = {max_new, eos, c->host_mode};
+    HIPCHK(hipMemcpyAsync(c->d_step, &zero, 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_params, prm, 12, hipMemcpyHostToDevice, s));
     if (c->armed.sample) HIPCHK(hipMemcpyAsync(c->d_sparams, &c->samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
-    if (c->armed.logprobs) HIPCHK(hipMemsetAsync(c->d_logprobs, 0, (size_t)B * max_new * 4, s));    // entries past a row's length stay 0.0
     if (c->armed.process) HIPCHK(hipMemcpyAsync(c->d_lgparams, &c->lgp, sizeof(LogitsParams), hipMemcpyHostToDevice, s));
     if (c->armed.process || c->armed.stop || per_row)       // the whole table, or the header alone when it is empty (the processors' kernel reads its four counts; a per-row batch may arm them at an admission)
         HIPCHK(hipMemcpyAsync(c->d_ctab, &c->ctab, constraints_on(c->ctab) ? sizeof(ConstrainTable) : 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    c->fed = 0; c->steps_done = 0;
-    if (forced) HIPCHK(hipMemcpyAsync(c->d_forced, forced, (size_t)B * max_new * 4, hipMemcpyHostToDevice, s));
-    else HIPCHK(hipMemsetAsync(c->d_forced, 0xff, (size_t)B * max_new * 4, s));      // -1 = not forced
-    // gather the prefill hidden rows of the chosen slots into dH, then head + select (no position advance)
-    for (int b = 0; b < B; ++b)
-        HIPCHK(hipMemcpyAsync(c->dH + (size_t)b * c->H, c->xlast + (size_t)slots[b] * c->H, (size_t)c->H * 2, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));     // host stack arrays above must outlive the async copies
-    return head_and_select(c, c->dH, 0, logits_out, s);
+    TRY(seat_write(c, 0, B, slots, heads, iota, forced, 0, q, logits_out, s));
+    c->B = B;
+    return TRACE_OK;
 }
 
 extern "C" int trace_decode_steps(trace_ctx* c, int n, int use_graph, float* logits_out, void* stream) {
@@ -1850,17 +1884,20 @@ extern "C" int trace_decode_retire(trace_ctx* c, const int32_t* keep, int n_keep
     hipStream_t s = (hipStream_t)stream;
     const size_t row_ints = retire_row_ints(c->c.max_new_tokens, c->H);
     if (!c->d_retire) TRY(dalloc(c, &c->d_retire, SK_ROWS + SK_ROWS * row_ints));
+    const auto col = row_cols(c);
+    auto dev = [&](int k) { return col[k].on ? col[k].dev : nullptr; };      // (null where the armed mode has no such column)
     RetireArgs a{};
-    a.small[0] = c->d_slots; a.small[1] = c->d_pos; a.small[2] = c->d_heads; a.small[3] = c->d_done; a.small[4] = c->d_out_len; a.small[5] = c->d_row_id; a.small[6] = c->d_step0;
-    a.wide[0] = c->d_out_ids; a.wide[1] = c->d_forced; a.wide[2] = c->armed.logprobs ? reinterpret_cast<int32_t*>(c->d_logprobs) : nullptr;
+    for (int k = 0; k < RETIRE_SMALL; ++k) a.small[k] = dev(k);
+    for (int k = 0; k < 3; ++k) { a.wide[k] = dev(RETIRE_SMALL + k); a.rowp[k] = dev(RETIRE_SMALL + 3 + k); }
     a.x = c->dX; a.H = c->H; a.max_new = c->max_new;
-    if (c->armed.per_row) { a.rowp[0] = reinterpret_cast<int32_t*>(c->d_row_sp); a.rowp[1] = reinterpret_cast<int32_t*>(c->d_row_lp); a.rowp[2] = c->d_row_max; }
     HIPCHK(hipMemcpyAsync(c->d_retire, keep, (size_t)n_keep * 4, hipMemcpyHostToDevice, s));
     LCHK(launch_retire(a, c->d_retire, n_keep, B, c->d_retire + SK_ROWS, s));
     HIPCHK(hipStreamSynchronize(s));                 // the caller's keep list must outlive the async copy
+    for (const RowCol& k : col)                      // the host mirrors follow (keep[i] >= i: read before overwritten)
+        for (int i = 0; k.on && k.host && i < n_keep; ++i)
+            memmove(static_cast<char*>(k.host) + (size_t)i * k.ints * 4, static_cast<char*>(k.host) + (size_t)keep[i] * k.ints * 4, (size_t)k.ints * 4);
     c->pos_sum = 0;
-    for (int i = 0; i < n_keep; ++i) { c->h_pos0[i] = c->h_pos0[keep[i]]; c->h_step0[i] = c->h_step0[keep[i]]; c->h_slots[i] = c->h_slots[keep[i]]; c->pos_sum += c->h_pos0[i];
-                                       c->h_row_sp[i] = c->h_row_sp[keep[i]]; c->h_row_lp[i] = c->h_row_lp[keep[i]]; c->h_row_max[i] = c->h_row_max[keep[i]]; }      // (keep[i] >= i: read before overwritten)
+    for (int i = 0; i < n_keep; ++i) c->pos_sum += c->h_pos0[i];
     c->B = n_keep;
     if (n_keep == 1) { c->sh_slot = -1; c->sh_rows = 0; }      // one sequence shares with nobody (as at trace_decode_begin): its own slot holds the same rows
     return TRACE_OK;
@@ -1886,62 +1923,23 @@ extern "C" int trace_decode_admit_ex(trace_ctx* c, const int32_t* slots, int n, 
     const bool per_row = c->armed.per_row;
     if (per_row && !rows) return fail(TRACE_ERR_STATE, "trace_decode_admit: the running batch was begun with per-row params; admit into it through trace_decode_admit_ex with rows");
     if (!per_row && rows) return fail(TRACE_ERR_STATE, "trace_decode_admit_ex: the running batch was begun without per-row params (trace_decode_set_row_params)");
-    const int B = c->B, cap = std::min(c->max_B, c->fp8 || c->w4 ? SKINNY_ROWS : SK_ROWS), max_new = c->max_new;
+    const int B = c->B, cap = std::min(c->max_B, decode_cap(c));
     if (n > cap - B) return fail(TRACE_ERR_ARG, "trace_decode_admit: " + std::to_string(B) + " running + " + std::to_string(n) + " admitted rows exceed the cap (at most " + std::to_string(cap) + " sequences decode together)");
-    int32_t pos[SK_ROWS], zero[SK_ROWS] = {0}, org[SK_ROWS];
-    std::vector<SampleParams> rsp(per_row ? n : 0);
-    std::vector<LogitsParams> rlp(per_row ? n : 0);
-    std::vector<int32_t> rmx(per_row ? n : 0);
     if (per_row && rows[0].size < (int32_t)sizeof(trace_row_params)) return fail(TRACE_ERR_ARG, "trace_row_params::size is smaller than this library's struct");
+    Seated q;
+    TRY(seat_check(c, "trace_decode_admit: ", "trace_decode_admit_ex: ", n, slots, heads, forced, rows, per_row ? (size_t)rows[0].size : 0, c->max_new, q));
     for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= c->max_B || c->slot_len[slots[i]] <= 0) return fail(TRACE_ERR_STATE, "trace_decode_admit: slot not prefilled");
         for (int b = 0; b < B; ++b) if (c->h_slots[b] == slots[i]) return fail(TRACE_ERR_ARG, "trace_decode_admit: slot " + std::to_string(slots[i]) + " is already in the running batch");
-        for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(TRACE_ERR_ARG, "trace_decode_admit: duplicate slot");
-        if (heads[i] < 0 || heads[i] > 2) return fail(TRACE_ERR_ARG, "trace_decode_admit: head must be 0, 1 or 2");
         if (row_ids[i] < 0) return fail(TRACE_ERR_ARG, "trace_decode_admit: row_ids must not be negative");
-        pos[i] = c->slot_len[slots[i]];
-        if (per_row) {
-            const trace_row_params* r = reinterpret_cast<const trace_row_params*>(reinterpret_cast<const char*>(rows) + (size_t)i * rows[0].size);   // (the caller's stride)
-            if (r->size != rows[0].size) return fail(TRACE_ERR_ARG, "trace_decode_admit_ex: every trace_row_params must carry the same size");
-            if (const char* e = row_params_convert(*r, max_new, rsp[i], rlp[i], rmx[i])) return fail(TRACE_ERR_ARG, "trace_decode_admit_ex: row " + std::to_string(i) + ": " + e);
-        }
-        if (pos[i] + (per_row ? rmx[i] : max_new) > c->max_ctx) return fail(TRACE_ERR_ARG, "trace_decode_admit: prefill + max_new_tokens exceeds max_ctx");
-        org[i] = c->steps_done;
     }
-    if (per_row) {
-        if (const char* e = row_forced_bad(c, forced, n, max_new, rlp.data(), rmx.data())) return fail(TRACE_ERR_ARG, std::string("trace_decode_admit_ex: ") + e);
-    } else if (forced && (c->armed.process || c->armed.stop))
+    if (!per_row && forced && (c->armed.process || c->armed.stop))
         return fail(TRACE_ERR_ARG, "trace_decode_admit: forced ids with logits processors / constraints armed: the history is the recorded ids, not the fed ones");
     hipStream_t s = (hipStream_t)stream;
-    if (per_row) {      // host copies behind the batch's rows first (the copies below read them), then the device entries [B, B + n)
-        for (int i = 0; i < n; ++i) {
-            c->h_row_sp[B + i] = rsp[i]; c->h_row_lp[B + i] = rlp[i]; c->h_row_max[B + i] = rmx[i];
-            if (logits_armed(rlp[i])) c->armed.process = true;       // from here on logits_process runs for the batch (a tail of its own graph place)
-        }
-        HIPCHK(hipMemcpyAsync(c->d_row_sp + B, c->h_row_sp + B, n * sizeof(SampleParams), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_row_lp + B, c->h_row_lp + B, n * sizeof(LogitsParams), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_row_max + B, c->h_row_max + B, n * 4, hipMemcpyHostToDevice, s));
-    }
-    const size_t wide0 = (size_t)B * max_new, wide_n = (size_t)n * max_new;
-    HIPCHK(hipMemcpyAsync(c->d_slots + B, slots, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_row_id + B, row_ids, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_pos + B, pos, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_heads + B, heads, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_done + B, zero, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_out_len + B, zero, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_step0 + B, org, n * 4, hipMemcpyHostToDevice, s));
+    const int32_t zero[2] = {0, 0};
+    if (q.procs) c->armed.process = true;            // from here on logits_process runs for the batch (a tail of its own graph place)
     HIPCHK(hipMemcpyAsync(c->d_step + 2, zero, 8, hipMemcpyHostToDevice, s));          // the spare counter pair of the admission's own selection
-    HIPCHK(hipMemsetAsync(c->d_out_ids + wide0, 0, wide_n * 4, s));
-    if (c->armed.logprobs) HIPCHK(hipMemsetAsync(c->d_logprobs + wide0, 0, wide_n * 4, s));
-    if (forced) HIPCHK(hipMemcpyAsync(c->d_forced + wide0, forced, wide_n * 4, hipMemcpyHostToDevice, s));
-    else HIPCHK(hipMemsetAsync(c->d_forced + wide0, 0xff, wide_n * 4, s));
-    for (int i = 0; i < n; ++i)
-        HIPCHK(hipMemcpyAsync(c->dH + (size_t)(B + i) * c->H, c->xlast + (size_t)slots[i] * c->H, (size_t)c->H * 2, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));     // host arrays above must outlive the async copies
-    TRY(head_and_select(c, c->dH + (size_t)B * c->H, 0, nullptr, s, TailRows{B, n}));
-    for (int i = 0; i < n; ++i) { c->h_pos0[B + i] = pos[i]; c->h_step0[B + i] = org[i]; c->h_slots[B + i] = slots[i]; c->pos_sum += pos[i]; }
+    TRY(seat_write(c, B, n, slots, heads, row_ids, forced, c->steps_done, q, nullptr, s));
     c->B = B + n; c->admitted += n;
-    if (forced) c->has_forced = 1;
     return TRACE_OK;
 }
 
@@ -1960,6 +1958,20 @@ extern "C" int trace_debug_step_graphs(trace_ctx* c, int32_t* sizes, int cap) {
     }
     return n;
 }
+
+// Debugging aid: one column of row_cols for rows [0, B) of the running batch, as ints, into out[0 .. cap) (HOST); synchronous.  Returns the column's ints
+// a row, or 0 (nothing written) for a column the armed mode does not have.  trace_debug_decode_column(ctx, i) names column i, NULL past the end.
+extern "C" int trace_debug_decode_rows(trace_ctx* c, int column, int32_t* out, int cap) {
+    if (!c || c->B < 1) return fail(TRACE_ERR_STATE, "trace_decode_begin not called");
+    if (column < 0 || column >= N_COLS || !out) return fail(TRACE_ERR_ARG, "trace_debug_decode_rows: bad column / out");
+    const RowCol k = row_cols(c)[column];
+    if (!k.on) return 0;
+    if ((size_t)cap < (size_t)c->B * k.ints) return fail(TRACE_ERR_ARG, "trace_debug_decode_rows: cap is below B x " + std::to_string(k.ints) + " ints");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, k.dev, (size_t)c->B * k.ints * 4, hipMemcpyDeviceToHost));
+    return k.ints;
+}
+extern "C" const char* trace_debug_decode_column(trace_ctx* c, int i) { return c && i >= 0 && i < N_COLS ? row_cols(c)[i].name : nullptr; }
 
 extern "C" int trace_decode_read(trace_ctx* c, int32_t* out_ids, int32_t* out_len, int32_t* heads, void* stream) {
     if (!c || c->B < 1) return fail(TRACE_ERR_STATE, "trace_decode_begin not called");
