@@ -492,6 +492,22 @@ int trace_op_rmsnorm(const void* x, void* y, const void* w, int rows, int D, flo
 int trace_op_layernorm_ex(const void* x, int ldx, void* y, int ldy, const void* w, const void* b, int rows, int D, float eps, int silu,
                           const void* res, int ldres, void* stream);
 int trace_op_rmsnorm_ex(const void* x, int ldx, void* y, int ldy, const void* w, int rows, int D, float eps, void* stream);
+/* The STC connector's row kernels, each alone, as trace_stc_connector calls them.  Channels-last rows of the 16-bit element type, contiguous;
+ * fp32 arithmetic, one rounding at the store.  TRACE_ERR_ARG, before any launch, for a null tensor, a non-positive extent, a C that is not a
+ * positive multiple of 8 (64 for the pool) or an act outside 0..3.
+ *   dwconv3x3          y [N, H, W, C] = depthwise 3 x 3, pad 1, stride 1 of x [N, H, W, C]; w [C, 9] (Conv2d weight [C, 1, 3, 3])
+ *   avgpool            y [N, C] = mean over the HW pixels of x [N, HW, C] (N <= 65535)
+ *   bias_act           x [rows, C] = act(x + bias) in place; bias [C] or NULL; act 0 none, 1 SiLU, 2 sigmoid, 3 GELU (exact erf form)
+ *   scale_rows         x [N, HW, C] *= gate [N, C] in place
+ *   im2col3d           A [To Ho Wo, 8 C] = the 2 x 2 x 2 patches of x [T, H, W, C] for Conv3d(kernel 2, stride 2, padding 1): To = T / 2 + 1 (Ho, Wo
+ *                      alike), column ((kt 2 + kh) 2 + kw) C + c = x[2 to - 1 + kt][2 yo - 1 + kh][2 xo - 1 + kw][c], zero outside x (zeros are written)
+ *   permute_conv3d_w   out [Co, 8, Ci] = Conv3d weight w [Co, Ci, 2, 2, 2] in im2col3d's column order (tap = (kt 2 + kh) 2 + kw) */
+int trace_op_dwconv3x3(const void* x, const void* w, void* y, int N, int H, int W, int C, void* stream);
+int trace_op_avgpool(const void* x, void* y, int N, int HW, int C, void* stream);
+int trace_op_bias_act(void* x, const void* bias, int64_t rows, int C, int act, void* stream);
+int trace_op_scale_rows(void* x, const void* gate, int N, int HW, int C, void* stream);
+int trace_op_im2col3d(const void* x, void* A, int T, int H, int W, int C, void* stream);
+int trace_op_permute_conv3d_w(const void* w, void* out, int Co, int Ci, void* stream);
 /* SpatialSlotPool before `readout` (trace_slot_pool without its GEMM): feats + t * frame_stride + p * row_stride is patch p of frame t (elements;
  * frame_stride a multiple of 8, row_stride a multiple of 8 and >= D), ln_w / ln_b [D], slots [D, 8], cos_t / sin_t fp32 [n, D / 2] (the caller's
  * tables), res_out [T, 8, D], D a multiple of 16 up to 1024.  ws: trace_op_slot_pool_ws_floats(T, D) floats of device scratch. */

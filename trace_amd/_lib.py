@@ -125,6 +125,12 @@ SIGNATURES = {
     "trace_op_rmsnorm": (I, [P, P, P, I, I, F, P]),
     "trace_op_layernorm_ex": (I, [P, I, P, I, P, P, I, I, F, I, P, I, P]),
     "trace_op_rmsnorm_ex": (I, [P, I, P, I, P, I, I, F, P]),
+    "trace_op_dwconv3x3": (I, [P, P, P, I, I, I, I, P]),
+    "trace_op_avgpool": (I, [P, P, I, I, I, P]),
+    "trace_op_bias_act": (I, [P, P, C.c_int64, I, I, P]),
+    "trace_op_scale_rows": (I, [P, P, I, I, I, P]),
+    "trace_op_im2col3d": (I, [P, P, I, I, I, I, P]),
+    "trace_op_permute_conv3d_w": (I, [P, P, I, I, P]),
     "trace_op_slot_pool_ws_floats": (C.c_int64, [I, I]),
     "trace_op_slot_pool": (I, [P, C.c_int64, I, P, P, P, P, P, P, I, I, I, F, P, C.c_int64, P]),
     "trace_op_patch_embed_ws_elems": (C.c_int64, [I, I]),

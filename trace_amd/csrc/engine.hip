@@ -2468,6 +2468,44 @@ extern "C" int trace_op_rmsnorm_ex(const void* x, int ldx, void* y, int ldy, con
     LCHK(launch_rmsnorm((const bf16_t*)x, ldx, (bf16_t*)y, ldy, (const bf16_t*)w, rows, D, eps, (hipStream_t)stream));
     return TRACE_OK;
 }
+// The STC connector's row kernels (stc.hip), each alone on loose tensors, as stc_block / trace_stc_connector call them.  Every refusal comes before any launch.
+extern "C" int trace_op_dwconv3x3(const void* x, const void* w, void* y, int N, int H, int W, int C, void* stream) {
+    if (!x || !w || !y) return fail(TRACE_ERR_ARG, "null argument");
+    if (N < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail(TRACE_ERR_ARG, "dwconv3x3: N, H, W >= 1 and C a positive multiple of 8");
+    LCHK(launch_dwconv3x3((const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, N, H, W, C, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_avgpool(const void* x, void* y, int N, int HW, int C, void* stream) {
+    if (!x || !y) return fail(TRACE_ERR_ARG, "null argument");
+    if (N < 1 || N > 65535 || HW < 1 || C < 64 || C % 64) return fail(TRACE_ERR_ARG, "avgpool: 1 <= N <= 65535, HW >= 1 and C a positive multiple of 64");
+    LCHK(launch_avgpool((const bf16_t*)x, (bf16_t*)y, N, HW, C, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_bias_act(void* x, const void* bias, int64_t rows, int C, int act, void* stream) {
+    if (!x) return fail(TRACE_ERR_ARG, "null argument");
+    if (rows < 1 || C < 8 || C % 8) return fail(TRACE_ERR_ARG, "bias_act: rows >= 1 and C a positive multiple of 8");
+    if (act < ACT_NONE || act > ACT_GELU) return fail(TRACE_ERR_ARG, "bias_act: act is 0 (none), 1 (SiLU), 2 (sigmoid) or 3 (GELU)");
+    LCHK(launch_bias_act((bf16_t*)x, (const bf16_t*)bias, (long)rows, C, act, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_scale_rows(void* x, const void* gate, int N, int HW, int C, void* stream) {
+    if (!x || !gate) return fail(TRACE_ERR_ARG, "null argument");
+    if (N < 1 || HW < 1 || C < 8 || C % 8) return fail(TRACE_ERR_ARG, "scale_rows: N, HW >= 1 and C a positive multiple of 8");
+    LCHK(launch_scale_rows((bf16_t*)x, (const bf16_t*)gate, N, HW, C, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_im2col3d(const void* x, void* A, int T, int H, int W, int C, void* stream) {
+    if (!x || !A) return fail(TRACE_ERR_ARG, "null argument");
+    if (T < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail(TRACE_ERR_ARG, "im2col3d: T, H, W >= 1 and C a positive multiple of 8");
+    LCHK(launch_im2col3d((const bf16_t*)x, (bf16_t*)A, T, H, W, C, T / 2 + 1, H / 2 + 1, W / 2 + 1, (hipStream_t)stream));
+    return TRACE_OK;
+}
+extern "C" int trace_op_permute_conv3d_w(const void* w, void* out, int Co, int Ci, void* stream) {
+    if (!w || !out) return fail(TRACE_ERR_ARG, "null argument");
+    if (Co < 1 || Ci < 1) return fail(TRACE_ERR_ARG, "permute_conv3d_w: Co, Ci >= 1");
+    LCHK(launch_permute_conv3d_w((const bf16_t*)w, (bf16_t*)out, Co, Ci, (hipStream_t)stream));
+    return TRACE_OK;
+}
 // launch_slot_pool alone (no readout GEMM): res_out [T, 8, D].  ws: trace_op_slot_pool_ws_floats(T, D) floats.
 extern "C" int64_t trace_op_slot_pool_ws_floats(int T, int D) { return T > 0 && D > 0 ? (int64_t)launch_slot_pool_ws_floats(T, D) : (int64_t)TRACE_ERR_ARG; }
 extern "C" int trace_op_slot_pool(const void* feats, int64_t frame_stride, int row_stride, const void* ln_w, const void* ln_b, const void* slots,

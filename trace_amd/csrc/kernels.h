@@ -346,7 +346,6 @@ int launch_dwconv3x3(const bf16_t* x, const bf16_t* w /*[C][9]*/, bf16_t* y, int
 int launch_avgpool(const bf16_t* x, bf16_t* y /*[N][C]*/, int N, int HW, int C, hipStream_t s);
 int launch_bias_act(bf16_t* x, const bf16_t* bias, long rows, int C, int act, hipStream_t s);
 int launch_scale_rows(bf16_t* x, const bf16_t* gate /*[N][C]*/, int N, int HW, int C, hipStream_t s);
-int launch_add_act(bf16_t* x, const bf16_t* y, long n, int act, hipStream_t s);
 int launch_im2col3d(const bf16_t* x, bf16_t* A, int T, int H, int W, int C, int To, int Ho, int Wo, hipStream_t s);
 int launch_permute_conv3d_w(const bf16_t* w, bf16_t* out, int Co, int Ci, hipStream_t s);
 

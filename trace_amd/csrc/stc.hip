@@ -2,7 +2,7 @@
 // path).  Everything GEMM-shaped in the connector (1x1 convs, the 2x2x2 stride-2 Conv3d as an im2col GEMM, the SE
 // fully-connected layers, the readout MLP) runs on the MFMA kernels of gemm.hip / decode.hip; what is left are
 // HBM-bound channels-last row kernels: depthwise 3x3, global average pool, bias/activation, SE scaling,
-// residual + SiLU, the Conv3d patch gather, and a one-off weight permute.  Layout: [frame][h][w][C] bf16.
+// the Conv3d patch gather, and a one-off weight permute.  Layout: [frame][h][w][C] bf16.
 #include "common.h"
 #include "kernels.h"
 
@@ -119,19 +119,6 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(bf16_t* __restrict__ x,
     }
 }
 
-// x = act(x + y)
-__global__ __launch_bounds__(256) void add_act_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict__ y, long n8, int act) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
-        float a[8], b[8];
-        uint4* p = reinterpret_cast<uint4*>(x) + i;
-        unpack8(*p, a);
-        unpack8(reinterpret_cast<const uint4*>(y)[i], b);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = act_fn(a[e] + b[e], act);
-        *p = pack8(a);
-    }
-}
-
 // Conv3d k = s = 2, p = 1 gather: A[(to, yo, xo)][((kt*2+kh)*2+kw)*C + c] = x[2to-1+kt][2yo-1+kh][2xo-1+kw][c] (0 outside)
 __global__ __launch_bounds__(256) void im2col3d_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ A, int T, int H, int W,
                                                        int C, int To, int Ho, int Wo) {
@@ -168,37 +155,35 @@ int grid_for(long total) { return (int)((total + 255) / 256 < 8192 ? (total + 25
 
 #define DONE return hipGetLastError() == hipSuccess ? TRACE_OK : TRACE_ERR_HIP
 
+// Every launcher refuses what its kernel cannot take before it launches: a non-positive extent, a channel count that is not whole 16-byte chunks
 int launch_dwconv3x3(const bf16_t* x, const bf16_t* w, bf16_t* y, int N, int H, int W, int C, hipStream_t s) {
-    if (C % 8 || N < 1) return TRACE_ERR_ARG;
+    if (C < 8 || C % 8 || N < 1 || H < 1 || W < 1) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(dwconv3x3_kernel, dim3(grid_for((long)N * H * W * (C / 8))), dim3(256), 0, s, x, w, y, N, H, W, C);
     DONE;
 }
 int launch_avgpool(const bf16_t* x, bf16_t* y, int N, int HW, int C, hipStream_t s) {
-    if (C % 64 || N < 1) return TRACE_ERR_ARG;
+    if (C < 64 || C % 64 || N < 1 || N > 65535 || HW < 1) return TRACE_ERR_ARG;       // (N is the grid's y extent; HW divides)
     hipLaunchKernelGGL(avgpool_kernel, dim3(C / 64, N), dim3(256), 0, s, x, y, HW, C);
     DONE;
 }
 int launch_bias_act(bf16_t* x, const bf16_t* bias, long rows, int C, int act, hipStream_t s) {
-    if (C % 8 || rows < 1) return TRACE_ERR_ARG;
+    if (C < 8 || C % 8 || rows < 1 || act < ACT_NONE || act > ACT_GELU) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(bias_act_kernel, dim3(grid_for(rows * (C / 8))), dim3(256), 0, s, x, bias, rows, C, act);
     DONE;
 }
 int launch_scale_rows(bf16_t* x, const bf16_t* gate, int N, int HW, int C, hipStream_t s) {
-    if (C % 8) return TRACE_ERR_ARG;
+    if (C < 8 || C % 8 || N < 1 || HW < 1) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(scale_rows_kernel, dim3(grid_for((long)N * HW * (C / 8))), dim3(256), 0, s, x, gate, N, HW, C);
     DONE;
 }
-int launch_add_act(bf16_t* x, const bf16_t* y, long n, int act, hipStream_t s) {
-    if (n % 8) return TRACE_ERR_ARG;
-    hipLaunchKernelGGL(add_act_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, x, y, n / 8, act);
-    DONE;
-}
 int launch_im2col3d(const bf16_t* x, bf16_t* A, int T, int H, int W, int C, int To, int Ho, int Wo, hipStream_t s) {
-    if (C % 8) return TRACE_ERR_ARG;
+    if (C < 8 || C % 8 || T < 1 || H < 1 || W < 1) return TRACE_ERR_ARG;
+    if (To != T / 2 + 1 || Ho != H / 2 + 1 || Wo != W / 2 + 1) return TRACE_ERR_ARG;       // k = s = 2, p = 1: the output extents the kernel's taps belong to
     hipLaunchKernelGGL(im2col3d_kernel, dim3(grid_for((long)To * Ho * Wo * 8 * (C / 8))), dim3(256), 0, s, x, A, T, H, W, C, To, Ho, Wo);
     DONE;
 }
 int launch_permute_conv3d_w(const bf16_t* w, bf16_t* out, int Co, int Ci, hipStream_t s) {
+    if (Co < 1 || Ci < 1) return TRACE_ERR_ARG;
     hipLaunchKernelGGL(permute_conv3d_w_kernel, dim3(grid_for((long)Co * Ci * 8)), dim3(256), 0, s, w, out, Co, Ci);
     DONE;
 }

@@ -1473,6 +1473,72 @@ class ops:
         _lib.check(lib.trace_op_rmsnorm_ex(_ptr(x), x.stride(0), _ptr(y), y.stride(0), _ptr(w), x.shape[0], x.shape[1], float(eps), _stream()))
         return y
 
+    # ---- the STC connector's row kernels (trace_hip.h: "The STC connector's row kernels, each alone") ----
+    # Tensors are contiguous and of the element type; the extents come from their shapes unless `dims` gives them (a test of the op's own refusals
+    # passes extents the tensors do not have: the op answers TRACE_ERR_ARG before it touches anything).
+    @staticmethod
+    def _stc(*tensors):
+        for t in tensors:
+            if t is not None and (not t.is_contiguous() or t.dtype != ops.dtype()):
+                raise ValueError("STC row ops: contiguous tensors of the element type")
+        return _lib.load(ops.element)
+
+    @staticmethod
+    def dwconv3x3(x, w, out=None, dims=None):
+        """trace_op_dwconv3x3: x [N, H, W, C], w [C, 9] (or [C, 1, 3, 3]) -> y [N, H, W, C] (`out`: where to store)"""
+        y = torch.empty_like(x) if out is None else out
+        lib = ops._stc(x, w, y)
+        N, H, W, Cn = x.shape if dims is None else dims
+        _lib.check(lib.trace_op_dwconv3x3(_ptr(x), _ptr(w), _ptr(y), int(N), int(H), int(W), int(Cn), _stream()))
+        return y
+
+    @staticmethod
+    def avgpool(x, out=None, dims=None):
+        """trace_op_avgpool: x [N, HW, C] -> y [N, C]"""
+        y = torch.empty((x.shape[0], x.shape[-1]), dtype=x.dtype, device=x.device) if out is None else out
+        lib = ops._stc(x, y)
+        N, HW, Cn = x.shape if dims is None else dims
+        _lib.check(lib.trace_op_avgpool(_ptr(x), _ptr(y), int(N), int(HW), int(Cn), _stream()))
+        return y
+
+    @staticmethod
+    def bias_act(x, bias, act, dims=None):
+        """trace_op_bias_act, in place: x [rows, C] = act(x + bias); bias [C] or None; act 0 none, 1 SiLU, 2 sigmoid, 3 GELU (exact erf)"""
+        lib = ops._stc(x, bias)
+        rows, Cn = x.shape if dims is None else dims
+        _lib.check(lib.trace_op_bias_act(_ptr(x), _ptr(bias), int(rows), int(Cn), int(act), _stream()))
+        return x
+
+    @staticmethod
+    def scale_rows(x, gate, dims=None):
+        """trace_op_scale_rows, in place: x [N, HW, C] *= gate [N, C]"""
+        lib = ops._stc(x, gate)
+        N, HW, Cn = x.shape if dims is None else dims
+        _lib.check(lib.trace_op_scale_rows(_ptr(x), _ptr(gate), int(N), int(HW), int(Cn), _stream()))
+        return x
+
+    @staticmethod
+    def im2col3d(x, out=None, dims=None):
+        """trace_op_im2col3d: x [T, H, W, C] -> A [(T // 2 + 1) (H // 2 + 1) (W // 2 + 1), 8 C], the patches of Conv3d(kernel 2, stride 2, padding 1);
+        `out`: a buffer of at least that many elements to store into"""
+        T, H, W, Cn = x.shape if dims is None else dims
+        rows = (T // 2 + 1) * (H // 2 + 1) * (W // 2 + 1)
+        A = torch.empty((rows, 8 * Cn), dtype=x.dtype, device=x.device) if out is None else out
+        lib = ops._stc(x, A)
+        if dims is None and A.numel() < rows * 8 * Cn:
+            raise ValueError("out: room for [To Ho Wo, 8 C]")
+        _lib.check(lib.trace_op_im2col3d(_ptr(x), _ptr(A), int(T), int(H), int(W), int(Cn), _stream()))
+        return A if out is None else A.view(-1)[:rows * 8 * Cn].view(rows, 8 * Cn)
+
+    @staticmethod
+    def permute_conv3d_w(w, out=None, dims=None):
+        """trace_op_permute_conv3d_w: Conv3d weight w [Co, Ci, 2, 2, 2] -> [Co, 8 Ci] (im2col3d's column order)"""
+        Co, Ci = w.shape[:2] if dims is None else dims
+        o = torch.empty((Co, 8 * Ci), dtype=w.dtype, device=w.device) if out is None else out
+        lib = ops._stc(w, o)
+        _lib.check(lib.trace_op_permute_conv3d_w(_ptr(w), _ptr(o), int(Co), int(Ci), _stream()))
+        return o
+
     # ---- the prefill's cache-write kernels (trace_hip.h: "the prefill's cache-write kernels, each alone") ----
     # Every array is a contiguous tensor whose numel() is the element count the library checks against and whose data_ptr() is the base the kernel gets:
     # an offset into a larger buffer is a slice of its flat view (buf.view(-1)[off:]).  Strides and offsets go through as given.
